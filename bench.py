@@ -13,8 +13,14 @@ input.  Before timing, one untimed "epoch 0" pass over the key space pushes feat
 (kFeaCount) so the model is in its steady state (every key has V); then W warmup steps and K
 timed steps run on fresh batches (epoch >= 1, no count push), as in the reference.
 
-Prints one JSON line (driver contract) with a roofline object for the dominant kernel and a
-cpu_baseline (the oracle restatement timed on this host on a bounded sample).
+A plain run does only what the headline figure needs: set-up, the count-push epoch, the warmup
+and the K timed steps, then one JSON line (driver contract) with the throughput, ms_per_step
+and what the timed steps themselves recorded.  --dump-outputs DIR also writes what the last
+timed step returned to its caller (DIR/<name>.npy; the inputs are seeded, so two builds can be
+compared output for output).  --full adds everything that takes runs of its own: the untimed
+step-window and diagnostic passes behind the roofline objects, the host's call cost on an
+idle device, the sharded store's other schedules and the cpu_baseline (the oracle restatement
+timed on this host on a bounded sample).
 """
 import argparse
 import json
@@ -47,7 +53,17 @@ def parse():
     ap.add_argument("--nnz", type=int, default=None)
     ap.add_argument("--key-bits", type=int, default=None)
     ap.add_argument("--vdim", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the step-window and "
+                         "diagnostic passes (per-phase times, lanes, rooflines), the host's call "
+                         "cost on an idle device, the sharded store's other schedules, the CPU "
+                         "baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned to its caller "
+                         "as DIR/<name>.npy (float32 / float64): its predictions, the progress "
+                         "of the timed steps and the model over a seeded sample of its keys")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU baseline (a plain run has none)")
     ap.add_argument("--sharded", action="store_true",
                     help="use the key-range-sharded store even at N=1 (default for N>1)")
     ap.add_argument("--sync", action="store_true",
@@ -343,6 +359,43 @@ def cpu_baseline(args):
                       % (nb * args.cpu_batch, nb, args.cpu_batch)}
 
 
+DUMP_MODEL_BYTES = 32 << 20  # --dump-outputs: the model sample's share of the 64 MB bound
+DUMP_SEED = 20240229
+
+
+def write_outputs(dirname, arrays):
+    """--dump-outputs: DIR/<name>.npy, float32 or float64"""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def progress_array(prog):
+    """sgd::Progress of the timed steps: [rows, summed logloss, summed AUC * rows]"""
+    return np.array([prog["nrows"], prog["loss"], prog["auc"]], np.float64)
+
+
+def fused_outputs(torch, H, ctx, last, pred, prog):
+    """What a caller of the timed dfx_train_step calls holds after the last one: its
+    predictions (pred_out), the progress the K steps accumulated, and the model it updated —
+    Store::Pull ([w | V] values and their lens) over a fixed, seeded sample of the last batch's
+    sorted unique keys, sized so that the arrays stay well under 64 MB"""
+    d = ctx.V_dim
+    _, uniq, _ = H.Localizer(ctx).compact(last, want_cnt=False)
+    U = uniq.numel()
+    n = min(U, DUMP_MODEL_BYTES // (4 * (1 + d)))
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(U, n, replace=False))
+    keys = uniq[torch.from_numpy(pick).to(uniq.device)].contiguous()
+    vals, lens = H.Store(ctx).pull(keys)
+    out = {"pred": pred.cpu().numpy(), "progress": progress_array(prog),
+           "model_vals": vals.cpu().numpy()}
+    if lens is not None:
+        out["model_lens"] = lens.cpu().numpy().astype(np.float32)
+    return out
+
+
 def step_window(torch, dev, world, batches, run):
     """The timed window's shape (untimed replay of the same K steps, same barrier + sync
     bracket): one event on the main stream after each step's enqueue, so the K intervals are
@@ -445,10 +498,11 @@ def main():
     ctx.reserve(B, B * k)
     lib = H._lib.lib()
 
-    def step(batch, push_cnt):
+    def step(batch, push_cnt, pred=None):
         b = batch.as_batch()
         H.check(lib.dfx_train_step(ctx.h, ctypes.byref(b), H.kTraining, int(push_cnt),
-                                   ctypes.c_uint64(H.MAX_INDEX), None))
+                                   ctypes.c_uint64(H.MAX_INDEX),
+                                   None if pred is None else ctypes.c_void_p(pred.data_ptr())))
 
     # Batches come from a loader stream (as a reader's host->device copies would): the
     # library's Localizer lane waits only for that stream, so it overlaps the previous batch's
@@ -489,6 +543,10 @@ def main():
         live.append(make(2_000_000 * (rank + 1) + i))
         step(live[-1], False)
     batches = [make(3_000_000 * (rank + 1) + i) for i in range(args.steps)]
+    # --dump-outputs: the last timed step also hands its predictions to the caller (pred_out)
+    preds = [None] * args.steps
+    if args.dump_outputs:
+        preds[-1] = torch.zeros(B, dtype=torch.float32, device=dev)
     torch.cuda.synchronize()
     live.clear()
     H.prof_read(ctx)
@@ -505,8 +563,8 @@ def main():
     torch.cuda.synchronize()
     H.prof_host(ctx)
     t0 = time.perf_counter()
-    for bt in batches:
-        step(bt, False)
+    for bt, pr in zip(batches, preds):
+        step(bt, False, pr)
     t_enq = time.perf_counter() - t0
     host_wait = H.prof_host(ctx)
     torch.cuda.synchronize()
@@ -521,6 +579,63 @@ def main():
     phases, nrec, mean_u = H.prof_read(ctx)
     bwd_ms = phases["backward_update"]
     prog = H.progress(ctx)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs,
+                      fused_outputs(torch, H, ctx, batches[-1], preds[-1], prog))
+    value = world * B * args.steps / elapsed
+    out = {
+        "metric": "train examples/sec (FM V_dim=16) at 1/8 GPU + achieved HBM GB/s",
+        "value": round(value, 1),
+        "unit": "train examples/sec",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic (device-generated, resident in HBM before timing)",
+        "config": {"workload": (cf["name"] % dict(vdim=d, nnz=k, key_bits=kb))
+                               + ", fused dfx_train_step",
+                   "config": args.config,
+                   "rows_per_gpu_step": B, "global_batch": B * world,
+                   "parallelism": "single GPU"},
+        # what the timed steps themselves recorded (no run of its own behind any of it)
+        "phases_ms_per_step": {"backward_update": round(bwd_ms / max(nrec, 1), 4)},
+        "cold_epoch_ms_per_step": round(t_warm / n_warm_epoch * 1e3, 4),
+        "host_enqueue_ms_per_step": round(t_enq / args.steps * 1e3, 4),
+        # the host's own work per step: the calls' time less their waits on the capacity guard
+        # (which lets the host run a few steps ahead of the device, then blocks it)
+        "host_busy_ms_per_step": round((t_enq - host_wait["wait_s"]) / args.steps * 1e3, 4),
+        "host_waits": host_wait["waits"],
+        "mean_unique_keys": round(mean_u, 1),
+        "chunk_model": (chunk_model(B * k, mean_u, elapsed / args.steps * 1e3)
+                        if args.config == "c3" else None),
+        "train_loss_per_row": round(prog["loss"] / max(prog["nrows"], 1), 6),
+        "train_auc": round(prog["auc"] / max(prog["nrows"], 1), 6),
+    }
+    if args.full:
+        out.update(fused_full(args, torch, H, ctx, dev, world, batches, step, cf,
+                              bwd_ms, nrec, mean_u))
+    ctx.sync()
+    st = H.Store(ctx).stats()
+    out["model_keys"], out["model_vrows"] = st["n_keys"], st["n_vrows"]
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline \
+            and args.config == "c3":
+        out["cpu_baseline"] = cpu_baseline(args)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    ctx.close()
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def fused_full(args, torch, H, ctx, dev, world, batches, step, cf, bwd_ms, nrec, mean_u):
+    """--full, the fused step: the untimed passes over the timed batches again (the step
+    window, every phase and the lanes, the host's call cost on an idle device) and the
+    rooflines priced with them"""
+    B, k, d = args.batch, args.nnz, args.vdim
     window = step_window(torch, dev, world, batches, lambda bt: step(bt, False))
     # the per-step counters restart here: the live-V counts below are the diagnostic pass's
     # alone, and so must be the step count they are divided by (the window's steps counted
@@ -549,33 +664,13 @@ def main():
     torch.cuda.synchronize()
     host_idle.sort()
     H.progress(ctx)
-    ctx.sync()
-    st = H.Store(ctx).stats()
 
-    value = world * B * args.steps / elapsed
     per_launch_ms = {p: phases[p] / max(nrec, 1) for p in phases}
     ab = algorithmic_bytes(B, B * k, mean_u, d, cf["valued"], counts["U_V"], counts["occ_V"])
     dom = max(ab, key=lambda p: per_launch_ms[p])
     achieved = ab[dom] / (max(per_launch_ms[dom], 1e-9) * 1e-3) / 1e9
     pmc_file = "pmc_hbm.json" if args.config == "c3" else "pmc_hbm_%s.json" % args.config
     out = {
-        "metric": "train examples/sec (FM V_dim=16) at 1/8 GPU + achieved HBM GB/s",
-        "value": round(value, 1),
-        "unit": "train examples/sec",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic (device-generated, resident in HBM before timing)",
-        "config": {"workload": (cf["name"] % dict(vdim=d, nnz=k, key_bits=kb))
-                               + ", fused dfx_train_step",
-                   "config": args.config,
-                   "rows_per_gpu_step": B, "global_batch": B * world,
-                   "parallelism": "single GPU"},
         "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1),
                      "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBS, 4),
@@ -595,23 +690,11 @@ def main():
         "roofline_forward": forward_roofline(ab["forward"], per_launch_ms["forward"],
                                              args.config),
         "phases_ms_per_step": {p: round(v, 4) for p, v in per_launch_ms.items()},
-        "cold_epoch_ms_per_step": round(t_warm / n_warm_epoch * 1e3, 4),
-        "host_enqueue_ms_per_step": round(t_enq / args.steps * 1e3, 4),
-        # the host's own work per step: the calls' time less their waits on the capacity guard
-        # (which lets the host run a few steps ahead of the device, then blocks it)
-        "host_busy_ms_per_step": round((t_enq - host_wait["wait_s"]) / args.steps * 1e3, 4),
-        "host_waits": host_wait["waits"],
         "host_call_ms_idle_device": round(host_idle[len(host_idle) // 2] * 1e3, 4),
         "lanes_ms": {k_: round(v, 4) for k_, v in lanes.items()},
         "step_window": window,
-        "mean_unique_keys": round(mean_u, 1),
         "mean_live_v_keys": counts["U_V"] and round(counts["U_V"], 1),
         "mean_live_v_occurrences": counts["occ_V"] and round(counts["occ_V"], 1),
-        "chunk_model": (chunk_model(B * k, mean_u, elapsed / args.steps * 1e3)
-                        if args.config == "c3" else None),
-        "train_loss_per_row": round(prog["loss"] / max(prog["nrows"], 1), 6),
-        "train_auc": round(prog["auc"] / max(prog["nrows"], 1), 6),
-        "model_keys": st["n_keys"], "model_vrows": st["n_vrows"],
     }
     if dom == "backward_update" and args.config == "c3":
         # the ceiling of this kernel is the random-line rate, not the byte peak: a key's 144 B
@@ -625,13 +708,7 @@ def main():
             "frac": round(lines / CHUNK_RMW_PER_S, 4),
             "source": "tools/membench/spanbench (cold caches): 3.48 M sorted keys x 2 lines in "
                       "329 us alone; a 256-B-span layout 331 us"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == "c3":
-        out["cpu_baseline"] = cpu_baseline(args)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    ctx.close()
-    if world > 1:
-        dist.destroy_process_group()
+    return out
 
 
 def run_sharded(args, torch, dist, dev, rank, world, local):
@@ -825,125 +902,131 @@ def run_sharded(args, torch, dist, dev, rank, world, local):
         fb_ms = sum(evs[i][FB[0] + 1].elapsed_time(evs[i][FB[1] + 1])
                     for i in range(args.steps)) / args.steps
     prog = H.progress(ctx)
+    used_cpp = store is not None
+    ph, colls = {}, {}
 
-    # diagnostic pass (untimed): every phase
-    evs = run_steps(range(-1, nph))
-    torch.cuda.synchronize()
-    if store is not None:
-        ph = {p: v / max(n, 1) for p, (v, n) in store.take_marks().items()}
-    else:
-        if split:
-            names = DI.SPLIT_PHASES if pipe is None else DI.SPLIT_PIPE_PHASES
+    if args.full:
+        # diagnostic pass (untimed): every phase
+        evs = run_steps(range(-1, nph))
+        torch.cuda.synchronize()
+        if store is not None:
+            ph = {p: v / max(n, 1) for p, (v, n) in store.take_marks().items()}
         else:
-            names = DI.PHASES if pipe is None else DI.PIPE_PHASES
-        ph = {p: sum(evs[i][j].elapsed_time(evs[i][j + 1]) for i in range(args.steps))
-              / args.steps for j, p in enumerate(names)}
-    H.progress(ctx)
-    # the other collective schedules on the same batches, bulk synchronous (short runs): the
-    # all-to-all-v step, and the north_star's literal union all-gather / reduce-scatter
-    # (dist.rsag_step) — the measured baseline of the exchange design
-    colls = {}
+            if split:
+                names = DI.SPLIT_PHASES if pipe is None else DI.SPLIT_PIPE_PHASES
+            else:
+                names = DI.PHASES if pipe is None else DI.PIPE_PHASES
+            ph = {p: sum(evs[i][j].elapsed_time(evs[i][j + 1]) for i in range(args.steps))
+                  / args.steps for j, p in enumerate(names)}
+        H.progress(ctx)
     if pipe is not None:
         pipe.flush()
     if split:  # the owner's share of the last step, for the roofline's bytes
         o_rows, o_nnz, o_uniq = shard.split_owner_stats(0)
-    nb = min(args.steps, 20)
     main_name = (("split_sync" if args.sync else "split_pipelined") if split else
                  ("a2a_sync" if args.sync else "a2a_pipelined"))
     if store is not None:
         main_name += "_cpp"
     if store is not None and args.stale and not args.sync:
         main_name = "split_stale_cpp"
-    py_pipe = [None]
+    if args.full:
+        # the other collective schedules on the same batches, bulk synchronous (short runs): the
+        # all-to-all-v step, and the north_star's literal union all-gather / reduce-scatter
+        # (dist.rsag_step) — the measured baseline of the exchange design
+        nb = min(args.steps, 20)
+        py_pipe = [None]
 
-    def py_split_pipelined(shards, dblks, comm_, job):
-        if py_pipe[0] is None:
-            py_pipe[0] = DI.SplitPipeline(shards, comm_)
-        py_pipe[0].submit(dblks, job)
+        def py_split_pipelined(shards, dblks, comm_, job):
+            if py_pipe[0] is None:
+                py_pipe[0] = DI.SplitPipeline(shards, comm_)
+            py_pipe[0].submit(dblks, job)
 
-    def cpp_other_slices(shards, dblks, comm_, job):
-        store.submit(dblks, job)
+        def cpp_other_slices(shards, dblks, comm_, job):
+            store.submit(dblks, job)
 
-    sched = [("split_sync", DI.split_step), ("a2a_sync", DI.sharded_step),
-             ("rsag_sync", DI.rsag_step)]
-    if store is not None and not args.sync:  # the same schedule driven from Python
-        sched.insert(0, ("split_pipelined_py", py_split_pipelined))
-        # the C++ driver with the other slicing (rows in 2 slices, each slice's exchanges
-        # beside the next slice's compute; or unsliced if the main run was sliced)
-        other_k = 1 if args.slices > 1 else 2
-        if not args.stale:  # (the stale schedule runs unsliced)
-            sched.insert(1, ("split_pipelined_cpp_slices%d" % other_k, cpp_other_slices))
-    for cname, fn in sched:
-        if cname == main_name or (cname != "a2a_sync" and args.push_agg != "sum"):
-            continue
-        if fn is cpp_other_slices:
-            store.set_slices(other_k)
-        for bt in batches[:2]:
-            fn([shard], [bt], comm, H.kTraining)
-        if py_pipe[0] is not None:
-            py_pipe[0].flush()
-        if fn is cpp_other_slices:
+        sched = [("split_sync", DI.split_step), ("a2a_sync", DI.sharded_step),
+                 ("rsag_sync", DI.rsag_step)]
+        if store is not None and not args.sync:  # the same schedule driven from Python
+            sched.insert(0, ("split_pipelined_py", py_split_pipelined))
+            # the C++ driver with the other slicing (rows in 2 slices, each slice's exchanges
+            # beside the next slice's compute; or unsliced if the main run was sliced)
+            other_k = 1 if args.slices > 1 else 2
+            if not args.stale:  # (the stale schedule runs unsliced)
+                sched.insert(1, ("split_pipelined_cpp_slices%d" % other_k, cpp_other_slices))
+        for cname, fn in sched:
+            if cname == main_name or (cname != "a2a_sync" and args.push_agg != "sum"):
+                continue
+            if fn is cpp_other_slices:
+                store.set_slices(other_k)
+            for bt in batches[:2]:
+                fn([shard], [bt], comm, H.kTraining)
+            if py_pipe[0] is not None:
+                py_pipe[0].flush()
+            if fn is cpp_other_slices:
+                store.flush()
+            torch.cuda.synchronize()
+            dist.barrier()
+            t1 = time.perf_counter()
+            for bt in batches[:nb]:
+                fn([shard], [bt], comm, H.kTraining)
+            if py_pipe[0] is not None:
+                py_pipe[0].flush()
+                py_pipe[0] = None
+            if fn is cpp_other_slices:
+                store.flush()
+                store.set_slices(args.slices)
+            torch.cuda.synchronize()
+            dist.barrier()
+            dt = time.perf_counter() - t1
+            t = torch.tensor([dt], dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX, group=comm.cgroup)
+            dt = float(t.item())
+            colls[cname] = {"ms_per_step": round(dt / nb * 1e3, 4),
+                            "value": round(world * B * nb / dt, 1), "steps": nb}
+        if store is not None and not args.sync and args.push_agg == "sum":
+            # the C++ driver's other pipelined schedule on the same batches, so that one N-GPU run
+            # reports both: the pipelined default (bulk-synchronous results) beside the 1-step-stale
+            # one (each step's exchanges beside the other step's compute; DESIGN.md (e) predicts
+            # ~0.8 of the fused step per GPU at N = 8 against ~0.7) — or the default when --stale
+            # ran the main line.  A store of its own (its own RCCL communicators) on the same shard.
+            other_stale = not args.stale
             store.flush()
-        torch.cuda.synchronize()
-        dist.barrier()
-        t1 = time.perf_counter()
-        for bt in batches[:nb]:
-            fn([shard], [bt], comm, H.kTraining)
-        if py_pipe[0] is not None:
-            py_pipe[0].flush()
-            py_pipe[0] = None
-        if fn is cpp_other_slices:
-            store.flush()
-            store.set_slices(args.slices)
-        torch.cuda.synchronize()
-        dist.barrier()
-        dt = time.perf_counter() - t1
-        t = torch.tensor([dt], dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX, group=comm.cgroup)
-        dt = float(t.item())
-        colls[cname] = {"ms_per_step": round(dt / nb * 1e3, 4),
-                        "value": round(world * B * nb / dt, 1), "steps": nb}
-    used_cpp = store is not None
-    if store is not None and not args.sync and args.push_agg == "sum":
-        # the C++ driver's other pipelined schedule on the same batches, so that one N-GPU run
-        # reports both: the pipelined default (bulk-synchronous results) beside the 1-step-stale
-        # one (each step's exchanges beside the other step's compute; DESIGN.md (e) predicts
-        # ~0.8 of the fused step per GPU at N = 8 against ~0.7) — or the default when --stale
-        # ran the main line.  A store of its own (its own RCCL communicators) on the same shard.
-        other_stale = not args.stale
-        store.flush()
-        store.close()
-        store = None
-        ids2 = torch.zeros(DI.SplitStore.rccl_ids_size(), dtype=torch.uint8)
-        if rank == 0:
-            ids2 = torch.frombuffer(bytearray(DI.SplitStore.rccl_ids()), dtype=torch.uint8)
-        dist.broadcast(ids2, src=0, group=comm.cgroup)
-        st2 = DI.SplitStore([shard], pipelined=True, stale=other_stale,
-                            rccl=(rank, world, ids2.numpy().tobytes(), args.force_collectives))
-        for bt in batches[:2]:
-            st2.submit([bt], H.kTraining)
-        st2.flush()
-        torch.cuda.synchronize()
-        dist.barrier()
-        t1 = time.perf_counter()
-        for bt in batches[:nb]:
-            st2.submit([bt], H.kTraining)
-        st2.flush()
-        torch.cuda.synchronize()
-        dist.barrier()
-        dt = time.perf_counter() - t1
-        t = torch.tensor([dt], dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX, group=comm.cgroup)
-        dt = float(t.item())
-        colls["split_stale_cpp" if other_stale else "split_pipelined_cpp"] = {
-            "ms_per_step": round(dt / nb * 1e3, 4), "value": round(world * B * nb / dt, 1),
-            "steps": nb}
-        st2.close()
+            store.close()
+            store = None
+            ids2 = torch.zeros(DI.SplitStore.rccl_ids_size(), dtype=torch.uint8)
+            if rank == 0:
+                ids2 = torch.frombuffer(bytearray(DI.SplitStore.rccl_ids()), dtype=torch.uint8)
+            dist.broadcast(ids2, src=0, group=comm.cgroup)
+            st2 = DI.SplitStore([shard], pipelined=True, stale=other_stale,
+                                rccl=(rank, world, ids2.numpy().tobytes(), args.force_collectives))
+            for bt in batches[:2]:
+                st2.submit([bt], H.kTraining)
+            st2.flush()
+            torch.cuda.synchronize()
+            dist.barrier()
+            t1 = time.perf_counter()
+            for bt in batches[:nb]:
+                st2.submit([bt], H.kTraining)
+            st2.flush()
+            torch.cuda.synchronize()
+            dist.barrier()
+            dt = time.perf_counter() - t1
+            t = torch.tensor([dt], dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX, group=comm.cgroup)
+            dt = float(t.item())
+            colls["split_stale_cpp" if other_stale else "split_pipelined_cpp"] = {
+                "ms_per_step": round(dt / nb * 1e3, 4), "value": round(world * B * nb / dt, 1),
+                "steps": nb}
+            st2.close()
     H.progress(ctx)
     ctx.sync()
     st = H.Store(ctx).stats()
     tot = comm.allreduce_sum([[prog["loss"], prog["auc"], prog["nrows"], float(st["n_keys"]),
                                float(st["n_vrows"]), float(max(shard._U))]])[0]
+    if args.dump_outputs and rank == 0:
+        # the sharded step hands its caller the progress alone (summed over the ranks)
+        write_outputs(args.dump_outputs,
+                      {"progress": progress_array(dict(nrows=tot[2], loss=tot[0], auc=tot[1]))})
     if split:
         # roofline of the owner's fused backward + update on this rank (the fused step's
         # backward formula over the owner's rows, keys and unique keys)

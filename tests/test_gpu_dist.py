@@ -473,7 +473,7 @@ def test_bench_two_ranks_gloo(collective, sync):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--standalone", "--local-addr", "127.0.0.1", "bench.py", "--gpus", "2",
            "--steps", "3", "--warmup", "1", "--batch", "20000", "--key-bits", "20",
-           "--backend", "gloo", "--no-cpu-baseline", "--collective", collective] + (
+           "--backend", "gloo", "--full", "--no-cpu-baseline", "--collective", collective] + (
                ["--sync"] if sync else [])
     r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
@@ -606,8 +606,9 @@ def test_bench_rccl_collectives_at_world_one(collective):
             cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
                    "--nproc-per-node", "1", "--standalone", "--local-addr", "127.0.0.1",
                    "bench.py", "--sharded", "--steps", "4", "--warmup", "1",
-                   "--batch", "20000", "--key-bits", "20", "--no-cpu-baseline", "--collective",
-                   collective, "--driver", driver] + (["--force-collectives"] if force else [])
+                   "--batch", "20000", "--key-bits", "20", "--full", "--no-cpu-baseline",
+                   "--collective", collective, "--driver", driver] + (
+                       ["--force-collectives"] if force else [])
             r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=300)
             assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
             lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

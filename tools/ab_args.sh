@@ -10,7 +10,7 @@ for i in $(seq 1 $ROUNDS); do
   for v in "${VS[@]}"; do
     IFS='|' read -r name args <<< "$v"
     log=gpurun_out/aba_${name}_$i.log
-    timeout -k 10 200 python3 bench.py --no-cpu-baseline $args > $log 2>&1 || exit 1
+    timeout -k 10 200 python3 bench.py --full --no-cpu-baseline $args > $log 2>&1 || exit 1
     logs+=($log)
   done
 done

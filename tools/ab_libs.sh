@@ -2,6 +2,8 @@
 # Same-box A/B/...: bench each library in $LIBS (paths; "tree" = the in-tree build) in turn,
 # ROUNDS interleaved rounds (default 2), $BENCH_ARGS each; prints value and phases per run
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" && mkdir -p gpurun_out
+# the summaries below read what only a --full bench run reports (phases, lanes, rooflines)
+BENCH_ARGS="--full $BENCH_ARGS"
 for i in $(seq 1 ${ROUNDS:-2}); do
   n=0
   for lib in $LIBS; do

@@ -5,6 +5,8 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 ROUNDS=${ROUNDS:-2}
+# the summaries below read what only a --full bench run reports (phases, lanes, rooflines)
+BENCH_ARGS="--full $BENCH_ARGS"
 IFS=';' read -ra VS <<< "$VARIANTS"
 logs=()
 for i in $(seq 1 $ROUNDS); do

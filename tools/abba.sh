@@ -4,6 +4,8 @@
 # `bench.py --no-cpu-baseline $BENCH_ARGS`; logs under gpurun_out/$TAG/
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 TAG=${TAG:-abba}; mkdir -p gpurun_out/$TAG
+# the summaries below read what only a --full bench run reports (phases, lanes, rooflines)
+BENCH_ARGS="--full $BENCH_ARGS"
 run() {  # A|B, index
   local log=gpurun_out/$TAG/$1_$2.log
   if [ $1 = A ]; then

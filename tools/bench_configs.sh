@@ -2,6 +2,8 @@
 # the bench's other BASELINE configs and the small-batch regime, one bench line each
 # (gpurun_out/cfg_<name>.log); BENCH_EXTRA: extra bench.py arguments for every line
 cd "${GRAFT_REPO_ROOT:-.}" && mkdir -p gpurun_out
+# the summaries below read what only a --full bench run reports (phases, lanes, rooflines)
+BENCH_EXTRA="--full $BENCH_EXTRA"
 run() {  # name, then bench arguments
   local name=$1; shift
   timeout -k 10 400 python3 bench.py --no-cpu-baseline $BENCH_EXTRA "$@" > gpurun_out/cfg_$name.log 2>&1 || exit $?

@@ -4,6 +4,8 @@
 cd "${GRAFT_REPO_ROOT:-.}" && mkdir -p gpurun_out
 IFS=';' read -ra CFG <<< "$SWEEP"
 logs=()
+# the summaries below read what only a --full bench run reports (phases, lanes, rooflines)
+BENCH_ARGS="--full $BENCH_ARGS"
 for i in 1 2; do
   n=0
   for c in "${CFG[@]}"; do

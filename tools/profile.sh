@@ -6,7 +6,7 @@
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 TAG=${1:-r2}
-ARGS=${BENCH_ARGS:---steps 20 --warmup 5 --no-cpu-baseline}
+ARGS=${BENCH_ARGS:---steps 20 --warmup 5 --full --no-cpu-baseline}
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 run() {  # name, then the bench arguments
@@ -23,7 +23,7 @@ pmc() {  # name, counters, then the bench arguments
     || exit $?
   echo "pmc $name ok"
 }
-SHORT="--steps 3 --warmup 1 --no-cpu-baseline"
+SHORT="--steps 3 --warmup 1 --full --no-cpu-baseline"
 run fused $ARGS
 DFX_SERIAL=1 run serial $ARGS
 run split --sharded $ARGS

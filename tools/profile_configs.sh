@@ -9,12 +9,12 @@ export TMPDIR=/tmp
 mkdir -p gpurun_out
 for c in ${CONFIGS:-c2 c5 c4shard}; do
   timeout -k 10 400 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_${TAG}_$c -o trace \
-    --output-format csv -- python3 bench.py --config $c --steps 20 --warmup 5 --no-cpu-baseline \
+    --output-format csv -- python3 bench.py --config $c --steps 20 --warmup 5 --full --no-cpu-baseline \
     > gpurun_out/prof_${TAG}_$c.log 2>&1 || exit $?
   echo "trace $c ok"
   for ctr in FETCH_SIZE WRITE_SIZE; do
     timeout -s KILL 200 rocprofv3 --pmc $ctr -d gpurun_out/pmc_${TAG}_${c}_$ctr -o pmc \
-      --output-format csv -- python3 bench.py --config $c --steps 3 --warmup 1 --no-cpu-baseline \
+      --output-format csv -- python3 bench.py --config $c --steps 3 --warmup 1 --full --no-cpu-baseline \
       > gpurun_out/pmc_${TAG}_${c}_$ctr.log 2>&1 || exit $?
     echo "pmc $c $ctr ok"
   done

@@ -4,7 +4,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-ARGS=${BENCH_ARGS:---steps 20 --warmup 5 --no-cpu-baseline}
+ARGS=${BENCH_ARGS:---steps 20 --warmup 5 --full --no-cpu-baseline}
 IFS=';' read -ra VS <<< "$VARIANTS"
 for v in "${VS[@]}"; do
   IFS='|' read -r name lib ctx <<< "$v"
