@@ -142,8 +142,8 @@ __host__ __device__ inline float initv_value(int r, float scale) {
 // InitV's rows a coordinate per thread: row i of a block's list starts at LCG state st[i]
 // (3·d·rank steps past the seed) and its coordinate j is the rand_r draw 3·j steps further,
 // (A[j], C[j]) = lcg_jump(3·j) — the values one thread walking the row would draw.  vrow
-// 0xFFFFFFFF: skipped (pool full).  Callers: store.hip k_initv / k_initv_onepass, dist.hip
-// k_dist_initv_sum.
+// 0xFFFFFFFF: skipped (pool full).  The only coordinate-per-thread draw; its one caller is
+// initv.hip initv_draw, which every InitV kernel goes through.
 constexpr int kIvMaxD = 256;  // up to this V_dim; wider rows are drawn a row per thread
 template <int NT, class RowV, class RowC>
 __device__ inline void initv_draw_list(uint32_t n, const uint32_t* st, const uint32_t* vrow,

@@ -270,59 +270,6 @@ __global__ void k_dist_push(const uint32_t* segstart, const uint32_t* segslot,
   if (lane_id() == 0 && nf) atomicAdd(fcount, (uint32_t)nf);
 }
 
-// flagged keys (key order) -> (rank, key) order: rank keys, segment payloads (the sort that
-// follows reads the first *ftotal of them).  Strided over a capped grid.
-__global__ void k_dist_initv_list(const uint32_t* flags_excl, const uint32_t* ftotal,
-                                  const uint32_t* frank, const uint32_t* nuniq, int64_t bound,
-                                  uint32_t* rk, uint32_t* rv) {
-  const uint32_t F = *ftotal;
-  if (F == 0) return;  // no InitV this step (the steady state)
-  const int64_t n = std::min<int64_t>(*nuniq, bound);
-  for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u < n;
-       u += (int64_t)gridDim.x * blockDim.x) {
-    const uint32_t e = flags_excl[u];
-    const uint32_t nx = (u + 1 < n) ? flags_excl[u + 1] : F;
-    if (nx != e) {
-      rk[e] = frank[u];
-      rv[e] = (uint32_t)u;
-    }
-  }
-}
-
-// InitV (sgd_updater.cc:144-152) of the q-th draw: seed jumped 3*d*q steps, pool row n_vrows+q
-__global__ void k_dist_initv(const uint32_t* rv0, const uint32_t* rv1, const uint32_t* ftotal,
-                             const uint32_t* segslot, Table T, float scale, DevState* ds,
-                             const unsigned int* sortmeta) {
-  const int64_t F = (int64_t)*ftotal;
-  const uint32_t* rv = sortmeta[31] ? rv1 : rv0;
-  const int d = T.d;
-  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < F;
-       q += (int64_t)gridDim.x * blockDim.x) {
-    uint32_t s = lcg_advance(ds->seed, 3ull * (uint64_t)d * (uint64_t)q);
-    const int64_t vr = initv_row(T, ds->n_vrows, q, segslot[rv[q]]);
-    if (vr >= T.vcap) {
-      atomicOr(&ds->err, kErrPoolFull);
-      continue;
-    }
-    float* V = row_V(T, vr);
-    float* C = row_C(T, vr);
-    for (int k = 0; k < d; ++k) {
-      V[k] = initv_value(rand_r_dev(&s), scale);
-      C[k] = 0.f;
-    }
-    ent_at(T, segslot[rv[q]])->vrow = (int32_t)vr;
-  }
-}
-
-__global__ void k_dist_initv_finalize(const uint32_t* ftotal, int d, int64_t vcap,
-                                      DevState* ds, uint32_t* fcount) {
-  const uint32_t F = *ftotal;
-  *fcount = 0u;  // the flag count of the next Update of this slot
-  ds->seed = lcg_advance(ds->seed, 3ull * (uint64_t)d * F);
-  const unsigned long long nv = ds->n_vrows + F;
-  ds->n_vrows = nv > (unsigned long long)vcap ? (unsigned long long)vcap : nv;
-}
-
 // SGDUpdater::Get (sgd_updater.cc:34-58) per received key, in received order
 __global__ void k_dist_pull(int64_t R, const uint32_t* seg_of, const uint32_t* segslot,
                             Table T, Params P, float* out) {
@@ -468,8 +415,8 @@ __global__ __launch_bounds__(kDNT) void k_dist_push_vec(const uint32_t* __restri
 // key's gradient is the sum of the workers' gradient records (in rank order), applied by ONE
 // Update (sgd_updater.cc:76-142) — UpdateW, and UpdateV when V was pulled (every worker of the
 // step pulled the same state, so the records agree on `live`).  InitV requests are flagged in
-// key order; their draws are ranked over all owners (k_dist_initv_sum), so the rand_r stream is
-// the single reference updater's.
+// key order; their draws are ranked over all owners (initv.hip k_initv_rank_draw), so the rand_r
+// stream is the single reference updater's.
 template <int G>
 __global__ __launch_bounds__(kDNT) void k_dist_push_sum_vec(
     const uint32_t* __restrict__ segstart, const uint32_t* __restrict__ segslot,
@@ -584,270 +531,6 @@ __global__ void k_dist_push_sum(const uint32_t* segstart, const uint32_t* segslo
   if (lane_id() == 0 && nf) atomicAdd(fcount, (uint32_t)nf);
 }
 
-__global__ void k_dist_initv_count(const uint32_t* ftotal, int64_t* out) {
-  *out = (int64_t)*ftotal;
-}
-
-// InitV draws of this owner's flagged keys (key order), ranked after every lower owner's
-// draws of this step: the q-th of them jumps the shared seed by 3*d*(sum_{h<rank} F_h + q)
-__global__ __launch_bounds__(kDNT) void k_dist_initv_sum(const uint32_t* excl,
-                                                         const uint32_t* ftotal,
-                                                         const uint32_t* nuniq, int64_t bound,
-                                                         const uint32_t* segslot,
-                                                         const int64_t* Fall, int rank, Table T,
-                                                         float scale, const DevState* ds) {
-  const uint32_t F = *ftotal;
-  if (F == 0) return;
-  int64_t off = 0;
-  for (int h = 0; h < rank; ++h) off += Fall[h];
-  const int64_t n = std::min<int64_t>(*nuniq, bound);
-  const int d = T.d;
-  if (d > kIvMaxD) {  // (wide V: a row per thread)
-    for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u < n;
-         u += (int64_t)gridDim.x * blockDim.x) {
-      const uint32_t e = excl[u];
-      const uint32_t nx = (u + 1 < n) ? excl[u + 1] : F;
-      if (nx == e) continue;
-      uint32_t s = lcg_advance(ds->seed, 3ull * (uint64_t)d * (uint64_t)(off + e));
-      const int64_t vr = initv_row(T, ds->n_vrows, e, segslot[u]);
-      if (vr >= T.vcap) continue;  // kErrPoolFull is set by the finalize
-      float* V = row_V(T, vr);
-      float* C = row_C(T, vr);
-      for (int k = 0; k < d; ++k) {
-        V[k] = initv_value(rand_r_dev(&s), scale);
-        C[k] = 0.f;
-      }
-      ent_at(T, segslot[u])->vrow = (int32_t)vr;
-    }
-    return;
-  }
-  // per kDNT keys: the flagged ones listed (a block scan), then drawn a coordinate per thread
-  __shared__ uint32_t s_st[kDNT], s_vr[kDNT], s_A[kIvMaxD], s_C[kIvMaxD];
-  __shared__ uint32_t lds[kDNT / kWave + 1];
-  for (int j = threadIdx.x; j < d; j += kDNT) lcg_jump(3ull * (uint64_t)j, &s_A[j], &s_C[j]);
-  for (int64_t b0 = (int64_t)blockIdx.x * kDNT; b0 < n; b0 += (int64_t)gridDim.x * kDNT) {
-    const int64_t u = b0 + threadIdx.x;
-    uint32_t e = 0;
-    bool f = false;
-    if (u < n) {
-      e = excl[u];
-      f = ((u + 1 < n) ? excl[u + 1] : F) != e;
-    }
-    uint32_t cnt;
-    const uint32_t at = block_excl_scan<kDNT>(f ? 1u : 0u, lds, &cnt);
-    if (f) {
-      const int64_t vr = initv_row(T, ds->n_vrows, e, segslot[u]);
-      s_st[at] = lcg_advance(ds->seed, 3ull * (uint64_t)d * (uint64_t)(off + e));
-      if (vr >= T.vcap) {
-        s_vr[at] = 0xFFFFFFFFu;  // kErrPoolFull is set by the finalize
-      } else {
-        s_vr[at] = (uint32_t)vr;
-        ent_at(T, segslot[u])->vrow = (int32_t)vr;
-      }
-    }
-    __syncthreads();
-    initv_draw_list<kDNT>(cnt, s_st, s_vr, d, scale, s_A, s_C,
-                          [&](uint32_t r) { return row_V(T, r); },
-                          [&](uint32_t r) { return row_C(T, r); });
-    __syncthreads();
-  }
-}
-
-__global__ void k_dist_initv_sum_finalize(const uint32_t* ftotal, const int64_t* Fall,
-                                          int nranks, int d, int64_t vcap, DevState* ds,
-                                          uint32_t* fcount) {
-  int64_t tot = 0;
-  for (int h = 0; h < nranks; ++h) tot += Fall[h];
-  const uint32_t F = *ftotal;
-  *fcount = 0u;
-  ds->seed = lcg_advance(ds->seed, 3ull * (uint64_t)d * (uint64_t)tot);
-  const unsigned long long nv = ds->n_vrows + F;
-  if (nv > (unsigned long long)vcap) atomicOr(&ds->err, kErrPoolFull);
-  ds->n_vrows = nv > (unsigned long long)vcap ? (unsigned long long)vcap : nv;
-}
-
-// ---- the split owner's ranked InitV in two launches (round 6; was a three-launch scan, a count
-// kernel, the draws and a finalize: six launches on the critical path of every step, even in
-// the steady state where the backward flagged nothing and every launch exits at once).
-//   count: per tile of kIvrTile flags its count (ts[tile]); the last block (a ticket per block)
-//          sums them into this owner's F — the request count the owners all-gather
-//   draw:  per tile its exclusive prefix from ts, per chunk of kIvrNT flags a block scan, then the
-//          listed keys drawn a coordinate per thread at their rank over all owners (off + e);
-//          the last block advances the shared seed by every owner's draws and the V pool by F
-// The draws equal k_dist_initv_sum's (the same rank per key, the same rand_r jump); the tiles'
-// counts cross blocks through agent-scope atomics, as the look-back words do (lookback.h)
-constexpr int kIvrTile = 4096, kIvrNT = 256, kIvrGrid = 256;
-
-__device__ inline int64_t ivr_n(const uint32_t* nuniq, int64_t bound) {
-  const int64_t n = (int64_t)*nuniq;
-  return n < bound ? n : bound;
-}
-
-// the block's last-block ticket: true in every thread of the block that took the last ticket.
-// No fence: what crosses blocks goes through agent-scope atomics (a device-scope fence per
-// block would write back its XCD's L2, store.hip k_initv_onepass)
-__device__ inline bool ivr_last_block(unsigned* ticket, bool* s_last) {
-  __syncthreads();
-  if (threadIdx.x == 0) *s_last = atomicAdd(ticket, 1u) == gridDim.x - 1;
-  __syncthreads();
-  return *s_last;
-}
-
-__global__ __launch_bounds__(kIvrNT) void k_initv_rank_count(const uint32_t* flags, int64_t bound,
-                                                             const uint32_t* nuniq,
-                                                             const uint32_t* gate, uint32_t* ts,
-                                                             uint32_t* ftotal, int64_t* count_out,
-                                                             unsigned* ticket) {
-  __shared__ uint32_t lds[kIvrNT / kWave + 1];
-  __shared__ bool s_last;
-  if (gate && *gate == 0u) {  // no key flagged this step (the steady state): F = 0
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-      *ftotal = 0u;
-      *count_out = 0;
-    }
-    return;
-  }
-  const int64_t n = ivr_n(nuniq, bound);
-  const int64_t ntiles = (n + kIvrTile - 1) / kIvrTile;
-  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int64_t b0 = tile * kIvrTile;
-    uint32_t f = 0;
-    for (int i = threadIdx.x; i < kIvrTile; i += kIvrNT) {
-      const int64_t u = b0 + i;
-      f += (u < n && flags[u]) ? 1u : 0u;
-    }
-    uint32_t tot;
-    (void)block_excl_scan<kIvrNT>(f, lds, &tot);
-    if (threadIdx.x == 0)
-      __hip_atomic_store(ts + tile, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  if (!ivr_last_block(ticket, &s_last)) return;
-  uint32_t f = 0;
-  for (int64_t i = threadIdx.x; i < ntiles; i += kIvrNT)
-    f += __hip_atomic_load(ts + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  uint32_t F;
-  (void)block_excl_scan<kIvrNT>(f, lds, &F);
-  if (threadIdx.x == 0) {
-    *ftotal = F;
-    *count_out = (int64_t)F;
-    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-__global__ __launch_bounds__(kIvrNT) void k_initv_rank_draw(
-    const uint32_t* flags, int64_t bound, const uint32_t* nuniq, const uint32_t* ftotal,
-    const uint32_t* ts, const uint32_t* segslot, const int64_t* Fall, int rank, int nranks,
-    Table T, float scale, DevState* ds, int64_t vcap, uint32_t* fcount, unsigned* ticket,
-    unsigned long long* cap_host) {
-  __shared__ uint32_t lds[kIvrNT / kWave + 1];
-  __shared__ uint32_t s_st[kIvrNT], s_vr[kIvrNT], s_A[kIvMaxD], s_C[kIvMaxD];
-  __shared__ bool s_last;
-  int64_t tot = 0, off = 0;
-  for (int h = 0; h < nranks; ++h) {
-    tot += Fall[h];
-    if (h < rank) off += Fall[h];
-  }
-  if (tot == 0) {  // no owner draws: nothing advances (the gate's reset only)
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-      *fcount = 0u;
-      if (cap_host) {  // the capacity guard's counts (pinned host words)
-        cap_host[0] = ds->n_keys;
-        cap_host[1] = ds->n_vrows;
-      }
-    }
-    return;
-  }
-  const uint32_t F = *ftotal;
-  const int d = T.d;
-  if (F > 0) {
-    for (int j = threadIdx.x; j < d && j < kIvMaxD; j += kIvrNT)
-      lcg_jump(3ull * (uint64_t)j, &s_A[j], &s_C[j]);
-    const int64_t n = ivr_n(nuniq, bound);
-    const int64_t ntiles = (n + kIvrTile - 1) / kIvrTile;
-    const uint32_t seed = ds->seed;
-    const uint64_t nv0 = ds->n_vrows;
-    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-      uint32_t pre = 0;  // the tile's exclusive prefix: the counts of the tiles before it
-      for (int64_t i = threadIdx.x; i < tile; i += kIvrNT)
-        pre += __hip_atomic_load(ts + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      uint32_t base;
-      (void)block_excl_scan<kIvrNT>(pre, lds, &base);
-      if (__hip_atomic_load(ts + tile, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) continue;
-      const int64_t b0 = tile * kIvrTile;
-      for (int c0 = 0; c0 < kIvrTile; c0 += kIvrNT) {
-        const int64_t u = b0 + c0 + threadIdx.x;
-        const bool f = u < n && flags[u] != 0u;
-        uint32_t cnt;
-        const uint32_t at = block_excl_scan<kIvrNT>(f ? 1u : 0u, lds, &cnt);
-        if (f) {
-          const uint32_t e = base + at;
-          uint32_t st = lcg_advance(seed, 3ull * (uint64_t)d * (uint64_t)(off + e));
-          const int64_t vr = initv_row(T, nv0, e, segslot[u]);
-          if (vr >= T.vcap) {
-            s_vr[at] = 0xFFFFFFFFu;  // kErrPoolFull: set by the last block
-          } else {
-            s_vr[at] = (uint32_t)vr;
-            ent_at(T, segslot[u])->vrow = (int32_t)vr;
-            if (d > kIvMaxD) {  // (wide V: the row by its own thread)
-              float* V = row_V(T, vr);
-              float* C = row_C(T, vr);
-              for (int k = 0; k < d; ++k) {
-                V[k] = initv_value(rand_r_dev(&st), scale);
-                C[k] = 0.f;
-              }
-            }
-          }
-          s_st[at] = st;
-        }
-        __syncthreads();
-        if (d <= kIvMaxD)
-          initv_draw_list<kIvrNT>(cnt, s_st, s_vr, d, scale, s_A, s_C,
-                                  [&](uint32_t r) { return row_V(T, r); },
-                                  [&](uint32_t r) { return row_C(T, r); });
-        base += cnt;
-        __syncthreads();
-      }
-    }
-  }
-  // the last block: every owner's draws advance the shared seed, this owner's F the pool
-  if (!ivr_last_block(ticket, &s_last) || threadIdx.x != 0) return;
-  __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  *fcount = 0u;
-  ds->seed = lcg_advance(ds->seed, 3ull * (uint64_t)d * (uint64_t)tot);
-  const unsigned long long nv = ds->n_vrows + F;
-  if (nv > (unsigned long long)vcap) atomicOr(&ds->err, kErrPoolFull);
-  ds->n_vrows = nv > (unsigned long long)vcap ? (unsigned long long)vcap : nv;
-  if (cap_host) {
-    cap_host[0] = ds->n_keys;
-    cap_host[1] = ds->n_vrows;
-  }
-}
-
-int initv_rank_count(const Lane& L, uint32_t* flags, int64_t bound, const uint32_t* nuniq,
-                     uint32_t* ftotal, const uint32_t* gate, int64_t* count_dev) {
-  const int64_t ntiles = std::max<int64_t>(1, (bound + kIvrTile - 1) / kIvrTile);
-  DFX_TRY(L.ws->tiles.ensure(sizeof(uint32_t) * (ntiles + 1)));
-  const dim3 g((unsigned)std::min<int64_t>(ntiles, kIvrGrid));
-  hipLaunchKernelGGL(k_initv_rank_count, g, dim3(kIvrNT), 0, L.stream, flags, bound, nuniq, gate,
-                     L.ws->tiles.as<uint32_t>(), ftotal, count_dev, &L.ds->ivr_ticket[0]);
-  DFX_HIP(hipGetLastError());
-  return DFX_OK;
-}
-
-int initv_rank_draw(Context* c, const Lane& L, const uint32_t* flags, const uint32_t* ftotal,
-                    const uint32_t* nuniq, int64_t bound, const uint32_t* segslot,
-                    const int64_t* counts_all, int rank, int nranks, uint32_t* fcount,
-                    unsigned long long* cap_host) {
-  const int64_t ntiles = std::max<int64_t>(1, (bound + kIvrTile - 1) / kIvrTile);
-  DFX_TRY(L.ws->tiles.ensure(sizeof(uint32_t) * (ntiles + 1)));
-  const dim3 g((unsigned)std::min<int64_t>(ntiles, kIvrGrid));
-  hipLaunchKernelGGL(k_initv_rank_draw, g, dim3(kIvrNT), 0, L.stream, flags, bound, nuniq, ftotal,
-                     L.ws->tiles.as<uint32_t>(), segslot, counts_all, rank, nranks, c->T,
-                     c->P.V_init_scale, c->ds, c->T.vcap, fcount, &L.ds->ivr_ticket[1], cap_host);
-  DFX_HIP(hipGetLastError());
-  return DFX_OK;
-}
-
 // ---- union-indexed collectives (the north_star's literal reduce-scatter / all-gather) -------
 // The union of every worker's keys, sorted: union[excl[i]] = K[i] at run heads; upos[src] =
 // the union position of the item the merge took from source index src
@@ -908,37 +591,10 @@ static Lane owner_lane(Context* c, int slot) {
   return Lane{c->stream, &c->ows[slot], c->ods[slot], &c->ds->err};
 }
 
-// InitV of the flagged keys in (pushing rank, key) order, all on the device
+// push_agg=ranks: InitV of the slot's flagged keys in (pushing rank, key) order
 static int owner_initv(Context* c, int slot, int nranks) {
   const Lane OL = owner_lane(c, slot);
-  Workspace& ws = *OL.ws;
-  const int64_t R = c->dist_R[slot];
-  uint32_t* flags = ws.oflags.as<uint32_t>();
-  uint32_t* nuniq = &OL.ds->totals[1];
-  uint32_t* ftotal = &OL.ds->totals[2];
-  uint32_t* fcount = &OL.ds->totals[3];
-  // gated on the device by the flag count: the scan, the sort and the draws exit at once
-  // when no key asked for V (the steady state)
-  DFX_TRY(scan_u32(OL, flags, R, ftotal, nuniq, fcount));
-  uint32_t* rk0 = ws.vals0.as<uint32_t>();
-  uint32_t* rv0 = ws.vals1.as<uint32_t>();
-  uint32_t* rk1 = reinterpret_cast<uint32_t*>(ws.keys0.as<uint64_t>());
-  uint32_t* rv1 = reinterpret_cast<uint32_t*>(ws.keys1.as<uint64_t>());
-  const dim3 grid((R + kDNT - 1) / kDNT);
-  const dim3 igrid((unsigned)std::min<int64_t>((R + kDNT - 1) / kDNT, 1024));
-  hipLaunchKernelGGL(k_dist_initv_list, igrid, dim3(kDNT), 0, OL.stream, flags, ftotal,
-                     ws.ofrank.as<uint32_t>(), nuniq, R, rk0, rv0);
-  int bits = 0;
-  while ((1 << bits) < nranks) ++bits;
-  // stable by rank, over the *ftotal flagged keys
-  DFX_TRY(radix_sort_pairs<uint32_t>(OL, rk0, rv0, rk1, rv1, R, 0, bits > 0 ? 8 : 0, nullptr,
-                                     OL.ds->sortmeta, ftotal));
-  hipLaunchKernelGGL(k_dist_initv, igrid, dim3(kDNT), 0, OL.stream, rv0, rv1, ftotal,
-                     ws.osegslot.as<uint32_t>(), c->T, c->P.V_init_scale, c->ds,
-                     OL.ds->sortmeta);
-  hipLaunchKernelGGL(k_dist_initv_finalize, dim3(1), dim3(1), 0, OL.stream, ftotal, c->P.V_dim,
-                     c->T.vcap, c->ds, fcount);
-  return DFX_OK;
+  return initv_by_rank(c, OL, c->dist_R[slot], nranks, OL.ws->osegslot.as<uint32_t>());
 }
 
 // the owner's segments of a slot (find-or-insert of every received key), when still pending
@@ -1286,7 +942,7 @@ int dfx_dist_owner_push(dfx_ctx* ctx, int slot, const float* recv_grads) {
 }
 
 // push_agg=sum: the InitV requests of the slot's last count push or gradient push, ranked
-// over all owners.  initv_local scans this owner's flags (key order) and writes their number
+// over all owners.  initv_local counts this owner's flags (key order) and writes their number
 // to count_dev (device int64); the caller all-gathers the owners' counts (rank order) into
 // counts_all_dev[nranks] (device) and initv_draw draws this owner's keys after every lower
 // owner's, advancing the shared seed by the total (sgd_updater.cc:144-152 in global key order)
@@ -1296,16 +952,10 @@ int dfx_dist_initv_local(dfx_ctx* ctx, int slot, int64_t* count_dev) {
   Context* c = &ctx->c;
   DFX_CHECK_ARG(c->dist_sum, "dist_initv_local: only with push_agg=sum");
   const Lane OL = owner_lane(c, slot);
-  uint32_t* ftotal = &OL.ds->totals[2];
-  if (!c->dist_initv_pending[slot] || c->dist_R[slot] == 0) {
-    DFX_HIP(hipMemsetAsync(ftotal, 0, sizeof(uint32_t), OL.stream));
-  } else {
-    DFX_TRY(scan_u32(OL, OL.ws->oflags.as<uint32_t>(), c->dist_R[slot], ftotal,
-                     &OL.ds->totals[1], &OL.ds->totals[3]));
-  }
-  hipLaunchKernelGGL(k_dist_initv_count, dim3(1), dim3(1), 0, OL.stream, ftotal, count_dev);
-  DFX_HIP(hipGetLastError());
-  return DFX_OK;
+  // (no keys, or nothing pending: a bound of 0 counts none)
+  return initv_rank_count(OL, OL.ws->oflags.as<uint32_t>(),
+                          c->dist_initv_pending[slot] ? c->dist_R[slot] : 0, &OL.ds->totals[1],
+                          &OL.ds->totals[2], &OL.ds->totals[3], count_dev);
 }
 
 int dfx_dist_initv_draw(dfx_ctx* ctx, int slot, const int64_t* counts_all_dev, int rank,
@@ -1317,22 +967,13 @@ int dfx_dist_initv_draw(dfx_ctx* ctx, int slot, const int64_t* counts_all_dev, i
   Context* c = &ctx->c;
   DFX_CHECK_ARG(c->dist_sum, "dist_initv_draw: only with push_agg=sum");
   const Lane OL = owner_lane(c, slot);
-  const int64_t R = c->dist_R[slot];
-  uint32_t* ftotal = &OL.ds->totals[2];
-  if (c->dist_initv_pending[slot] && R > 0) {
-    const dim3 igrid((unsigned)std::min<int64_t>((R + kDNT - 1) / kDNT, 1024));
-    hipLaunchKernelGGL(k_dist_initv_sum, igrid, dim3(kDNT), 0, OL.stream,
-                       OL.ws->oflags.as<uint32_t>(), ftotal, &OL.ds->totals[1], R,
-                       OL.ws->osegslot.as<uint32_t>(), counts_all_dev, rank, c->T,
-                       c->P.V_init_scale, c->ds);
-  }
-  hipLaunchKernelGGL(k_dist_initv_sum_finalize, dim3(1), dim3(1), 0, OL.stream, ftotal,
-                     counts_all_dev, nranks, c->P.V_dim, c->T.vcap, c->ds, &OL.ds->totals[3]);
+  DFX_TRY(initv_rank_draw(c, OL, OL.ws->oflags.as<uint32_t>(), &OL.ds->totals[2],
+                          &OL.ds->totals[1], c->dist_initv_pending[slot] ? c->dist_R[slot] : 0,
+                          OL.ws->osegslot.as<uint32_t>(), counts_all_dev, rank, nranks,
+                          &OL.ds->totals[3]));
   c->dist_initv_pending[slot] = false;
   if (c->dist_pushed[slot]) c->dist_live[slot] = false;  // the step is done with the table
-  DFX_TRY(cap_record(c));
-  DFX_HIP(hipGetLastError());
-  return DFX_OK;
+  return cap_record(c);
 }
 
 int dfx_dist_push_agg_sum(dfx_ctx* ctx) { return ctx ? ctx->c.dist_sum : -1; }

@@ -74,8 +74,11 @@ struct DevState {
   double scratch[8];
   unsigned int iv_ticket;      // the one-launch InitV's tile tickets (reset by k_step_finalize)
   unsigned int iv_epoch;       // its look-back words' tag (advanced by k_step_finalize)
-  unsigned int ivr_ticket[2];  // the ranked InitV's two launches: block tickets (self-resetting)
-  unsigned int iv_done;        // the fused InitV's blocks done (its last block finalizes the step)
+  // arrival words of the InitV kernels (initv.hip initv_arrive): blocks arrived << 32 | the sum
+  // they carried; the last block to arrive reads the sum from its own add and zeroes the word
+  unsigned long long ivr_ticket[2];  // the ranked InitV's two launches
+  unsigned long long iv_done;        // the fused InitV (its last block finalizes the step)
+  long long iv_count;          // a single owner's request count, as initv_rank_draw's counts_all
   // the bucket Localizer (locbucket.hip): min / max of the batch's keys, and the key range its
   // bucket map was fitted to (the previous batch on this lane; pk_valid == 0: none yet)
   unsigned long long kmin, kmax, pk_min, pk_max;
@@ -448,38 +451,46 @@ int step_reserve(Context* c, int64_t rows, int64_t nnz);  // ws_reserve + the st
 int loc_reserve(Workspace& w, int64_t nnz, hipStream_t st);
 int auc_reserve(Workspace& w, int64_t rows, hipStream_t st);
 
-// store phases (store.hip).  n_host < 0: the count is ds->u_count; n_bound sizes the grid.
-// nds: the device state whose u_count holds the count when n_host < 0
-// gate (optional, device): the number of set flags, or any nonzero; zero skips the pass
-// finalize = false: the caller advances the seed and the V-row count itself (by *total_dev)
-// the fused step's last work (step.hip step_finalize_body): the forward's loss partials summed,
-// the progress counters, the InitV pass's seed advance, the capacity guard's counts
+// the fused step's last work (step_finalize_body): the forward's loss partials summed, the
+// progress counters, the InitV pass's seed advance, the capacity guard's counts
 struct FinArgs {
   DevState* ds = nullptr;
   const DevState* bds = nullptr;
   int64_t B = 0;
-  const uint32_t* initv_total = nullptr;
+  bool initv = false;  // an InitV pass ran: the seed and the V pool advance by its request count
   int d = 0;
   int64_t vcap = 0;
   const double* loss_part = nullptr;
   int64_t nparts = 0;
   unsigned long long* cap_host = nullptr;
 };
-int run_initv(Context* c, int64_t n_host, int64_t n_bound, uint32_t* flags, uint32_t* total_dev,
-              const uint32_t* slot, const DevState* nds = nullptr,
-              const uint32_t* gate = nullptr, bool finalize = true,
-              const FinArgs* fin = nullptr);
+// InitV of the keys flagged (0 / 1, read raw) in flags[0 .. n), key order, slot: their table
+// slots (initv.hip).  n = nds->u_count (device) when nds is given, bounded by n_bound which sizes
+// the grid; else n_bound.  fin: the fused step — one launch, gated by ds->n_init, whose last
+// block runs step_finalize_body(*fin); else the ranked pair as one owner on the main lane, the
+// seed and the V-row count advanced by its draw
+int run_initv(Context* c, int64_t n_bound, const uint32_t* flags, const uint32_t* slot,
+              const DevState* nds = nullptr, const FinArgs* fin = nullptr);
 
-// the threads that run it (k_step_finalize; the fused InitV's blocks, store.hip kStNT)
+// an InitV pass's end: the rand_r stream past the draws of every owner, the V pool past this
+// owner's rows (capped: kErrPoolFull was raised by the keys that got none, initv.hip initv_place)
+__device__ inline void initv_advance(DevState* ds, int d, uint64_t draws, uint64_t rows,
+                                     int64_t vcap) {
+  ds->seed = lcg_advance(ds->seed, 3ull * (uint64_t)d * draws);
+  const unsigned long long nv = ds->n_vrows + rows;
+  ds->n_vrows = nv > (unsigned long long)vcap ? (unsigned long long)vcap : nv;
+}
+
+// the threads that run it (k_step_finalize; the fused InitV's blocks, initv.hip kIvNT)
 constexpr int kFinNT = 256;
 // the step's last work: the forward's loss partials summed (a fixed order: NT-strided, then the
 // waves in order), the progress counters, the InitV pass's seed advance, and the capacity
 // guard's counts into its pinned ring entry (cap_host, or NULL).  Run by k_step_finalize, or by
-// the last block of the fused InitV (store.hip k_initv_onepass: one launch less per step); both
-// with kFinNT threads, so a step's loss is the same sum either way.  initv_total is read with
-// an agent-scope load: the InitV kernel's last tile wrote it from another block
+// the last block of the fused InitV (initv.hip k_initv_onepass: one launch less per step); both
+// with kFinNT threads, so a step's loss is the same sum either way.  initv_n: the InitV pass's
+// request count, which that last block has from the add that elected it (initv_arrive)
 template <int NT>
-__device__ inline void step_finalize_body(const FinArgs& f, double* red) {
+__device__ inline void step_finalize_body(const FinArgs& f, uint32_t initv_n, double* red) {
   DevState* ds = f.ds;
   // the fused backward's striped {new_w, n_keys}: summed by wave 0, zeroed for the next step
   unsigned long long snw = 0, snk = 0;
@@ -513,12 +524,7 @@ __device__ inline void step_finalize_body(const FinArgs& f, double* red) {
   ds->n_init = 0;  // the backward's InitV request count (gates the next step's InitV pass)
   ds->iv_ticket = 0u;  // the next step's one-launch InitV takes its tiles from 0 again
   ds->iv_epoch += 1u;
-  if (f.initv_total) {  // the InitV pass's rand_r advance and V rows (k_initv_finalize's work)
-    const uint32_t n = __hip_atomic_load(f.initv_total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    ds->seed = lcg_advance(ds->seed, 3ull * (uint64_t)f.d * n);
-    const unsigned long long nv = ds->n_vrows + n;
-    ds->n_vrows = nv > (unsigned long long)f.vcap ? (unsigned long long)f.vcap : nv;
-  }
+  if (f.initv) initv_advance(ds, f.d, initv_n, initv_n, f.vcap);
   // (atomics: the Localizer lane's probe for the next batch may be inserting beside this)
   if (snw) atomicAdd((unsigned long long*)&ds->new_w, snw);
   if (snk) atomicAdd(&ds->n_keys, snk);
@@ -530,8 +536,7 @@ __device__ inline void step_finalize_body(const FinArgs& f, double* red) {
 
 // fused Update(kFeaCount): one segment per unique key (count = segment length = nds->u_count)
 int push_cnt_seg_run(Context* c, int64_t n_bound, const uint32_t* segstart,
-                     const uint32_t* segslot, uint32_t* flags, uint32_t* total_dev,
-                     const DevState* nds);
+                     const uint32_t* segslot, uint32_t* flags, const DevState* nds);
 int store_reserve(Context* c, int64_t n_keys, int64_t n_vrows);
 // before enqueueing work that inserts at most `add` keys (and draws at most `add` V rows):
 // make sure the table stays below 0.9 load and the V pool cannot overflow, growing at a sync
@@ -546,17 +551,20 @@ void cap_release(Context* c);
 // at a sync point (the stream is idle): grow the table once its load passes 0.5
 int store_maybe_grow(Context* c);
 
-// metrics (metric.hip): AUC*n and sum of log(1+exp(-y pred)) into device doubles
-// push_agg=sum InitV ranked over all owners (dist.hip), for the flags of any owner step: count
-// counts the flags (per unique key, key order) by tile and writes their number to count_dev;
-// draw draws this owner's flagged keys after every lower owner's and advances the shared seed
-// by the total of counts_all[nranks] — one launch each
-int initv_rank_count(const Lane& L, uint32_t* flags, int64_t bound, const uint32_t* nuniq,
+// InitV ranked over all owners of a sharded model (initv.hip), for the raw 0 / 1 flags of any
+// owner step (per unique key, key order; nuniq: their device count, NULL: bound): count writes
+// their number to *ftotal and *count_dev (0 while *gate == 0, gate optional); draw draws this
+// owner's flagged keys after every lower owner's, advances the shared seed by the total of
+// counts_all[nranks] and zeroes *fcount (optional: the gate) — one launch each
+int initv_rank_count(const Lane& L, const uint32_t* flags, int64_t bound, const uint32_t* nuniq,
                      uint32_t* ftotal, const uint32_t* gate, int64_t* count_dev);
 int initv_rank_draw(Context* c, const Lane& L, const uint32_t* flags, const uint32_t* ftotal,
                     const uint32_t* nuniq, int64_t bound, const uint32_t* segslot,
                     const int64_t* counts_all, int rank, int nranks, uint32_t* fcount,
                     unsigned long long* cap_host = nullptr);  // (the capacity guard's counts)
+// push_agg=ranks: InitV of a key-range server's R received keys' segments in (pushing rank,
+// key) order, from the owner lane's oflags / ofrank and totals[1..3] (dist.hip)
+int initv_by_rank(Context* c, const Lane& OL, int64_t R, int nranks, const uint32_t* segslot);
 // Update(kFeaCount) of a localized batch's segments (count = segment length), InitV requests
 // into flags; no draws (store.hip)
 int push_cnt_seg_flags(Context* c, const Lane& L, int64_t n_bound, const uint32_t* segstart,
@@ -564,6 +572,7 @@ int push_cnt_seg_flags(Context* c, const Lane& L, int64_t n_bound, const uint32_
 // SGDUpdater::Get's find-or-insert over a lane's sorted unique keys (step.hip k_probe_keys)
 int probe_keys_run(Context* c, const Lane& L, int64_t bound, const uint64_t* uniq,
                    uint32_t* segslot);
+// metrics (metric.hip): AUC*n and sum of log(1+exp(-y pred)) into device doubles
 // mode: kwarg auc_sort (3 wave buckets, 2 block buckets, 1 radix, 0 merge)
 int auc_run(const Lane& L, int64_t B, const float* label, const float* pred, double* out_dev,
             int mode);

@@ -182,7 +182,7 @@ int probe_keys_run(Context* c, const Lane& L, int64_t bound, const uint64_t* uni
 
 __global__ __launch_bounds__(kFinNT) void k_step_finalize(FinArgs f) {
   __shared__ double red[kFinNT / kWave];
-  step_finalize_body<kFinNT>(f, red);
+  step_finalize_body<kFinNT>(f, 0u, red);
 }
 
 // the fused backward's striped {new_w, n_keys} folded into the state (k_step_finalize's first
@@ -255,7 +255,6 @@ int train_step(Context* c, const dfx_batch* b, int job_type, int push_cnt, uint6
   uint32_t* occ_row = bw.occ_row.as<uint32_t>();
   float* occ_x = b->value ? bw.occ_x.as<float>() : nullptr;
   uint32_t* flags = ws.flags.as<uint32_t>();
-  uint32_t* total = &c->ds->totals[0];
   float* pred = pred_out ? pred_out : ws.pred.as<float>();
 
   // ---- loc lane: the batch is ready on the caller's stream; this parity's buffers are free
@@ -316,7 +315,7 @@ int train_step(Context* c, const dfx_batch* b, int job_type, int push_cnt, uint6
                        nullptr, segslot, c->ds);
   prof_mark(c, 2);
   if (cnt_first) {
-    DFX_TRY(push_cnt_seg_run(c, nnz, segstart, segslot, flags, total, bds));
+    DFX_TRY(push_cnt_seg_run(c, nnz, segstart, segslot, flags, bds));
   }
   prof_mark(c, 3);
 
@@ -361,7 +360,7 @@ int train_step(Context* c, const dfx_batch* b, int job_type, int push_cnt, uint6
   // the step's last work: folded into the InitV launch when one runs (its last block), else a
   // kernel of its own
   FinArgs fin;
-  fin.ds = c->ds; fin.bds = bds; fin.B = B; fin.initv_total = initv ? total : nullptr;
+  fin.ds = c->ds; fin.bds = bds; fin.B = B; fin.initv = initv;
   fin.d = d; fin.vcap = c->T.vcap; fin.loss_part = a.loss_part; fin.nparts = nblk;
   if (bwd_runs) {
     BwdArgs g{};
@@ -395,7 +394,7 @@ int train_step(Context* c, const dfx_batch* b, int job_type, int push_cnt, uint6
     if (rc != DFX_OK) return bwd_runs ? fold_stripes_on_error(c, rc) : rc;
   }
   if (initv) {
-    const int rc = run_initv(c, -1, nnz, flags, total, segslot, bds, &c->ds->n_init, false, &fin);
+    const int rc = run_initv(c, nnz, flags, segslot, bds, &fin);
     if (rc != DFX_OK) return fold_stripes_on_error(c, rc);
   } else {
     hipLaunchKernelGGL(k_step_finalize, dim3(1), dim3(kFinNT), 0, c->stream, fin);

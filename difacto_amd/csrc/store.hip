@@ -9,9 +9,8 @@
 //                       key's whole scalar state.
 //   V     f32[vcap*2d]  rows of [V(d) | Vaux(d)] (embedding + AdaGrad accumulators in one
 //                       row: one 128-byte line per key at V_dim 16), allocated by InitV
-// InitV (sgd_updater.cc:144-152) draws glibc rand_r in key order; on the GPU every key that
-// needs V gets its exclusive-scan rank r among this push's InitV keys and jumps the LCG by
-// 3*V_dim*r steps, which reproduces the reference's sequential draws exactly.
+// The push kernels here only flag the keys that need V; InitV itself (sgd_updater.cc:144-152:
+// the rows, the rand_r draws in the reference's order) is initv.hip's run_initv.
 #include <algorithm>
 #include <cstddef>
 #include <cstdio>
@@ -23,7 +22,7 @@
 
 #include <chrono>
 
-#include "lookback.h"
+#include "internal.h"
 
 namespace dfx {
 
@@ -40,271 +39,6 @@ __device__ inline void block_count_add(int v, unsigned long long* dst) {
     if (s) atomicAdd(dst, (unsigned long long)(long long)s);
   }
   __syncthreads();
-}
-
-__device__ inline int64_t count_of(int64_t n_host, const DevState* ds) {
-  return n_host >= 0 ? n_host : (int64_t)ds->u_count;
-}
-
-// ---- InitV --------------------------------------------------------------------------------
-// excl: exclusive scan of the per-key InitV flags; *total: their sum; slot: table slot of
-// each flagged key.
-__global__ __launch_bounds__(kStNT) void k_initv(int64_t n_host, const uint32_t* excl,
-                                                 const uint32_t* total, const uint32_t* slot,
-                                                 Table T, float scale, DevState* ds,
-                                                 const DevState* nds, const uint32_t* gate) {
-  if (gate && *gate == 0u) return;
-  const int64_t n = count_of(n_host, nds);
-  const int d = T.d;
-  if (d > kIvMaxD) {  // (wide V: a row per thread)
-    // strided over a grid capped like a gated scan's (run_initv)
-    for (int64_t u = (int64_t)blockIdx.x * kStNT + threadIdx.x; u < n;
-         u += (int64_t)gridDim.x * kStNT) {
-      const uint32_t e = excl[u];
-      const uint32_t nx = (u + 1 < n) ? excl[u + 1] : *total;
-      if (nx == e) continue;
-      uint32_t s = lcg_advance(ds->seed, 3ull * (uint64_t)d * e);
-      const int64_t vr = initv_row(T, ds->n_vrows, e, slot[u]);
-      if (vr >= T.vcap) {
-        atomicOr(&ds->err, kErrPoolFull);
-        continue;
-      }
-      float* V = row_V(T, vr);
-      float* C = row_C(T, vr);
-      for (int k = 0; k < d; ++k) {
-        V[k] = initv_value(rand_r_dev(&s), scale);
-        C[k] = 0.f;
-      }
-      ent_at(T, slot[u])->vrow = (int32_t)vr;
-    }
-    return;
-  }
-  // per kStNT keys: the flagged ones listed (a block scan), then drawn a coordinate per thread
-  __shared__ uint32_t s_st[kStNT], s_vr[kStNT], s_A[kIvMaxD], s_C[kIvMaxD];
-  __shared__ uint32_t lds[kStNT / kWave + 1];
-  for (int j = threadIdx.x; j < d; j += kStNT) lcg_jump(3ull * (uint64_t)j, &s_A[j], &s_C[j]);
-  for (int64_t b0 = (int64_t)blockIdx.x * kStNT; b0 < n; b0 += (int64_t)gridDim.x * kStNT) {
-    const int64_t u = b0 + threadIdx.x;
-    uint32_t e = 0;
-    bool f = false;
-    if (u < n) {
-      e = excl[u];
-      f = ((u + 1 < n) ? excl[u + 1] : *total) != e;
-    }
-    uint32_t cnt;
-    const uint32_t at = block_excl_scan<kStNT>(f ? 1u : 0u, lds, &cnt);
-    if (f) {
-      const int64_t vr = initv_row(T, ds->n_vrows, e, slot[u]);
-      s_st[at] = lcg_advance(ds->seed, 3ull * (uint64_t)d * e);
-      if (vr >= T.vcap) {
-        atomicOr(&ds->err, kErrPoolFull);
-        s_vr[at] = 0xFFFFFFFFu;
-      } else {
-        s_vr[at] = (uint32_t)vr;
-        ent_at(T, slot[u])->vrow = (int32_t)vr;
-      }
-    }
-    __syncthreads();
-    initv_draw_list<kStNT>(cnt, s_st, s_vr, d, scale, s_A, s_C,
-                           [&](uint32_t r) { return row_V(T, r); },
-                           [&](uint32_t r) { return row_C(T, r); });
-    __syncthreads();
-  }
-}
-
-__global__ void k_initv_finalize(const uint32_t* total, int d, int64_t vcap, DevState* ds) {
-  const uint32_t n = *total;
-  ds->seed = lcg_advance(ds->seed, 3ull * (uint64_t)d * n);
-  unsigned long long nv = ds->n_vrows + n;
-  ds->n_vrows = nv > (unsigned long long)vcap ? (unsigned long long)vcap : nv;
-}
-
-// The fused step's InitV in ONE launch (it replaced the scan's three launches + k_initv: in the
-// steady state, where no key needs V, all four only found the device gate closed).  Block b
-// counts tile b's kIvTile flags, publishes the count and finds its prefix by the block-wide
-// decoupled look-back over the lower tiles' tagged words (lookback.h), then draws its keys' V
-// exactly as k_initv.
-// The last tile writes the total; with fin.ds set the step's last work follows in this launch
-// (step_finalize_body: the seed and n_vrows advanced by the total, the progress, the capacity
-// guard's counts) — by block 0 when the gate is closed, else by the last block to finish, one
-// launch less per step (round 6).
-// 8192-key tiles (a thread's 32 flags as one bit mask), the requested keys listed kIvList at a
-// time: 4096-key tiles took 850 tickets at C3, ~9 us of serialised atomics.
-constexpr int kIvItems = 32, kIvTile = kStNT * kIvItems, kIvList = 4096;
-
-static_assert(kStNT == kFinNT, "the fused InitV's blocks run the step's finalize");
-
-__device__ void initv_onepass_body(const uint32_t* flags, uint32_t* total, const uint32_t* slot,
-                                   const Table& T, float scale, DevState* ds, const DevState* nds,
-                                   unsigned long long* status, int64_t n, uint32_t need);
-
-__global__ __launch_bounds__(kStNT) void k_initv_onepass(const uint32_t* flags, uint32_t* total,
-                                                         const uint32_t* slot, Table T,
-                                                         float scale, DevState* ds,
-                                                         const DevState* nds,
-                                                         const uint32_t* gate,
-                                                         unsigned long long* status, FinArgs fin) {
-  __shared__ double s_red[kFinNT / kWave];
-  __shared__ bool s_last;
-  const int64_t n = (int64_t)nds->u_count;
-  const uint32_t need = (uint32_t)((n + kIvTile - 1) / kIvTile);
-  if (*gate == 0u || need == 0) {  // nothing to draw: block 0 finalizes
-    if (blockIdx.x != 0) return;
-    if (threadIdx.x == 0)
-      __hip_atomic_store(total, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (fin.ds) {
-      __syncthreads();
-      step_finalize_body<kFinNT>(fin, s_red);
-    }
-    return;
-  }
-  if (blockIdx.x >= need) return;
-  initv_onepass_body(flags, total, slot, T, scale, ds, nds, status, n, need);
-  if (!fin.ds) return;
-  // every block that took a tile counts itself done; the last one finalizes the step (its
-  // draws read ds->seed / n_vrows, which the finalize advances).  No fence: the finalize reads
-  // nothing this launch wrote but the total (an agent-scope store and load), and a device-scope
-  // fence per block writes its XCD's L2 back — here full of the backward's dirty model lines
-  // (measured: with the fences C3 lost 2.7 % in every step that drew a V row)
-  __syncthreads();
-  if (threadIdx.x == 0) s_last = atomicAdd(&ds->iv_done, 1u) == need - 1;
-  __syncthreads();
-  if (!s_last) return;
-  if (threadIdx.x == 0) __hip_atomic_store(&ds->iv_done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  step_finalize_body<kFinNT>(fin, s_red);
-}
-
-__device__ void initv_onepass_body(const uint32_t* flags, uint32_t* total, const uint32_t* slot,
-                                   const Table& T, float scale, DevState* ds, const DevState* nds,
-                                   unsigned long long* status, int64_t n, uint32_t need) {
-  __shared__ uint32_t lds[kStNT / kWave + 1];
-  __shared__ uint32_t s_lb[3 * kStNT / kWave];
-  // tile by ticket, in the order blocks start: a block only waits on running ones.  Block index
-  // order is not start order across XCDs, and the AUC lane's look-back sort can run beside this
-  // kernel, so tile = block index could wait on a block that cannot be placed.  The
-  // block that draws the last ticket zeroes the counter for the next launch (k_step_finalize
-  // zeroes it too).  Only as many blocks as the batch has tiles draw one: the grid is sized for
-  // the nnz bound, and each ticket is a returning atomic on one word, ~11 ns apiece serialised
-  // (DESIGN.md (d)); the blocks past the count leave at once, and the tickets still go to running
-  // blocks in start order.
-  __shared__ uint32_t s_tile;
-  if (threadIdx.x == 0) {
-    s_tile = atomicAdd(&ds->iv_ticket, 1u);
-    if (s_tile == need - 1)
-      __hip_atomic_store(&ds->iv_ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
-  const int64_t tile = s_tile;
-  const int64_t base = tile * kIvTile;
-  const uint32_t tag = ds->iv_epoch & 0x3FFFFFFFu;
-  // this thread's kIvItems consecutive flags (0 / 1) as bits
-  const int64_t i0 = base + (int64_t)threadIdx.x * kIvItems;
-  uint32_t mask = 0;
-  if (i0 + kIvItems <= n && ((uintptr_t)flags & 15u) == 0) {
-    const uint4* f4 = reinterpret_cast<const uint4*>(flags + i0);
-#pragma unroll
-    for (int q = 0; q < kIvItems / 4; ++q) {
-      const uint4 v = f4[q];
-      mask |= ((v.x ? 1u : 0u) | (v.y ? 2u : 0u) | (v.z ? 4u : 0u) | (v.w ? 8u : 0u)) << (4 * q);
-    }
-  } else {
-#pragma unroll 4
-    for (int k = 0; k < kIvItems; ++k)
-      if (i0 + k < n && flags[i0 + k]) mask |= 1u << k;
-  }
-  const uint32_t cnt = (uint32_t)__popc(mask);
-  uint32_t tot;
-  const uint32_t ex = block_excl_scan<kStNT>(cnt, lds, &tot);
-  const uint32_t pre = block_lookback<kStNT>(status, tile, tag, tot, &ds->err, s_lb);
-  if (threadIdx.x == 0 && base + kIvTile >= n)  // the last tile
-    __hip_atomic_store(total, pre + tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (tot == 0) return;  // block-uniform
-  const int d = T.d;
-  if (d > kIvMaxD) {  // (wide V: each thread draws its keys' rows in turn)
-    uint32_t e = pre + ex;
-    for (uint32_t m = mask; m; m &= m - 1) {
-      const int64_t u = i0 + (__ffs(m) - 1);
-      uint32_t s = lcg_advance(ds->seed, 3ull * (uint64_t)d * e);
-      const int64_t vr = initv_row(T, ds->n_vrows, e, slot[u]);
-      ++e;
-      if (vr >= T.vcap) {
-        atomicOr(&ds->err, kErrPoolFull);
-        continue;
-      }
-      float* V = row_V(T, vr);
-      float* C = row_C(T, vr);
-      for (int q = 0; q < d; ++q) {
-        V[q] = initv_value(rand_r_dev(&s), scale);
-        C[q] = 0.f;
-      }
-      ent_at(T, slot[u])->vrow = (int32_t)vr;
-    }
-    return;
-  }
-  // the block's requested keys, kIvList at a time, each with its V row and the LCG state at its
-  // first draw (3·d·rank steps past the seed, sgd_updater.cc:118-121), then every (key,
-  // coordinate) drawn by its own thread: coordinate j's state is 3·j steps on (A_j·state + C_j),
-  // the same rand_r values as one thread walking the row — a row's d draws were one lane's d · 3
-  // dependent LCG steps (C5: ~0.1 ms of the step with ~1.5 k requests per 4096-key tile)
-  __shared__ uint32_t s_st[kIvList], s_vr[kIvList];
-  __shared__ uint32_t s_A[kIvMaxD], s_C[kIvMaxD];
-  for (int j = threadIdx.x; j < d; j += kStNT) lcg_jump(3ull * (uint64_t)j, &s_A[j], &s_C[j]);
-  for (uint32_t q0 = 0; q0 < tot; q0 += kIvList) {
-    if (ex < q0 + kIvList && ex + cnt > q0) {
-      uint32_t idx = ex;
-      for (uint32_t m = mask; m; m &= m - 1, ++idx) {
-        if (idx < q0) continue;
-        if (idx >= q0 + kIvList) break;
-        const int64_t u = i0 + (__ffs(m) - 1);
-        const uint32_t e = pre + idx;
-        const int64_t vr = initv_row(T, ds->n_vrows, e, slot[u]);
-        s_st[idx - q0] = lcg_advance(ds->seed, 3ull * (uint64_t)d * e);
-        if (vr >= T.vcap) {
-          atomicOr(&ds->err, kErrPoolFull);
-          s_vr[idx - q0] = 0xFFFFFFFFu;
-        } else {
-          s_vr[idx - q0] = (uint32_t)vr;
-          ent_at(T, slot[u])->vrow = (int32_t)vr;
-        }
-      }
-    }
-    __syncthreads();
-    initv_draw_list<kStNT>(tot - q0 < (uint32_t)kIvList ? tot - q0 : (uint32_t)kIvList, s_st, s_vr,
-                           d, scale, s_A, s_C, [&](uint32_t r) { return row_V(T, r); },
-                           [&](uint32_t r) { return row_C(T, r); });
-    __syncthreads();
-  }
-}
-
-// flags[0..n) -> InitV.  flags is scanned in place; total_dev receives the count.
-int run_initv(Context* c, int64_t n_host, int64_t n_bound, uint32_t* flags, uint32_t* total_dev,
-              const uint32_t* slot, const DevState* nds, const uint32_t* gate, bool finalize,
-              const FinArgs* fin) {
-  if (c->P.V_dim <= 0 || n_bound <= 0) return DFX_OK;
-  if (!nds) nds = c->ds;
-  if (gate && n_host < 0 && !finalize) {  // the fused step
-    const int64_t ntiles = (n_bound + kIvTile - 1) / kIvTile;
-    Workspace& ws = c->ws;
-    void* before = ws.ivstat.p;
-    DFX_TRY(ws.ivstat.ensure((size_t)ntiles * 8));
-    if (ws.ivstat.p != before)  // fresh words read as unpublished (tag 0, flag 0)
-      DFX_HIP(hipMemsetAsync(ws.ivstat.p, 0, ws.ivstat.bytes, c->stream));
-    hipLaunchKernelGGL(k_initv_onepass, dim3((unsigned)ntiles), dim3(kStNT), 0, c->stream, flags,
-                       total_dev, slot, c->T, c->P.V_init_scale, c->ds, nds, gate,
-                       ws.ivstat.as<unsigned long long>(), fin ? *fin : FinArgs{});
-    DFX_HIP(hipGetLastError());
-    return DFX_OK;
-  }
-  DFX_TRY(scan_u32(c, flags, n_bound, total_dev, n_host >= 0 ? nullptr : &nds->u_count, gate));
-  const int64_t nb = (n_bound + kStNT - 1) / kStNT;
-  hipLaunchKernelGGL(k_initv, dim3((unsigned)(gate && nb > 1024 ? 1024 : nb)), dim3(kStNT), 0,
-                     c->stream,
-                     n_host, flags, total_dev, slot, c->T, c->P.V_init_scale, c->ds, nds, gate);
-  if (finalize)
-    hipLaunchKernelGGL(k_initv_finalize, dim3(1), dim3(1), 0, c->stream, total_dev, c->P.V_dim,
-                       c->T.vcap, c->ds);
-  DFX_HIP(hipGetLastError());
-  return DFX_OK;
 }
 
 // ---- Update(kFeaCount) (sgd_updater.cc:64-75) ---------------------------------------------
@@ -352,13 +86,12 @@ __global__ __launch_bounds__(kStNT) void k_push_cnt_seg(const uint32_t* segstart
 }
 
 int push_cnt_seg_run(Context* c, int64_t n_bound, const uint32_t* segstart,
-                     const uint32_t* segslot, uint32_t* flags, uint32_t* total_dev,
-                     const DevState* nds) {
+                     const uint32_t* segslot, uint32_t* flags, const DevState* nds) {
   if (n_bound <= 0) return DFX_OK;
   hipLaunchKernelGGL(k_push_cnt_seg, dim3((n_bound + kStNT - 1) / kStNT), dim3(kStNT), 0,
                      c->stream, segstart, segslot, c->T, c->P, flags, nds);
   DFX_HIP(hipGetLastError());
-  return run_initv(c, -1, n_bound, flags, total_dev, segslot, nds);
+  return run_initv(c, n_bound, flags, segslot, nds);
 }
 
 int push_cnt_seg_flags(Context* c, const Lane& L, int64_t n_bound, const uint32_t* segstart,
@@ -1021,7 +754,7 @@ static int store_push(Context* c, const uint64_t* keys, int64_t n, int type, con
     hipLaunchKernelGGL(k_push_cnt, dim3((n + kStNT - 1) / kStNT), dim3(kStNT), 0, c->stream, n,
                        keys, vals, c->T, c->P, slot, flags, c->ds);
     DFX_HIP(hipGetLastError());
-    return run_initv(c, n, n, flags, total, slot);
+    return run_initv(c, n, flags, slot);
   }
   if (type != DFX_GRADIENT) {
     set_error("UNKNOWN value_type (sgd_updater.cc:100)");
@@ -1041,7 +774,7 @@ static int store_push(Context* c, const uint64_t* keys, int64_t n, int type, con
   hipLaunchKernelGGL(k_push_grad, dim3((n + kStNT - 1) / kStNT), dim3(kStNT), 0, c->stream, n,
                      keys, vals, lens, off, c->T, c->P, slot, flags, c->ds);
   DFX_HIP(hipGetLastError());
-  return run_initv(c, n, n, flags, total, slot);
+  return run_initv(c, n, flags, slot);
 }
 
 int dfx_store_reserve(dfx_ctx* ctx, int64_t n_keys, int64_t n_vrows) {

@@ -28,12 +28,17 @@ CFGS = {
     "fm_v5_odd": dict(V_dim=5, V_threshold=2, lr=0.05, l1=0.1, seed=11),
     "logit": dict(V_dim=0, lr=0.2, l1=0.05),
     "fm_v64": dict(V_dim=64, V_threshold=0, lr=0.05, V_lr=0.01, l1=0.0, seed=9),
+    # wider than InitV's coordinate-per-thread draw (common.h kIvMaxD): a row per thread
+    # (257: the owner's forward / backward have no kernel for 260, "unsupported V_dim")
+    "fm_v257_wide": dict(V_dim=257, V_threshold=0, lr=0.05, V_lr=0.01, l1=0.0, seed=17),
 }
 
 
-def _run(N, kw, steps, rows=400, nnz=12, key_space=6000, jobs=None, empty=()):
+def _run(N, kw, steps, rows=400, nnz=12, key_space=6000, jobs=None, empty=(), push_steps=2,
+         after_step=None):
     """N loopback shards through dist.split_step against the oracle's single updater on the
-    concatenated batches; returns the contexts (closed by the caller) and the oracle"""
+    concatenated batches; returns the contexts (closed by the caller) and the oracle.
+    after_step(ctxs, one, seen, s): further checks after step s"""
     from difacto_amd import dist as DI
     from difacto_amd import hotpath as H
     ctxs = [H.Context(0, max_keys=1 << 16, push_agg="sum", **kw) for _ in range(N)]
@@ -46,7 +51,7 @@ def _run(N, kw, steps, rows=400, nnz=12, key_space=6000, jobs=None, empty=()):
                             binary=(r % 2 == 0), seed=900 + 37 * s + r, ragged=(s == 2))
                 for r in range(N)]
         job = jobs[s] if jobs else H.kTraining
-        push = s < 2
+        push = s < push_steps
         dbs = [H.DeviceRowBlock(ctxs[r], step[r]) for r in range(N)]
         preds = [torch.zeros(max(step[r].size, 1), dtype=torch.float32, device=ctxs[r].device)
                  for r in range(N)]
@@ -70,6 +75,8 @@ def _run(N, kw, steps, rows=400, nnz=12, key_space=6000, jobs=None, empty=()):
             b0 += B
         assert got == pytest.approx(loss, rel=1e-5), (N, s)
         seen.append(cat)
+        if after_step:
+            after_step(ctxs, one, seen, s)
     return ctxs, one, seen
 
 
@@ -98,14 +105,39 @@ def _check_model(ctxs, one, seen, N, rtol=1e-5):
     return n_v
 
 
-@pytest.mark.parametrize("N", [1, 2, 3, 8])
-@pytest.mark.parametrize("name", ["fm_v8", "fm_v16", "fm_v5_odd", "logit"])
+@pytest.mark.parametrize("name,N", [(name, N) for name in ["fm_v8", "fm_v16", "fm_v5_odd", "logit"]
+                                    for N in [1, 2, 3, 8]] + [("fm_v257_wide", 2)])
 def test_split_equals_one_step_on_concatenated_batches(name, N):
     kw = CFGS[name]
     ctxs, one, seen = _run(N, kw, steps=5)
     n_v = _check_model(ctxs, one, seen, N)
     if kw.get("V_dim", 0) > 0:
         assert n_v > 0
+    for c in ctxs:
+        c.close()
+
+
+@pytest.mark.parametrize("N", [1, 3])
+def test_split_initv_request_count_changes(N):
+    """a count push in every step, so the owners' InitV request counts go from many to near
+    none: after every step the shared rand_r state and the owners' V rows equal the oracle's (a
+    stale count of step t - 1 in either ranked launch would show as a seed mismatch at step t)"""
+    from difacto_amd import hotpath as H
+    kw = dict(V_dim=16, V_threshold=2, lr=0.1, V_lr=0.01, l1=0.0, l1_shrk=0, seed=3)
+
+    def check(ctxs, one, seen, s):
+        for c in ctxs:
+            c.sync()
+        stats = [H.Store(c).stats() for c in ctxs]
+        assert all(st["seed"] == one.seed for st in stats), (N, s)
+        uniq = np.unique(np.concatenate([O.localize(b.offs, b.ids)[0] for b in seen]))
+        rows = int((one.get(uniq)[1] == kw["V_dim"] + 1).sum())  # l1_shrk=0: every V shows
+        assert sum(st["n_vrows"] for st in stats) == rows, (N, s)
+
+    # the N workers' batches concatenate to 3000 rows of 39
+    ctxs, one, seen = _run(N, kw, steps=6, rows=3000 // N, nnz=39, key_space=1 << 16,
+                           push_steps=6, after_step=check)
+    assert _check_model(ctxs, one, seen, N) > 0
     for c in ctxs:
         c.close()
 
