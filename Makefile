@@ -13,31 +13,35 @@ LIB = difacto_amd/libdifacto_amd.so
 
 HOSTBIN = build/host_tests
 TRAINBIN = build/dfx_train
-HOSTLIB = difacto_amd/host/gpu_adapters.cc difacto_amd/host/reader.cc
+HOSTLIB = difacto_amd/host/gpu_adapters.cc difacto_amd/host/reader.cc \
+  difacto_amd/host/device_reader.cc
+# CityHash64, one text for reader.cc and the device parser (textparse.hip)
+CITYHDR = $(CSRC)/cityhash.h
 HOSTSRC = $(HOSTLIB) difacto_amd/host/dist_store.cc difacto_amd/host/split_learner.cc \
   tests/host/host_tests.cc
 HOSTHDR = difacto_amd/host/iface.h difacto_amd/host/gpu_adapters.h difacto_amd/host/reader.h \
   difacto_amd/host/dist_host.h difacto_amd/host/dist_store.h difacto_amd/host/split_learner.h \
-  include/difacto_amd.h include/difacto_amd_dist.h
+  difacto_amd/host/device_reader.h include/difacto_amd.h include/difacto_amd_dist.h $(CITYHDR)
 HOSTFLAGS = -std=c++14 -O2 -Wall -pthread
 
 READERBIN = build/reader_tests
 GENBIN = build/gen_criteo
 CONVBIN = build/dfx_convert
 RBENCH = build/reader_bench
+TPBIN = build/textparse_tests
 
 DISTLIB = difacto_amd/libdfx_dist.so
 
 all: $(LIB) $(DISTLIB) oracle $(HOSTBIN) $(TRAINBIN) $(READERBIN) $(GENBIN) $(CONVBIN) $(RBENCH) \
-  build/expf_check build/locbench
+  $(TPBIN) build/expf_check build/locbench
 
-$(RBENCH): difacto_amd/host/reader.cc tools/reader_bench.cc difacto_amd/host/reader.h
+$(RBENCH): difacto_amd/host/reader.cc tools/reader_bench.cc difacto_amd/host/reader.h $(CITYHDR)
 	@mkdir -p build
 	g++ $(HOSTFLAGS) -o $@ difacto_amd/host/reader.cc tools/reader_bench.cc
 
 # the data converter (src/reader/converter.h): text formats -> rec (CompressedRowBlock RecordIO)
 $(CONVBIN): difacto_amd/host/reader.cc difacto_amd/host/convert_main.cc difacto_amd/host/reader.h \
-  difacto_amd/host/iface.h
+  difacto_amd/host/iface.h $(CITYHDR)
 	@mkdir -p build
 	g++ $(HOSTFLAGS) -o $@ difacto_amd/host/reader.cc difacto_amd/host/convert_main.cc
 
@@ -47,9 +51,17 @@ $(GENBIN): tools/gen_criteo.cc
 
 # the readers alone (CPU only: no libdifacto_amd)
 $(READERBIN): difacto_amd/host/reader.cc tests/host/reader_tests.cc difacto_amd/host/reader.h \
-  difacto_amd/host/iface.h
+  difacto_amd/host/iface.h $(CITYHDR)
 	@mkdir -p build
 	g++ $(HOSTFLAGS) -o $@ difacto_amd/host/reader.cc tests/host/reader_tests.cc -ldl
+
+# the device text parser, the row gather and DeviceBatchReader against the host reader
+# (dfx_parse_criteo / dfx_gather_rows vs ParseCriteo / GatherRows / BatchReader), plus the CPU
+# modes: the batch planner, the raw-mode chunk cuts, the shared CityHash64
+$(TPBIN): $(HOSTLIB) tests/host/textparse_tests.cc $(HOSTHDR) $(LIB)
+	@mkdir -p build
+	g++ $(HOSTFLAGS) -o $@ $(HOSTLIB) tests/host/textparse_tests.cc -Ldifacto_amd -ldifacto_amd \
+	  -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN/../difacto_amd' -Wl,-rpath,/opt/rocm/lib
 
 # C++ host adapters (the reference's Loss/Updater/Store over the C-ABI) + their test driver;
 # plain g++ against the C-ABI (the sharded store's exchange, dist_host.o, links RCCL)

@@ -93,6 +93,25 @@ _SIGS = {
     "dfx_feeder_create_slots": (ctypes.c_int, [vp, c_i64, c_i64, ctypes.c_int,
                                                ctypes.POINTER(vp)]),
     "dfx_feeder_consumed_back": (ctypes.c_int, [vp, ctypes.c_int]),
+    "dfx_parse_criteo": (ctypes.c_int, [vp, vp, c_i64, ctypes.c_int, c_i64, c_i64, vp, vp, vp,
+                                        vp]),
+    "dfx_parse_criteo_wait": (ctypes.c_int, [vp, vp, i64p]),
+    "dfx_gather_rows": (ctypes.c_int, [vp, vp, vp, vp, vp, c_i64, c_i64, vp, vp, vp, c_i64]),
+    "dfx_textfeed_create": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, c_i64, c_i64,
+                                           ctypes.POINTER(vp)]),
+    "dfx_textfeed_destroy": (ctypes.c_int, [vp]),
+    "dfx_textfeed_text": (ctypes.c_int, [vp, ctypes.c_int, c_i64, ctypes.POINTER(vp)]),
+    "dfx_textfeed_submit": (ctypes.c_int, [vp, ctypes.c_int, c_i64, ctypes.c_int, c_i64]),
+    "dfx_textfeed_wait": (ctypes.c_int, [vp, ctypes.c_int, i64p, ctypes.POINTER(vp),
+                                         ctypes.POINTER(vp)]),
+    "dfx_textfeed_upload": (ctypes.c_int, [vp, ctypes.c_int, c_i64, c_i64, vp, vp, vp]),
+    "dfx_textfeed_batch_begin": (ctypes.c_int, [vp]),
+    "dfx_textfeed_gather": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, c_i64, c_i64,
+                                           c_i64]),
+    "dfx_textfeed_batch_end": (ctypes.c_int, [vp, c_i64, c_i64, ctypes.POINTER(Batch)]),
+    "dfx_textfeed_consumed": (ctypes.c_int, [vp]),
+    "dfx_textfeed_slot_batch": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(Batch)]),
+    "dfx_textfeed_slot_consumed": (ctypes.c_int, [vp, ctypes.c_int]),
     "dfx_dist_record_floats": (ctypes.c_int, [vp]),
     "dfx_dist_localize": (ctypes.c_int, [vp, ctypes.POINTER(Batch), c_u64, ctypes.c_int,
                                          ctypes.c_int, vp, vp]),

@@ -220,6 +220,9 @@ struct Context {
   hipStream_t own_part_stream = nullptr;
   hipStream_t in_stream = nullptr;  // where batches are produced (dfx_ctx_set_input_stream)
   bool has_in_stream = false;
+  // scratch of the text parser and the row gather (textparse.hip), used in the input stream's
+  // order: tile tuples, per-line cell table, per-line arrays, scan partials, counters
+  DevBuf tp_tiles, tp_cells, tp_lines, tp_pair, tp_tot, tp_stat, tg_len, tg_tot;
   Workspace bws[kSlots];  // [0], [1]: also the fused step's Localizer parities
   DevState* bds[kSlots] = {};
   Workspace aws;

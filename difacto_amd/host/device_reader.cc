@@ -1,0 +1,229 @@
+// device_reader.cc — see device_reader.h.
+#include "device_reader.h"
+
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+
+#include "gpu_adapters.h"
+
+namespace difacto {
+
+static double Seconds() {
+  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch())
+      .count();
+}
+
+DeviceTextFeed::DeviceTextFeed(dfx_ctx* ctx, size_t batch_size, size_t shuf_buf)
+    : batch_size_(batch_size ? batch_size : 1), shuf_buf_(shuf_buf) {
+  DfxCheck(dfx_textfeed_create(ctx, kSlots, kRing, (int64_t)batch_size_, (int64_t)shuf_buf_, &h_),
+           "dfx_textfeed_create");
+}
+
+DeviceTextFeed::~DeviceTextFeed() {
+  if (h_) dfx_textfeed_destroy(h_);
+}
+
+// src -> dst over up to nthreads threads; returns the number of '\n' bytes copied
+static size_t CopyCountLines(char* dst, const char* src, size_t bytes, int nthreads) {
+  auto part = [](char* d, const char* s, size_t n) {
+    std::memcpy(d, s, n);
+    size_t c = 0;
+    for (const char *p = d, *e = d + n; p < e; ++p, ++c) {
+      p = static_cast<const char*>(std::memchr(p, '\n', e - p));
+      if (!p) break;
+    }
+    return c;
+  };
+  const int T = (int)std::min<size_t>(std::max(nthreads, 1), 1 + bytes / (1 << 20));
+  if (T <= 1) return part(dst, src, bytes);
+  std::vector<size_t> cnt(T, 0);
+  std::vector<std::thread> th;
+  for (int t = 0; t < T; ++t) {
+    const size_t a = bytes * t / T, b = bytes * (t + 1) / T;
+    th.emplace_back([&, t, a, b]() { cnt[t] = part(dst + a, src + a, b - a); });
+  }
+  size_t total = 0;
+  for (int t = 0; t < T; ++t) {
+    th[t].join();
+    total += cnt[t];
+  }
+  return total;
+}
+
+DeviceBatchReader::DeviceBatchReader(DeviceTextFeed* feed, const std::string& path,
+                                     const std::string& format, int part, int nparts,
+                                     size_t batch_size, size_t shuf_buf, float neg_sampling,
+                                     int nthreads, size_t chunk_bytes)
+    : f_(feed->h()),
+      reader_(path, format, part, nparts, chunk_bytes, nthreads, 0),
+      train_(format != "criteo_test"),
+      batch_size_(batch_size),
+      nthreads_(nthreads < 1 ? 1 : nthreads) {
+  DFX_HOST_CHECK(format == "criteo" || format == "criteo_test",
+                 "the device reader parses criteo and criteo_test, not " + format);
+  DFX_HOST_CHECK(batch_size <= feed->batch_size() && shuf_buf <= feed->shuf_buf(),
+                 "batch or shuffle buffer larger than the text feed's");
+  if (batch_size_) {
+    planner_.reset(new BatchPlanner(
+        batch_size, shuf_buf, neg_sampling,
+        [this](size_t* rows, const uint64_t** off, const float** lab) {
+          return FetchChunk(rows, off, lab);
+        },
+        [this](const GatherOp& op) {
+          const int src = op.src == GatherOp::kShuffle ? -1 : seq_slot_[op.src];
+          DfxCheck(dfx_textfeed_gather(f_, src, op.to_batch ? 1 : 0,
+                                       op.rows.empty() ? nullptr : op.rows.data(),
+                                       (int64_t)op.begin, (int64_t)op.n, (int64_t)op.r0),
+                   "dfx_textfeed_gather");
+        }));
+  }
+  for (int s = 0; s < DeviceTextFeed::kSlots; ++s) free_.push_back(s);
+  loader_ = std::thread([this]() { Load(); });
+}
+
+DeviceBatchReader::~DeviceBatchReader() {
+  {
+    std::lock_guard<std::mutex> lk(mu_);
+    stop_ = true;
+  }
+  cv_.notify_all();
+  loader_.join();
+  // parses still in flight read the slots' pinned text
+  for (const Filled& c : submitted_) {
+    int64_t stat[4];
+    (void)dfx_textfeed_wait(f_, c.slot, stat, nullptr, nullptr);
+  }
+}
+
+void DeviceBatchReader::Load() {
+  for (;;) {
+    int slot;
+    {
+      std::unique_lock<std::mutex> lk(mu_);
+      cv_.wait(lk, [this]() { return stop_ || !free_.empty(); });
+      if (stop_) return;
+      slot = free_.front();
+      free_.pop_front();
+    }
+    const char* data;
+    size_t size;
+    if (!reader_.NextRaw(&data, &size)) {
+      {
+        std::lock_guard<std::mutex> lk(mu_);
+        eof_ = true;
+      }
+      cv_.notify_all();
+      return;
+    }
+    char* dst = nullptr;
+    DfxCheck(dfx_textfeed_text(f_, slot, (int64_t)size, &dst), "dfx_textfeed_text");
+    const double t0 = Seconds();
+    const size_t nl = CopyCountLines(dst, data, size, nthreads_);
+    {
+      std::lock_guard<std::mutex> lk(mu_);
+      times_.copy += Seconds() - t0;
+      filled_.push_back(Filled{slot, size, nl});
+    }
+    cv_.notify_all();
+  }
+}
+
+void DeviceBatchReader::SubmitFilled(bool wait) {
+  std::deque<Filled> take;
+  {
+    std::unique_lock<std::mutex> lk(mu_);
+    if (wait) {
+      const double t0 = Seconds();
+      cv_.wait(lk, [this]() { return eof_ || !filled_.empty(); });
+      times_.wait_text += Seconds() - t0;
+    }
+    take.swap(filled_);
+  }
+  for (const Filled& c : take) {
+    // rows <= lines <= newlines: whole lines, the last one terminated (TextReader::NextRaw)
+    DfxCheck(dfx_textfeed_submit(f_, c.slot, (int64_t)c.bytes, train_ ? 1 : 0,
+                                 (int64_t)c.newlines),
+             "dfx_textfeed_submit");
+    submitted_.push_back(c);
+  }
+}
+
+void DeviceBatchReader::ReleaseChunk() {
+  if (cur_slot_ < 0) return;
+  {
+    std::lock_guard<std::mutex> lk(mu_);
+    free_.push_back(cur_slot_);
+  }
+  cv_.notify_all();
+  cur_slot_ = -1;
+}
+
+bool DeviceBatchReader::FetchChunk(size_t* rows, const uint64_t** off, const float** lab) {
+  ReleaseChunk();
+  SubmitFilled(false);
+  if (submitted_.empty()) {
+    SubmitFilled(true);
+    if (submitted_.empty()) return false;  // the end of the part
+  }
+  const Filled c = submitted_.front();
+  submitted_.pop_front();
+  int64_t stat[4];
+  const double t0 = Seconds();
+  DfxCheck(dfx_textfeed_wait(f_, c.slot, stat, off, lab), "dfx_textfeed_wait");
+  times_.wait_parse += Seconds() - t0;
+  SubmitFilled(false);  // slots filled meanwhile: their parses run beside this chunk's batches
+  *rows = (size_t)stat[0];
+  if (stat[2]) {  // needs_host: the host parser's rows into the same device arrays
+    ++fallback_;
+    char* text = nullptr;
+    DfxCheck(dfx_textfeed_text(f_, c.slot, (int64_t)c.bytes, &text), "dfx_textfeed_text");
+    reader_.ParseChunk(text, c.bytes, &host_blk_);
+    static_assert(sizeof(size_t) == sizeof(uint64_t), "size_t offsets");
+    DfxCheck(dfx_textfeed_upload(f_, c.slot, (int64_t)host_blk_.Size(),
+                                 (int64_t)host_blk_.index.size(),
+                                 reinterpret_cast<const uint64_t*>(host_blk_.offset.data()),
+                                 host_blk_.index.data(), host_blk_.label.data()),
+             "dfx_textfeed_upload");
+    *rows = host_blk_.Size();
+    *off = reinterpret_cast<const uint64_t*>(host_blk_.offset.data());
+    *lab = host_blk_.label.data();
+  }
+  cur_slot_ = c.slot;
+  seq_slot_.push_back(c.slot);
+  chunk_lab_ = *lab;
+  return true;
+}
+
+bool DeviceBatchReader::Next() {
+  if (!batch_size_) {  // every chunk one batch
+    size_t rows = 0;
+    const uint64_t* off;
+    const float* lab;
+    do {
+      if (!FetchChunk(&rows, &off, &lab)) return false;
+    } while (rows == 0);
+    DfxCheck(dfx_textfeed_slot_batch(f_, cur_slot_, &batch_), "dfx_textfeed_slot_batch");
+    slot_batch_ = true;
+    return true;
+  }
+  const double t0 = Seconds();
+  DfxCheck(dfx_textfeed_batch_begin(f_), "dfx_textfeed_batch_begin");
+  times_.wait_step += Seconds() - t0;
+  size_t rows, nnz;
+  if (!planner_->Next(&rows, &nnz)) return false;
+  DfxCheck(dfx_textfeed_batch_end(f_, (int64_t)rows, (int64_t)nnz, &batch_),
+           "dfx_textfeed_batch_end");
+  slot_batch_ = false;
+  return true;
+}
+
+void DeviceBatchReader::Consumed() {
+  if (slot_batch_) {
+    DfxCheck(dfx_textfeed_slot_consumed(f_, cur_slot_), "dfx_textfeed_slot_consumed");
+  } else {
+    DfxCheck(dfx_textfeed_consumed(f_), "dfx_textfeed_consumed");
+  }
+}
+
+}  // namespace difacto

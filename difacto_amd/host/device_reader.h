@@ -1,0 +1,115 @@
+// device_reader.h — Criteo minibatches formed on the device from raw text.
+//
+// The host reader (reader.h) tokenises, hashes and copies every row on CPU threads.  Here the
+// host's per-byte work is one copy of the raw chunk into pinned memory; the device parses it
+// (dfx_parse_criteo), the batch planner (reader.h BatchPlanner) runs on the host from the
+// parsed chunk's offsets and labels (12 bytes a row), and the row copies of the plan run on
+// the device (dfx_gather_rows) into a ring of device batches — the batches BatchReader forms
+// (src/reader/batch_reader.cc:29-78) for the chunks TextReader cuts (src/reader/reader.h:18-55).
+//
+//   loader thread   TextReader::NextRaw -> parallel copy into a pinned text slot, counting
+//                   newlines (max_rows; 39 ids a row at most size the rest)
+//   caller's thread dfx_textfeed_submit (upload, parse, offsets / labels back) as soon as a
+//                   slot is filled, so the chunk after next is parsed while the current
+//                   chunk's batches train; the planner and its gathers per Next()
+//
+// A chunk the device flags (needs_host: the forms listed in include/difacto_amd.h) is parsed
+// by ParseCriteo on the host and uploaded into the same device arrays; FallbackChunks counts
+// them.  criteo and criteo_test only.
+#ifndef DIFACTO_AMD_HOST_DEVICE_READER_H_
+#define DIFACTO_AMD_HOST_DEVICE_READER_H_
+
+#include <condition_variable>
+#include <deque>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../../include/difacto_amd.h"
+#include "reader.h"
+
+namespace difacto {
+
+/** the device side shared by the readers of a run: pinned text slots, parsed chunks, the
+ * shuffle buffer and the batch ring (dfx_textfeed); its loader stream is the context's input
+ * stream while it lives */
+class DeviceTextFeed {
+ public:
+  static constexpr int kSlots = 3, kRing = 3;
+  DeviceTextFeed(dfx_ctx* ctx, size_t batch_size, size_t shuf_buf);
+  ~DeviceTextFeed();
+  DeviceTextFeed(const DeviceTextFeed&) = delete;
+  DeviceTextFeed& operator=(const DeviceTextFeed&) = delete;
+  dfx_textfeed* h() const { return h_; }
+  size_t batch_size() const { return batch_size_; }
+  size_t shuf_buf() const { return shuf_buf_; }
+
+ private:
+  dfx_textfeed* h_ = nullptr;
+  size_t batch_size_, shuf_buf_;
+};
+
+class DeviceBatchReader {
+ public:
+  /** batch_size == 0: every chunk is one batch (validation and prediction read chunk_bytes =
+   * 256 MB chunks as batches, sgd_learner.cc:281-286); else BatchReader's batches, with
+   * batch_size and shuf_buf within the feed's.  One reader at a time uses a feed. */
+  DeviceBatchReader(DeviceTextFeed* feed, const std::string& path, const std::string& format,
+                    int part, int nparts, size_t batch_size, size_t shuf_buf, float neg_sampling,
+                    int nthreads = 8, size_t chunk_bytes = 64 << 20);
+  ~DeviceBatchReader();
+  DeviceBatchReader(const DeviceBatchReader&) = delete;
+  DeviceBatchReader& operator=(const DeviceBatchReader&) = delete;
+  /** the next batch, queued on the device (asynchronous); false at the end of the part */
+  bool Next();
+  const dfx_batch& Value() const { return batch_; }
+  /** after the dfx_train_step that took Value() was queued: its arrays are in use until then */
+  void Consumed();
+  /** whole-chunk mode: the current chunk's labels on the host (the copy back of the parse) */
+  const float* HostLabels() const { return chunk_lab_; }
+  /** chunks the device handed back to the host parser so far */
+  size_t FallbackChunks() const { return fallback_; }
+  /** where the reader's time went, in seconds: the loader thread's copies into pinned memory;
+   * the caller blocked on a text slot being filled (the host copy is the limit), on a chunk's
+   * parse (upload + parse kernels), on a ring batch being consumed (the step) */
+  struct Times {
+    double copy = 0, wait_text = 0, wait_parse = 0, wait_step = 0;
+  };
+  Times TimesSpent() const { return times_; }
+
+ private:
+  struct Filled {
+    int slot;
+    size_t bytes, newlines;
+  };
+  void Load();                  // the loader thread
+  void SubmitFilled(bool wait); // queue the parses of the filled slots
+  bool FetchChunk(size_t* rows, const uint64_t** off, const float** lab);
+  void ReleaseChunk();
+  dfx_textfeed* f_;
+  TextReader reader_;
+  bool train_;
+  size_t batch_size_;
+  int nthreads_;
+  std::unique_ptr<BatchPlanner> planner_;
+  std::thread loader_;
+  std::mutex mu_;
+  std::condition_variable cv_;
+  std::deque<int> free_;
+  std::deque<Filled> filled_;
+  bool eof_ = false, stop_ = false;
+  std::deque<Filled> submitted_;
+  int cur_slot_ = -1;               // the chunk the planner reads (or the whole-chunk batch)
+  std::vector<int> seq_slot_;       // chunk sequence number -> slot
+  RowBlockContainer<feaid_t> host_blk_;  // a flagged chunk, parsed on the host
+  const float* chunk_lab_ = nullptr;
+  size_t fallback_ = 0;
+  Times times_;  // copy: written by the loader thread, read after it has ended or between chunks
+  dfx_batch batch_{};
+  bool slot_batch_ = false;
+};
+
+}  // namespace difacto
+#endif  // DIFACTO_AMD_HOST_DEVICE_READER_H_

@@ -506,6 +506,26 @@ void GpuSGDLearner::ProcessBatch(const dmlc::RowBlock<feaid_t>& batch, int job_t
   }
 }
 
+void GpuSGDLearner::ProcessDeviceBatch(const dfx_batch& batch, int job_type, bool push_cnt,
+                                       std::vector<real_t>* pred_out) {
+  DFX_HOST_CHECK(fused_, "device batches run the fused path (fused=1)");
+  push_cnt = push_cnt && job_type == kTraining && V_dim_ > 0;
+  dfx_ctx* c = updater_->context()->h();
+  float* dp = nullptr;
+  if (pred_out) {
+    if (!dpred_) dpred_.reset(new DevArray<float>(c));
+    dpred_->ensure((size_t)batch.size);
+    dp = dpred_->get();
+  }
+  DfxCheck(dfx_train_step(c, &batch, job_type, push_cnt ? 1 : 0,
+                          std::numeric_limits<uint64_t>::max(), dp),
+           "dfx_train_step");
+  if (pred_out) {
+    pred_out->resize((size_t)batch.size);
+    dpred_->download(pred_out->data(), (size_t)batch.size);
+  }
+}
+
 Progress GpuSGDLearner::TakeProgress() {
   Progress out = prog_;
   prog_ = Progress();

@@ -181,6 +181,13 @@ class GpuSGDLearner {
    * receives the batch's predictions (joins the device), as SavePred writes them. */
   void ProcessBatch(const dmlc::RowBlock<feaid_t>& batch, int job_type, bool push_cnt,
                     std::vector<real_t>* pred = nullptr);
+  /** the fused path for a batch already on the device (DeviceBatchReader, device_reader.h):
+   * dfx_train_step without the pinned copy; the batch's producer is the context's input
+   * stream.  pred (optional) receives the predictions (joins the device). */
+  void ProcessDeviceBatch(const dfx_batch& batch, int job_type, bool push_cnt,
+                          std::vector<real_t>* pred = nullptr);
+  /** the learner's device context (the fused path's; null when a Store was given) */
+  dfx_ctx* context() const { return updater_ ? updater_->context()->h() : nullptr; }
   /** sgd::Progress accumulated since the last call (joins the device) */
   Progress TakeProgress();
   /** the learner's own updater (null when a Store was given) */

@@ -13,130 +13,12 @@
 #include <limits>
 #include <thread>
 
+#include "../csrc/cityhash.h"
+
 namespace difacto {
 
-// ---- CityHash64 v1.1 (published algorithm, restated) ------------------------------------
-namespace {
-constexpr uint64_t k0 = 0xc3a5c85c97cb3127ULL;
-constexpr uint64_t k1 = 0xb492b66fbe98f273ULL;
-constexpr uint64_t k2 = 0x9ae16a3b2f90404fULL;
-
-inline uint64_t Fetch64(const char* p) {
-  uint64_t r;
-  std::memcpy(&r, p, 8);
-  return r;
-}
-inline uint32_t Fetch32(const char* p) {
-  uint32_t r;
-  std::memcpy(&r, p, 4);
-  return r;
-}
-inline uint64_t Rotate(uint64_t v, int s) { return s == 0 ? v : ((v >> s) | (v << (64 - s))); }
-inline uint64_t ShiftMix(uint64_t v) { return v ^ (v >> 47); }
-inline uint64_t HashLen16(uint64_t u, uint64_t v, uint64_t mul) {
-  uint64_t a = (u ^ v) * mul;
-  a ^= (a >> 47);
-  uint64_t b = (v ^ a) * mul;
-  b ^= (b >> 47);
-  b *= mul;
-  return b;
-}
-inline uint64_t HashLen16(uint64_t u, uint64_t v) {
-  return HashLen16(u, v, 0x9ddfea08eb382d69ULL);
-}
-uint64_t HashLen0to16(const char* s, size_t len) {
-  if (len >= 8) {
-    const uint64_t mul = k2 + len * 2;
-    const uint64_t a = Fetch64(s) + k2;
-    const uint64_t b = Fetch64(s + len - 8);
-    const uint64_t c = Rotate(b, 37) * mul + a;
-    const uint64_t d = (Rotate(a, 25) + b) * mul;
-    return HashLen16(c, d, mul);
-  }
-  if (len >= 4) {
-    const uint64_t mul = k2 + len * 2;
-    const uint64_t a = Fetch32(s);
-    return HashLen16(len + (a << 3), Fetch32(s + len - 4), mul);
-  }
-  if (len > 0) {
-    const uint8_t a = (uint8_t)s[0], b = (uint8_t)s[len >> 1], c = (uint8_t)s[len - 1];
-    const uint32_t y = (uint32_t)a + ((uint32_t)b << 8);
-    const uint32_t z = (uint32_t)len + ((uint32_t)c << 2);
-    return ShiftMix(y * k2 ^ z * k0) * k2;
-  }
-  return k2;
-}
-uint64_t HashLen17to32(const char* s, size_t len) {
-  const uint64_t mul = k2 + len * 2;
-  const uint64_t a = Fetch64(s) * k1;
-  const uint64_t b = Fetch64(s + 8);
-  const uint64_t c = Fetch64(s + len - 8) * mul;
-  const uint64_t d = Fetch64(s + len - 16) * k2;
-  return HashLen16(Rotate(a + b, 43) + Rotate(c, 30) + d, a + Rotate(b + k2, 18) + c, mul);
-}
-inline std::pair<uint64_t, uint64_t> WeakHashLen32WithSeeds(uint64_t w, uint64_t x, uint64_t y,
-                                                            uint64_t z, uint64_t a,
-                                                            uint64_t b) {
-  a += w;
-  b = Rotate(b + a + z, 21);
-  const uint64_t c = a;
-  a += x;
-  a += y;
-  b += Rotate(a, 44);
-  return {a + z, b + c};
-}
-inline std::pair<uint64_t, uint64_t> WeakHashLen32WithSeeds(const char* s, uint64_t a,
-                                                            uint64_t b) {
-  return WeakHashLen32WithSeeds(Fetch64(s), Fetch64(s + 8), Fetch64(s + 16), Fetch64(s + 24), a,
-                                b);
-}
-uint64_t HashLen33to64(const char* s, size_t len) {
-  const uint64_t mul = k2 + len * 2;
-  uint64_t a = Fetch64(s) * k2;
-  uint64_t b = Fetch64(s + 8);
-  const uint64_t c = Fetch64(s + len - 24);
-  const uint64_t d = Fetch64(s + len - 32);
-  const uint64_t e = Fetch64(s + 16) * k2;
-  const uint64_t f = Fetch64(s + 24) * 9;
-  const uint64_t g = Fetch64(s + len - 8);
-  const uint64_t h = Fetch64(s + len - 16) * mul;
-  const uint64_t u = Rotate(a + g, 43) + (Rotate(b, 30) + c) * 9;
-  const uint64_t v = ((a + g) ^ d) + f + 1;
-  const uint64_t w = __builtin_bswap64((u + v) * mul) + h;
-  const uint64_t x = Rotate(e + f, 42) + c;
-  const uint64_t y = (__builtin_bswap64((v + w) * mul) + g) * mul;
-  const uint64_t z = e + f + c;
-  a = __builtin_bswap64((x + z) * mul + y) + b;
-  b = ShiftMix((z + a) * mul + d + h) * mul;
-  return b + x;
-}
-}  // namespace
-
-uint64_t CityHash64(const char* s, size_t len) {
-  if (len <= 32) return len <= 16 ? HashLen0to16(s, len) : HashLen17to32(s, len);
-  if (len <= 64) return HashLen33to64(s, len);
-  uint64_t x = Fetch64(s + len - 40);
-  uint64_t y = Fetch64(s + len - 16) + Fetch64(s + len - 56);
-  uint64_t z = HashLen16(Fetch64(s + len - 48) + len, Fetch64(s + len - 24));
-  auto v = WeakHashLen32WithSeeds(s + len - 64, len, z);
-  auto w = WeakHashLen32WithSeeds(s + len - 32, y + k1, x);
-  x = x * k1 + Fetch64(s);
-  len = (len - 1) & ~static_cast<size_t>(63);
-  do {
-    x = Rotate(x + y + v.first + Fetch64(s + 8), 37) * k1;
-    y = Rotate(y + v.second + Fetch64(s + 48), 42) * k1;
-    x ^= w.second;
-    y += v.first + Fetch64(s + 40);
-    z = Rotate(z + w.first, 33) * k1;
-    v = WeakHashLen32WithSeeds(s, v.second * k1, x + w.first);
-    w = WeakHashLen32WithSeeds(s + 32, z + w.second, y + Fetch64(s + 16));
-    std::swap(z, x);
-    s += 64;
-    len -= 64;
-  } while (len != 0);
-  return HashLen16(HashLen16(v.first, w.first) + ShiftMix(y) * k1 + z,
-                   HashLen16(v.second, w.second) + x);
-}
+// ---- CityHash64 v1.1: csrc/cityhash.h, the text the device parser compiles too ------------
+uint64_t CityHash64(const char* s, size_t len) { return dfx_city::CityHash64(s, len); }
 
 // ---- parsers ----------------------------------------------------------------------------
 void ParseLibSVM(const char* p, const char* e, RowBlockContainer<feaid_t>* out) {
@@ -782,9 +664,22 @@ void TextReader::RunAhead() {
   }
 }
 
+bool TextReader::NextRaw(const char** data, size_t* size) {
+  DFX_HOST_CHECK(!rec_ && !parser_.joinable(), "NextRaw: text formats, not mixed with Next");
+  return CutNext(data, size);
+}
+
 bool TextReader::ParseNext() {
   ClearRows(&blk_);
   if (rec_) return NextRec();
+  const char* buf;
+  size_t cut;
+  if (!CutNext(&buf, &cut)) return false;
+  ParseChunk(buf, cut, &blk_);
+  return blk_.Size() > 0 || pos_ < end_;
+}
+
+bool TextReader::CutNext(const char** data, size_t* size) {
   if (pos_ >= end_) return false;
   // whole lines only: the chunk ends after its last newline (or, for a line longer than the
   // chunk, after that line) unless the part ends first
@@ -811,6 +706,13 @@ bool TextReader::ParseNext() {
   }
   pos_ += cut;
   read_ += cut;
+  *data = buf;
+  *size = cut;
+  return true;
+}
+
+void TextReader::ParseChunk(const char* buf, size_t cut, RowBlockContainer<feaid_t>* out) {
+  ClearRows(out);
   // split at line boundaries over the worker threads, parse, concatenate in order
   std::vector<size_t> cuts{0};
   for (int t = 1; t < nthreads_; ++t) {
@@ -843,15 +745,14 @@ bool TextReader::ParseNext() {
     });
   }
   for (auto& x : th) x.join();
-  ConcatParts(&parts_, &blk_);
-  return blk_.Size() > 0 || pos_ < end_;
+  ConcatParts(&parts_, out);
 }
 
 // ---- BatchReader ------------------------------------------------------------------------
 BatchReader::BatchReader(const std::string& path, const std::string& format, int part,
                          int nparts, size_t batch_size, size_t shuf_buf, float neg_sampling,
-                         int nthreads)
-    : reader_(path, format, part, nparts, 64 << 20, nthreads, shuf_buf ? 4 : 2),
+                         int nthreads, size_t chunk_bytes)
+    : reader_(path, format, part, nparts, chunk_bytes, nthreads, shuf_buf ? 4 : 2),
       batch_size_(batch_size),
       shuf_buf_(shuf_buf),
       neg_sampling_(neg_sampling),
@@ -931,6 +832,128 @@ bool BatchReader::Next() {
     }
   if (binary) batch_.value.clear();
   return batch_.Size() > 0;
+}
+
+// ---- BatchPlanner -----------------------------------------------------------------------
+// BatchReader::Refill / Next with every GatherRows replaced by an emitted GatherOp and every
+// container by its row lengths and labels; keep the two in step.
+BatchPlanner::BatchPlanner(size_t batch_size, size_t shuf_buf, float neg_sampling,
+                           ChunkFn next_chunk, EmitFn emit)
+    : batch_size_(batch_size),
+      shuf_buf_(shuf_buf),
+      neg_sampling_(neg_sampling),
+      next_chunk_(std::move(next_chunk)),
+      emit_(std::move(emit)) {
+  DFX_HOST_CHECK(batch_size > 0, "batch_size must be > 0");
+  DFX_HOST_CHECK(shuf_buf == 0 || shuf_buf >= batch_size, "shuffle buffer < batch size");
+}
+
+bool BatchPlanner::NextChunk() {  // reader_.Next()
+  chunk_rows_ = 0;
+  if (done_) return false;
+  if (!next_chunk_(&chunk_rows_, &chunk_off_, &chunk_lab_)) {
+    done_ = true;
+    chunk_rows_ = 0;
+    return false;
+  }
+  ++chunk_seq_;
+  return true;
+}
+
+size_t BatchPlanner::Len(size_t j) const {
+  return src_shuffle_ ? in_len_[j] : (size_t)(chunk_off_[j + 1] - chunk_off_[j]);
+}
+
+bool BatchPlanner::Refill() {
+  start_ = 0;
+  order_.clear();
+  if (!shuf_buf_) {
+    do {
+      if (!NextChunk()) return false;
+    } while (chunk_rows_ == 0);
+    src_shuffle_ = false;
+    have_src_ = true;
+    order_.resize(chunk_rows_);
+    for (size_t i = 0; i < order_.size(); ++i) order_[i] = i;
+    return true;
+  }
+  in_len_.clear();
+  in_lab_.clear();
+  src_shuffle_ = true;
+  have_src_ = true;
+  while (in_len_.size() < shuf_buf_) {
+    if (pend_pos_ >= chunk_rows_) {
+      if (!NextChunk()) break;
+      pend_pos_ = 0;
+      continue;
+    }
+    const size_t take = std::min(shuf_buf_ - in_len_.size(), chunk_rows_ - pend_pos_);
+    GatherOp op;
+    op.src = chunk_seq_;
+    op.to_batch = false;
+    op.begin = pend_pos_;
+    op.n = take;
+    op.r0 = in_len_.size();
+    emit_(op);
+    for (size_t j = pend_pos_; j < pend_pos_ + take; ++j) {
+      in_len_.push_back((uint32_t)(chunk_off_[j + 1] - chunk_off_[j]));
+      in_lab_.push_back(chunk_lab_[j]);
+    }
+    pend_pos_ += take;
+  }
+  order_.resize(in_len_.size());
+  for (size_t i = 0; i < order_.size(); ++i) order_[i] = i;
+  std::shuffle(order_.begin(), order_.end(), shuffle_rng_);
+  return !in_len_.empty();
+}
+
+bool BatchPlanner::Next(size_t* rows, size_t* nnz) {
+  batch_rows_ = batch_nnz_ = 0;
+  sel_.clear();
+  auto flush = [&]() {
+    if (sel_.empty()) return;
+    GatherOp op;
+    op.src = src_shuffle_ ? (int)GatherOp::kShuffle : chunk_seq_;
+    op.n = sel_.size();
+    op.r0 = batch_rows_;
+    for (uint32_t j : sel_) batch_nnz_ += Len(j);
+    op.rows.swap(sel_);
+    emit_(op);
+    batch_rows_ += op.n;
+    sel_.clear();
+  };
+  while (batch_rows_ + sel_.size() < batch_size_) {
+    if (start_ >= order_.size()) {
+      if (have_src_ && !sel_.empty()) flush();
+      if (!Refill()) break;
+    }
+    if (!shuf_buf_ && neg_sampling_ >= 1.f) {  // rows in file order: one bulk copy
+      const size_t len = std::min(order_.size() - start_, batch_size_ - batch_rows_);
+      GatherOp op;
+      op.src = chunk_seq_;
+      op.begin = start_;
+      op.n = len;
+      op.r0 = batch_rows_;
+      emit_(op);
+      batch_nnz_ += (size_t)(chunk_off_[start_ + len] - chunk_off_[start_]);
+      batch_rows_ += len;
+      start_ += len;
+      continue;
+    }
+    const float* lab = src_shuffle_ ? in_lab_.data() : chunk_lab_;
+    while (start_ < order_.size() && batch_rows_ + sel_.size() < batch_size_) {
+      const size_t j = order_[start_++];
+      if (neg_sampling_ < 1.f) {
+        const float p = (float)rand_r(&seed_) / (float)RAND_MAX;
+        if (lab[j] <= 0 && p > 1 - neg_sampling_) continue;
+      }
+      sel_.push_back((uint32_t)j);
+    }
+  }
+  if (!sel_.empty()) flush();
+  *rows = batch_rows_;
+  *nnz = batch_nnz_;
+  return batch_rows_ > 0;
 }
 
 // ---- ThreadedBatchReader ----------------------------------------------------------------

@@ -17,12 +17,20 @@
 //   BatchReader     src/reader/batch_reader.cc:29-78: batch_size rows per batch, a shuffle
 //                   buffer of shuf_buf rows, negative down-sampling with rand_r, all-one
 //                   values dropped (binary data)
+//   BatchPlanner    the same batches planned from row lengths and labels alone, as a list of
+//                   row copies: the host half of the device reader (device_reader.h), which
+//                   reads raw chunks (TextReader::NextRaw, cut where Next cuts them), parses
+//                   criteo text on the device (dfx_parse_criteo) and carries the plan out with
+//                   device gathers (dfx_gather_rows).  The default stays this host reader.
 //
 // Parity notes: the LZ4 block codec and the dmlc RecordIO framing are third-party formats
 // (lz4, dmlc-core: un-vendored in the reference tree) restated from their published
 // specifications; the CPU tests pin the codec against the image's liblz4.so.1 in both
 // directions.  CityHash64 is the published v1.1 algorithm restated (the library is not in
-// the reference tree; no test vectors are available here, so criteo ids are parity unpinned).
+// the reference tree; no test vectors are available here, so criteo ids are parity unpinned
+// against the reference).  It lives in csrc/cityhash.h, the one text this reader and the device
+// parser compile; tests/golden/cityhash_cells.json pins its values across builds, and the GPU
+// tests pin the device parser to ParseCriteo byte for byte.
 // The shuffle permutes with std::mt19937 (seed 0) where the reference calls
 // std::random_shuffle on glibc rand(); shuffled batch membership is parity unpinned
 // (SURVEY.md §8(d)), unshuffled reading (shuffle = 0) matches the reference's row order.
@@ -33,6 +41,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <deque>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <random>
@@ -112,8 +121,17 @@ class TextReader {
   bool Next();
   const RowBlockContainer<feaid_t>& Value() const { return ahead_ ? cur_ : blk_; }
   size_t BytesRead() const { return read_; }
+  /** raw mode (text formats, ahead == 0, not mixed with Next): the bytes of the next chunk,
+   * cut exactly where Next cuts it (same part range, same line boundary, an unterminated last
+   * line as a terminated copy), not parsed; valid until the next call.  A device parser that
+   * reads chunks this way sees the chunks the host reader parses. */
+  bool NextRaw(const char** data, size_t* size);
+  /** parse one chunk of whole lines (as NextRaw returns it) into *out with this reader's
+   * format and threads: what Next does to the chunk */
+  void ParseChunk(const char* data, size_t size, RowBlockContainer<feaid_t>* out);
 
  private:
+  bool CutNext(const char** data, size_t* size);  // the next chunk's bytes
   bool ParseNext();  // the next chunk into blk_
   void RunAhead();
   int ahead_ = 0;
@@ -141,7 +159,8 @@ class TextReader {
 class BatchReader {
  public:
   BatchReader(const std::string& path, const std::string& format, int part, int nparts,
-              size_t batch_size, size_t shuf_buf, float neg_sampling, int nthreads = 8);
+              size_t batch_size, size_t shuf_buf, float neg_sampling, int nthreads = 8,
+              size_t chunk_bytes = 64 << 20);
   bool Next();
   const RowBlockContainer<feaid_t>& Value() const { return batch_; }
   /** exchange the current batch with *c (hands the batch over, takes c's buffers) */
@@ -162,6 +181,60 @@ class BatchReader {
   std::vector<size_t> order_;
   size_t start_ = 0;
   RowBlockContainer<feaid_t> batch_;
+};
+
+/** one row copy of a batch plan: rows of a parsed chunk or of the shuffle buffer appended to
+ * the shuffle buffer or to the batch being formed (GatherRows's arguments) */
+struct GatherOp {
+  enum { kShuffle = -1 };
+  int src = 0;            // the chunk's sequence number (0, 1, ...) or kShuffle
+  bool to_batch = true;   // destination: the batch being formed, else the shuffle buffer
+  size_t begin = 0, n = 0;  // rows.empty(): the range [begin, begin + n) of src
+  size_t r0 = 0;            // the destination's row count before the copy
+  std::vector<uint32_t> rows;  // else the list rows[0..n)
+};
+
+/** The batches BatchReader forms, planned from row lengths and labels alone (no ids are
+ * touched, no HIP): the copies are handed to `emit` in order, for a device (DeviceBatchReader)
+ * or the host (GatherRows) to carry out.  It mirrors BatchReader::Refill / Next statement by
+ * statement — the shuf_buf-row shuffle buffer filled across chunks, std::shuffle with the
+ * persistent std::mt19937{0}, the rand_r down-sampling consuming labels in the same order
+ * with the same seed, batches straddling chunks, the short last batch — so for the same
+ * chunks it plans exactly BatchReader's batches. */
+class BatchPlanner {
+ public:
+  /** the next parsed chunk: its row count, offsets (rows + 1) and labels, valid until the
+   * next call; false at the end of the part.  After the call no later copy reads the chunk
+   * before it. */
+  using ChunkFn = std::function<bool(size_t* rows, const uint64_t** offset, const float** label)>;
+  using EmitFn = std::function<void(const GatherOp&)>;
+  BatchPlanner(size_t batch_size, size_t shuf_buf, float neg_sampling, ChunkFn next_chunk,
+               EmitFn emit);
+  /** plans (and emits the copies of) the next batch; false when no rows are left */
+  bool Next(size_t* rows, size_t* nnz);
+
+ private:
+  bool Refill();
+  bool NextChunk();
+  size_t Len(size_t j) const;
+  size_t batch_size_, shuf_buf_;
+  float neg_sampling_;
+  ChunkFn next_chunk_;
+  EmitFn emit_;
+  unsigned seed_ = 0;
+  std::mt19937 shuffle_rng_{0};
+  int chunk_seq_ = -1;  // the current chunk's sequence number
+  bool done_ = false;
+  size_t chunk_rows_ = 0, pend_pos_ = 0;
+  const uint64_t* chunk_off_ = nullptr;
+  const float* chunk_lab_ = nullptr;
+  bool src_shuffle_ = false, have_src_ = false;  // rows being batched: shuffle buffer or chunk
+  std::vector<uint32_t> in_len_;                 // the shuffle buffer's row lengths and labels
+  std::vector<float> in_lab_;
+  std::vector<size_t> order_;
+  size_t start_ = 0;
+  std::vector<uint32_t> sel_;
+  size_t batch_rows_ = 0, batch_nnz_ = 0;
 };
 
 /** a BatchReader on its own thread, `depth` batches ahead: the producer half of

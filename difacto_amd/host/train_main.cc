@@ -5,7 +5,15 @@
 //                   [batch_size=100] [shuffle=10] [neg_sampling=1] [max_num_epochs=20]
 //                   [num_jobs_per_epoch=10] [stop_rel_objv=1e-5] [model_in=F] [model_out=F]
 //                   [load_epoch=-1] [has_aux=0] [task=0|2] [pred_out=F] [pred_prob=1]
-//                   [fused=1] [nthreads=8] [V_dim=..] [lr=..] [l1=..] ...  (SGDUpdaterParam)
+//                   [fused=1] [nthreads=8] [parse=host|device] [V_dim=..] [lr=..] [l1=..] ...
+//                   (SGDUpdaterParam)
+//
+// parse=device (data_format=criteo|criteo_test, the single-GPU fused path: training, data_val
+// validation and task=2 prediction): the raw text is copied to pinned memory and uploaded, the
+// device parses it (dfx_parse_criteo) and forms the batches (DeviceBatchReader,
+// device_reader.h) — the same batches, so the same results, as the default parse=host.  With
+// any other format, fused=0 or the sharded runs it is an error (exit 2).  A chunk the device
+// hands back (needs_host) is parsed by the host; their count is printed per epoch if non-zero.
 //
 // Sharded store (KVStoreDist over GPUs, dist_host.h): `shards=N` holds N shards on this GPU
 // (loopback exchange, for tests); `shards=-1` or a launch with WORLD_SIZE > 1 (RANK / LOCAL_RANK as
@@ -36,6 +44,7 @@
 #include <vector>
 #include <string>
 
+#include "device_reader.h"
 #include "dist_host.h"
 #include "gpu_adapters.h"
 #include "reader.h"
@@ -56,6 +65,7 @@ struct Param {
   std::string exchange = "a2a";  // a2a: GpuShardedStore (KVStoreDist); split: GpuSplitLearner
   bool has_aux = false, pred_prob = true;
   double stop_rel_objv = 1e-5;
+  std::string parse = "host";  // device: DeviceBatchReader (criteo text parsed on the GPU)
 };
 
 // sgd_learner.h:65-69
@@ -82,13 +92,41 @@ std::string Text(const Progress& p) {
 }
 
 Progress RunEpoch(GpuSGDLearner* learner, const Param& P, int epoch, int job_type,
-                  FILE* pred_file = nullptr) {
+                  FILE* pred_file = nullptr, DeviceTextFeed* feed = nullptr,
+                  DeviceBatchReader::Times* times = nullptr, double* step_s = nullptr) {
   Progress prog;
   std::vector<real_t> pred;
   const bool train = job_type == GpuSGDLearner::kTraining;
   const std::string& path = train ? P.data_in : P.data_val;
+  size_t fallback = 0;
   for (int part = 0; part < P.num_jobs_per_epoch; ++part) {
-    if (train) {
+    if (feed) {
+      // parse=device: the same parts, chunks and batches, formed on the device
+      DeviceBatchReader reader(feed, path, P.data_format, part, P.num_jobs_per_epoch,
+                               train ? P.batch_size : 0, train ? P.batch_size * P.shuffle : 0,
+                               train ? P.neg_sampling : 1.f, P.nthreads,
+                               train ? (size_t)64 << 20 : (size_t)256 << 20);
+      while (reader.Next()) {
+        const dfx_batch& b = reader.Value();
+        const double ts = Now();
+        learner->ProcessDeviceBatch(b, job_type, train && epoch == 0,
+                                    pred_file ? &pred : nullptr);
+        reader.Consumed();
+        if (step_s) step_s[0] += Now() - ts;
+        const float* label = reader.HostLabels();
+        for (size_t i = 0; pred_file && i < pred.size(); ++i)  // SavePred
+          std::fprintf(pred_file, "%g\t%g\n", label[i],
+                       P.pred_prob ? 1.0 / (1.0 + std::exp(-pred[i])) : (double)pred[i]);
+      }
+      fallback += reader.FallbackChunks();
+      if (times) {
+        const DeviceBatchReader::Times t = reader.TimesSpent();
+        times->copy += t.copy;
+        times->wait_text += t.wait_text;
+        times->wait_parse += t.wait_parse;
+        times->wait_step += t.wait_step;
+      }
+    } else if (train) {
       // sgd_learner.cc:273-280
       ThreadedBatchReader reader(path, P.data_format, part, P.num_jobs_per_epoch, P.batch_size,
                                  P.batch_size * P.shuffle, P.neg_sampling, P.nthreads);
@@ -108,11 +146,16 @@ Progress RunEpoch(GpuSGDLearner* learner, const Param& P, int epoch, int job_typ
                        P.pred_prob ? 1.0 / (1.0 + std::exp(-pred[i])) : (double)pred[i]);
       }
     }
+    const double tj = Now();
     const Progress p = learner->TakeProgress();
+    if (step_s) step_s[1] += Now() - tj;
     prog.nrows += p.nrows;
     prog.loss += p.loss;
     prog.auc += p.auc;
   }
+  if (fallback)
+    std::printf("parse=device: %zu chunk%s parsed by the host (needs_host)\n", fallback,
+                fallback == 1 ? "" : "s");
   return prog;
 }
 // ---- the sharded store ----------------------------------------------------------------------
@@ -401,6 +444,7 @@ int main(int argc, char** argv) {
     else if (k == "pipelined") P.pipelined = std::stoi(v) != 0;
     else if (k == "exchange") P.exchange = v;
     else if (k == "model_in_parts") P.model_in_parts = std::stoi(v);
+    else if (k == "parse") P.parse = v;
     else {
       fused_given = fused_given || k == "fused";
       rest.push_back({k, v});
@@ -411,9 +455,33 @@ int main(int argc, char** argv) {
     return 2;
   }
   const char* ws = std::getenv("WORLD_SIZE");
-  if (P.shards != 0 || (ws && std::atoi(ws) > 1)) return RunSharded(P, rest);
+  const bool sharded = P.shards != 0 || (ws && std::atoi(ws) > 1);
+  if (P.parse != "host" && P.parse != "device") {
+    std::fprintf(stderr, "parse must be host or device\n");
+    return 2;
+  }
+  if (P.parse == "device") {  // no silent fall-back to the host reader
+    bool fused = true;
+    for (const auto& kv : rest)
+      if (kv.first == "fused") fused = std::stoi(kv.second) != 0;
+    const char* why = nullptr;
+    if (P.data_format != "criteo" && P.data_format != "criteo_test")
+      why = "data_format=criteo or criteo_test";
+    else if (!fused)
+      why = "the fused path (fused=1)";
+    else if (sharded)
+      why = "the single-GPU run (shards=0)";
+    if (why) {
+      std::fprintf(stderr, "parse=device needs %s\n", why);
+      return 2;
+    }
+  }
+  if (sharded) return RunSharded(P, rest);
   if (!fused_given) rest.push_back({"fused", "1"});
   GpuSGDLearner learner(rest);
+  std::unique_ptr<DeviceTextFeed> feed;
+  if (P.parse == "device")
+    feed.reset(new DeviceTextFeed(learner.context(), P.batch_size, P.batch_size * P.shuffle));
   int k0 = 0;
   if (!P.model_in.empty()) {  // sgd_learner.cc:58-67
     FileStream fi(ModelName(P.model_in, P.load_epoch > 0 ? P.load_epoch : -1).c_str(), "rb");
@@ -433,7 +501,7 @@ int main(int argc, char** argv) {
         return 1;
       }
     }
-    const Progress pr = RunEpoch(&learner, P, k0, GpuSGDLearner::kPrediction, pf);
+    const Progress pr = RunEpoch(&learner, P, k0, GpuSGDLearner::kPrediction, pf, feed.get());
     if (pf) std::fclose(pf);
     std::printf("Prediction: %s\n", Text(pr).c_str());
     return 0;
@@ -442,13 +510,21 @@ int main(int argc, char** argv) {
   double pre_loss = 0, pre_val_auc = 0;  // sgd_learner.cc:52
   for (int k = k0; k < P.max_num_epochs; ++k) {
     const double te = Now();
-    const Progress tr = RunEpoch(&learner, P, k, GpuSGDLearner::kTraining);
+    DeviceBatchReader::Times rt;
+    double step_s[2] = {0, 0};  // inside dfx_train_step calls; the epoch's final join
+    const Progress tr =
+        RunEpoch(&learner, P, k, GpuSGDLearner::kTraining, nullptr, feed.get(), &rt, step_s);
     const double dt = Now() - te;
     std::printf("Epoch[%d] Training: %s  (%.0f ex/s incl. parse+PCIe, %.2f s)\n", k,
                 Text(tr).c_str(), tr.nrows / dt, Now() - t0);
+    if (feed)  // where the device reader's time went (device_reader.h Times)
+      std::printf("  reader: epoch %.3f s, host copy %.3f s (loader thread); caller waited for "
+                  "text %.3f s, for the parse %.3f s, for a ring batch %.3f s, in dfx_train_step "
+                  "%.3f s, in the final join %.3f s\n",
+                  dt, rt.copy, rt.wait_text, rt.wait_parse, rt.wait_step, step_s[0], step_s[1]);
     Progress va;
     if (!P.data_val.empty()) {
-      va = RunEpoch(&learner, P, k, GpuSGDLearner::kValidation);
+      va = RunEpoch(&learner, P, k, GpuSGDLearner::kValidation, nullptr, feed.get());
       std::printf("Epoch[%d] Validation: %s\n", k, Text(va).c_str());
     }
     std::fflush(stdout);

@@ -257,6 +257,31 @@ def train_step(ctx, dblk, job_type=kTraining, push_cnt=False, max_index=MAX_INDE
                                     ctypes.c_uint64(max_index), _p(pred)))
 
 
+def parse_criteo(ctx, data, is_train=True):
+    """Criteo text (whole lines, bytes) parsed on the device (dfx_parse_criteo, replacing
+    criteo_parser.h:40-92) -> (RowBlock, needs_host).  needs_host: the chunk holds a form the
+    device leaves to the host parser (include/difacto_amd.h lists them); the block is then
+    None.  is_train=False is criteo_test (no label column)."""
+    from .data import RowBlock
+    data = bytes(data)
+    max_rows = data.count(b"\n") + 1
+    max_nnz = 39 * max_rows
+    dev = ctx.device
+    text = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev) if data else None
+    offs = torch.empty(max_rows + 1, dtype=torch.int64, device=dev)
+    ids = torch.empty(max_nnz, dtype=torch.int64, device=dev)
+    labels = torch.empty(max_rows, dtype=torch.float32, device=dev)
+    stat_dev = torch.empty(4, dtype=torch.int64, device=dev)
+    check(_lib.lib().dfx_parse_criteo(ctx.h, _p(text), len(data), int(bool(is_train)), max_rows,
+                                      max_nnz, _p(offs), _p(ids), _p(labels), _p(stat_dev)))
+    stat = (ctypes.c_int64 * 4)()
+    check(_lib.lib().dfx_parse_criteo_wait(ctx.h, _p(stat_dev), stat))
+    rows, nnz, needs_host = stat[0], stat[1], bool(stat[2])
+    if needs_host:
+        return None, True
+    return RowBlock(u64(offs[:rows + 1]), u64(ids[:nnz]), None, labels[:rows].cpu().numpy()), False
+
+
 # main-stream phases of dfx_train_step (the Localizer runs on its own lane; "localize" is
 # the part of it the main stream waits for)
 PHASES = ("localize", "probe_pull", "feacnt", "forward", "eval_auc", "backward_update", "initv")

@@ -150,6 +150,70 @@ int dfx_feeder_create_slots(dfx_ctx* ctx, int64_t max_rows, int64_t max_nnz, int
                             dfx_feeder** out);
 int dfx_feeder_consumed_back(dfx_feeder* f, int back);
 
+/* ---- Criteo text on the device (difacto_amd/csrc/textparse.hip) --------------------------
+ * dfx_parse_criteo replaces CriteoParser::ParseBlock (src/reader/criteo_parser.h:40-92) for a
+ * chunk of whole lines text_dev[0, nbytes) in device memory: offset[rows + 1] (offset[0] == 0),
+ * index[nnz] = (CityHash64(cell) << 12) | column for every non-empty cell of the first 39
+ * feature columns, label[rows]; is_train == 0 is criteo_test (no label column, labels 0).
+ * The result equals the host reader's ParseCriteo (difacto_amd/host/reader.cc) byte for byte,
+ * or the chunk is flagged: stat_dev[4] (device) = {rows, nnz, needs_host, overflow}.
+ * needs_host == 1: the outputs are undefined and the host parses the chunk.  Only these forms
+ * may raise it: a label cell that is not [+-]?[0-9]{1,9} filling the cell (an empty one too),
+ * a '\r' byte anywhere, an empty line, a last byte that is not '\n'.
+ * overflow == 1: the chunk needs more than max_rows rows or max_nnz ids; rows / nnz then hold
+ * the needed counts (with more than 2 * max_rows + 1 lines: the upper bounds lines and
+ * 39 * lines) and nothing was written.  No byte outside the text is read, nothing past the
+ * capacities is written.  nbytes >= 2^31 is DFX_ERR_ARG (positions are 32-bit).
+ * dfx_gather_rows replaces the row copies of BatchReader (src/reader/batch_reader.cc:29-78;
+ * the host reader's GatherRows): rows rows_dev[0..n) of a source CSR (rows_dev NULL: rows
+ * [begin, begin + n)) appended to a destination CSR at row r0, offsets rebased onto
+ * dst_offset[r0] (0 when r0 == 0), labels copied; the caller sizes the destination.
+ * Both are asynchronous on the context's input stream (dfx_ctx_set_input_stream; none: the
+ * context stream), beside the step like the feeder's copies.  dfx_parse_criteo_wait joins that
+ * stream, copies the four counts to stat (host) and returns DFX_ERR_CAPACITY on overflow. */
+int dfx_parse_criteo(dfx_ctx* ctx, const char* text_dev, int64_t nbytes, int is_train,
+                     int64_t max_rows, int64_t max_nnz, uint64_t* offset, uint64_t* index,
+                     float* label, int64_t* stat_dev);
+int dfx_parse_criteo_wait(dfx_ctx* ctx, const int64_t* stat_dev, int64_t* stat);
+int dfx_gather_rows(dfx_ctx* ctx, const uint64_t* src_offset, const uint64_t* src_index,
+                    const float* src_label, const uint32_t* rows_dev, int64_t begin, int64_t n,
+                    uint64_t* dst_offset, uint64_t* dst_index, float* dst_label, int64_t r0);
+
+/* The text feeder: raw text to device batches (src/reader/reader.h:18-55 + batch_reader.cc
+ * with the parsing and the row copies on the device).  nslots pinned text slots, a loader
+ * stream that becomes the context's input stream, one parsed chunk (device CSR + pinned
+ * copies of its offsets and labels) per slot, a shuffle buffer of shuf_rows rows and a ring
+ * of nring device batches of batch_rows rows (39 ids a row at most: rows size everything).
+ *   dfx_textfeed_text      the slot's pinned text buffer, at least `bytes` long; fill it
+ *   dfx_textfeed_submit    upload + dfx_parse_criteo + the copies back, asynchronous
+ *   dfx_textfeed_wait      join: stat[4] as dfx_parse_criteo_wait, the pinned offsets / labels
+ *   dfx_textfeed_upload    a chunk the host parsed (needs_host) into the slot's arrays
+ *   dfx_textfeed_batch_begin / _gather / _batch_end   form the next ring batch: gathers from
+ *                          a slot's chunk (src >= 0) or the shuffle buffer (src == -1) into
+ *                          the batch (to_batch) or the shuffle buffer, rows a HOST list or
+ *                          NULL for the range [begin, begin + n), appended at row r0
+ *   dfx_textfeed_consumed  after dfx_train_step(*out): the ring entry is in use until then
+ *   dfx_textfeed_slot_batch / _slot_consumed   a slot's whole chunk as one batch (validation
+ *                          reads 256 MB chunks as batches, sgd_learner.cc:281-286) */
+typedef struct dfx_textfeed dfx_textfeed;
+int dfx_textfeed_create(dfx_ctx* ctx, int nslots, int nring, int64_t batch_rows,
+                        int64_t shuf_rows, dfx_textfeed** out);
+int dfx_textfeed_destroy(dfx_textfeed* f);
+int dfx_textfeed_text(dfx_textfeed* f, int slot, int64_t bytes, char** pinned);
+int dfx_textfeed_submit(dfx_textfeed* f, int slot, int64_t nbytes, int is_train,
+                        int64_t max_rows);
+int dfx_textfeed_wait(dfx_textfeed* f, int slot, int64_t* stat, const uint64_t** offset_host,
+                      const float** label_host);
+int dfx_textfeed_upload(dfx_textfeed* f, int slot, int64_t rows, int64_t nnz,
+                        const uint64_t* offset, const uint64_t* index, const float* label);
+int dfx_textfeed_batch_begin(dfx_textfeed* f);
+int dfx_textfeed_gather(dfx_textfeed* f, int src, int to_batch, const uint32_t* rows,
+                        int64_t begin, int64_t n, int64_t r0);
+int dfx_textfeed_batch_end(dfx_textfeed* f, int64_t rows, int64_t nnz, dfx_batch* out);
+int dfx_textfeed_consumed(dfx_textfeed* f);
+int dfx_textfeed_slot_batch(dfx_textfeed* f, int slot, dfx_batch* out);
+int dfx_textfeed_slot_consumed(dfx_textfeed* f, int slot);
+
 /* ---- Localizer::Compact (localizer.h:41-51) -------------------------------------------
  * keys = ReverseBytes(index % max_index); uniq[U] ascending, cnt[U] occurrence counts
  * (float, may be NULL), col[nnz] = rank of each nnz's key (the u32 CSR index).  Offsets,
