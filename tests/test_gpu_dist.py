@@ -11,6 +11,7 @@ import torch
 from difacto_amd import data as D
 from oracle import dist_oracle as DO
 from oracle import oracle as O
+from tests import metric_exact as M
 
 pytestmark = pytest.mark.gpu
 
@@ -109,6 +110,10 @@ def test_sharded_loopback_matches_sharded_oracle(name, agg):
             want_auc = (O.auc_stable_ties(step[r].labels, out[r][2])
                         if O.has_ties(out[r][2]) else out[r][1])
             assert pr["auc"] == pytest.approx(want_auc, rel=1e-4, abs=1e-6)
+            # the worker's own predictions: AUC * n exactly, the loss to double rounding
+            assert pr["auc"] == M.auc_times_n(step[r].labels, p), (name, s, r)
+            S, tol = M.logloss_sum(step[r].labels, p)
+            assert abs(pr["loss"] - S) <= tol, (name, s, r, pr["loss"], S, tol)
     keys = np.unique(np.concatenate([O.localize(b.offs, b.ids)[0]
                                      for step in batches for b in step]))
     n_v = _check_servers(name, ctxs, so, keys, N, agg)

@@ -13,6 +13,7 @@ import torch
 
 from difacto_amd import data as D
 from oracle import oracle as O
+from tests import metric_exact as M
 
 pytestmark = pytest.mark.gpu
 
@@ -98,6 +99,11 @@ def _run(H, cfg, batches, n_cnt, max_keys, pred_rtol, model_rtol, check_model=Tr
         assert abs(p["loss"] - loss) <= 1e-4 * abs(loss), (step, p["loss"], loss)
         assert abs(p["auc"] - _auc_expect(blk.labels, opred, auc)) <= 1e-4 * blk.size, step
         assert p["nrows"] == blk.size
+        # against the device's own predictions: AUC * n exactly, the loss to double rounding
+        got = pred.cpu().numpy()
+        assert p["auc"] == M.auc_times_n(blk.labels, got), step
+        S, tol = M.logloss_sum(blk.labels, got)
+        assert abs(p["loss"] - S) <= tol, (step, p["loss"], S, tol)
         if ex is not None:
             ex.train_step(blk.offs, blk.ids, blk.vals, blk.labels, push_cnt=push)
             uniq, _, _ = O.localize(blk.offs, blk.ids)

@@ -1,13 +1,18 @@
 """Parity of the HIP path (through the C-ABI) with the oracle and the reference's known
 answers.  Bars (BASELINE.json north_star): Localizer bit-exact; predictions and gradients
-within 1e-5 relative (fp32); loss / AUC within 1e-4.  Predictions are also checked for
-bit-exactness, which the kernels achieve by summing in the reference's order."""
+within 1e-5 relative (fp32); loss / AUC within 1e-4 of the reference, whose own sums run in
+float.  Against its own float64 restatement (tests/metric_exact.py) the device is held much
+tighter: AUC * n exactly and the logloss within double rounding (here in
+test_auc_and_evaluate and test_auc_radix_and_merge_sorts_agree, on every path in
+test_gpu_metric_exact.py).  Predictions are also checked for bit-exactness, which the kernels
+achieve by summing in the reference's order."""
 import numpy as np
 import pytest
 import torch
 
 from difacto_amd import data as D
 from oracle import oracle as O
+from tests import metric_exact as M
 
 pytestmark = pytest.mark.gpu
 
@@ -210,17 +215,26 @@ def test_auc_and_evaluate(H):
     tl, tp = c.tensor(label, torch.float32), c.tensor(pred, torch.float32)
     a = H.auc(c, tl, tp)
     assert abs(a - O.auc(label, pred)) <= 1e-4 * n
-    assert abs(H.FMLoss(c, 0).evaluate(tl, tp) - O.evaluate(label, pred)) <= 1e-6 * n
+    assert a == M.auc_times_n(label, pred)  # the device's own arithmetic: exact
+    ev = H.FMLoss(c, 0).evaluate(tl, tp)
+    assert abs(ev - O.evaluate(label, pred)) <= 1e-6 * n
+    S, tol = M.logloss_sum(label, pred)
+    assert abs(ev - S) <= tol, (ev, S, tol)
+    # all predictions equal: one run of ties kept in input order
+    ones = np.ones(n, np.float32)
+    assert H.auc(c, tl, c.tensor(ones, torch.float32)) == M.auc_times_n(label, ones)
     # degenerate batch: the reference returns 1 (not 1*n)
-    assert H.auc(c, tl, c.tensor(np.ones(n, np.float32), torch.float32)) > 0
     assert H.auc(c, c.tensor(np.ones(n, np.float32), torch.float32), tp) == 1.0
 
 
-@pytest.mark.parametrize("n", [1, 2, 4095, 4097, 10000, 12288, 12289, 100000, 1000003])
+@pytest.mark.parametrize("n", [1, 2, 4095, 4097, 10000, 12288, 12289, 100000, 4096 * 240,
+                               1000003])
 def test_auc_radix_and_merge_sorts_agree(H, n):
     """the AUC lane's two stable sorts (auc_sort=radix | merge; up to 12288 rows both take the
-    one-block LDS sort, k_auc_block): the same AUC*n, equal to the input-order tie break of the
-    oracle, with heavy ties (quantised predictions, one constant digit pattern), with all
+    one-block LDS sort, k_auc_block; above 4096 * 240 rows — kMaxMergeRuns runs — merge mode
+    takes the radix sort too, so at 1,000,003 both contexts run the radix sort and 4096 * 240
+    is the largest size at which the two sorts differ): the same AUC*n, equal to the
+    input-order tie break of the oracle and, exactly, to tests/metric_exact.py, with heavy ties (quantised predictions, one constant digit pattern), with all
     predictions equal (epoch 0, w = 0) and with signed zeros (-0 == +0).  Each context sees every
     snapshot twice"""
     rng = np.random.default_rng(n)
@@ -232,11 +246,13 @@ def test_auc_radix_and_merge_sorts_agree(H, n):
                  np.zeros(n, np.float32), (rng.standard_normal(n) - 0.3 * label).astype(np.float32),
                  signed0]:
         want = O.auc_stable_ties(label, pred) if O.has_ties(pred) else O.auc(label, pred)
+        exact = M.auc_times_n(label, pred)
         for _ in range(2):
             got = [H.auc(c, c.tensor(label, torch.float32), c.tensor(pred, torch.float32))
                    for c in cs]
             assert got[0] == got[1], got
             assert abs(got[0] - want) <= 1e-4 * n, (got, want)
+            assert got[0] == exact, (got, exact)
     for c in cs:
         c.close()
 

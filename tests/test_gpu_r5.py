@@ -14,6 +14,7 @@ import torch
 
 from difacto_amd import data as D
 from oracle import oracle as O
+from tests import metric_exact as M
 
 pytestmark = pytest.mark.gpu
 
@@ -72,6 +73,10 @@ def test_walk_forward_bit_identical(H, rows, d, binary):
         assert abs(qa["loss"] - qb["loss"]) <= 1e-12 * abs(qa["loss"]) and qa["auc"] == qb["auc"]
         assert abs(qb["loss"] - loss) <= 1e-4 * abs(loss)
         assert abs(qb["auc"] - _auc_expect(blk.labels, opred, auc)) <= 1e-4 * blk.size
+        # against the device's own predictions: AUC * n exactly, the loss to double rounding
+        assert qa["auc"] == M.auc_times_n(blk.labels, got)
+        S, tol = M.logloss_sum(blk.labels, got)
+        assert abs(qa["loss"] - S) <= tol and abs(qb["loss"] - S) <= tol, (qa, qb, S, tol)
     uniq, _, _ = O.localize(blk.offs, blk.ids)
     va, la = H.Store(ca).pull(ca.tensor(uniq, torch.int64))
     vb, lb = H.Store(cb).pull(cb.tensor(uniq, torch.int64))

@@ -11,6 +11,7 @@ import torch
 from difacto_amd import data as D
 from oracle import dist_oracle as DO
 from oracle import oracle as O
+from tests import metric_exact as M
 
 pytestmark = pytest.mark.gpu
 
@@ -72,6 +73,10 @@ def _run(N, kw, steps, rows=400, nnz=12, key_space=6000, jobs=None, empty=(), pu
                 want_auc = (O.auc_stable_ties(step[r].labels, p) if O.has_ties(p)
                             else O.auc(step[r].labels, p))
                 assert pr["auc"] == pytest.approx(want_auc, rel=1e-4, abs=1e-6), (N, s, r)
+                # the worker's own predictions: AUC * n exactly, the loss to double rounding
+                assert pr["auc"] == M.auc_times_n(step[r].labels, p), (N, s, r)
+                S, tol = M.logloss_sum(step[r].labels, p)
+                assert abs(pr["loss"] - S) <= tol, (N, s, r, pr["loss"], S, tol)
             b0 += B
         assert got == pytest.approx(loss, rel=1e-5), (N, s)
         seen.append(cat)
