@@ -112,6 +112,15 @@ _SIGS = {
     "dfx_textfeed_consumed": (ctypes.c_int, [vp]),
     "dfx_textfeed_slot_batch": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(Batch)]),
     "dfx_textfeed_slot_consumed": (ctypes.c_int, [vp, ctypes.c_int]),
+    "dfx_batchcache_create": (ctypes.c_int, [vp, c_i64, c_i64, ctypes.POINTER(vp)]),
+    "dfx_batchcache_destroy": (ctypes.c_int, [vp]),
+    "dfx_batchcache_begin": (ctypes.c_int, [vp, c_i64]),
+    "dfx_batchcache_append": (ctypes.c_int, [vp, ctypes.POINTER(Batch),
+                                             ctypes.POINTER(ctypes.c_int)]),
+    "dfx_batchcache_seal": (ctypes.c_int, [vp, i64p]),
+    "dfx_batchcache_count": (ctypes.c_int, [vp, c_i64, i64p]),
+    "dfx_batchcache_get": (ctypes.c_int, [vp, c_i64, c_i64, ctypes.POINTER(Batch)]),
+    "dfx_batchcache_stats": (ctypes.c_int, [vp, i64p]),
     "dfx_dist_record_floats": (ctypes.c_int, [vp]),
     "dfx_dist_localize": (ctypes.c_int, [vp, ctypes.POINTER(Batch), c_u64, ctypes.c_int,
                                          ctypes.c_int, vp, vp]),

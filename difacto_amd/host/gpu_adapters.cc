@@ -425,7 +425,8 @@ GpuSGDLearner::~GpuSGDLearner() {
 }
 
 void GpuSGDLearner::ProcessBatch(const dmlc::RowBlock<feaid_t>& batch, int job_type,
-                                 bool push_cnt, std::vector<real_t>* pred_out) {
+                                 bool push_cnt, std::vector<real_t>* pred_out,
+                                 dfx_batch* dev_batch) {
   push_cnt = push_cnt && job_type == kTraining && V_dim_ > 0;
   if (fused_) {
     const int64_t B = (int64_t)batch.size, nnz = B ? (int64_t)batch.offset[B] : 0;
@@ -451,6 +452,7 @@ void GpuSGDLearner::ProcessBatch(const dmlc::RowBlock<feaid_t>& batch, int job_t
     DfxCheck(dfx_feeder_submit(feeder_, B, nnz, batch.value != nullptr, batch.weight != nullptr,
                                &b),
              "dfx_feeder_submit");
+    if (dev_batch) *dev_batch = b;
     float* dp = nullptr;
     if (pred_out) {
       if (!dpred_) dpred_.reset(new DevArray<float>(c));
@@ -536,6 +538,54 @@ Progress GpuSGDLearner::TakeProgress() {
     out.loss += p.loss;
     out.auc += p.auc;
   }
+  return out;
+}
+
+// ---- device batch cache --------------------------------------------------------------------
+DeviceBatchCache::DeviceBatchCache(dfx_ctx* ctx, int64_t budget_bytes, int64_t block_bytes) {
+  DfxCheck(dfx_batchcache_create(ctx, budget_bytes, block_bytes, &h_), "dfx_batchcache_create");
+}
+
+DeviceBatchCache::~DeviceBatchCache() {
+  if (h_) dfx_batchcache_destroy(h_);
+}
+
+void DeviceBatchCache::Begin(int64_t list) {
+  DfxCheck(dfx_batchcache_begin(h_, list), "dfx_batchcache_begin");
+}
+
+bool DeviceBatchCache::Append(const dfx_batch& b) {
+  int kept = 0;
+  DfxCheck(dfx_batchcache_append(h_, &b, &kept), "dfx_batchcache_append");
+  return kept != 0;
+}
+
+int64_t DeviceBatchCache::Seal() {
+  int64_t n = 0;
+  DfxCheck(dfx_batchcache_seal(h_, &n), "dfx_batchcache_seal");
+  return n;
+}
+
+int64_t DeviceBatchCache::Count(int64_t list) const {
+  int64_t n = 0;
+  DfxCheck(dfx_batchcache_count(h_, list, &n), "dfx_batchcache_count");
+  return n;
+}
+
+dfx_batch DeviceBatchCache::Get(int64_t list, int64_t i) const {
+  dfx_batch b;
+  DfxCheck(dfx_batchcache_get(h_, list, i, &b), "dfx_batchcache_get");
+  return b;
+}
+
+DeviceBatchCache::Stats DeviceBatchCache::GetStats() const {
+  int64_t s[4] = {0, 0, 0, 0};
+  DfxCheck(dfx_batchcache_stats(h_, s), "dfx_batchcache_stats");
+  Stats out;
+  out.sealed = s[0];
+  out.dropped = s[1];
+  out.batches = s[2];
+  out.bytes = s[3];
   return out;
 }
 

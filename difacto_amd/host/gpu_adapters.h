@@ -178,9 +178,13 @@ class GpuSGDLearner {
   /** one minibatch of raw feature ids; push_cnt = epoch 0 of training with V_dim > 0.
    * Asynchronous on the fused path: the batch is copied into pinned staging and uploaded on
    * the feeder's loader stream; the step runs behind the previous one.  pred (optional):
-   * receives the batch's predictions (joins the device), as SavePred writes them. */
+   * receives the batch's predictions (joins the device), as SavePred writes them.
+   * dev_batch (optional, fused path): receives the device batch the feeder uploaded; its
+   * buffers are the feeder's, reused by the upload after next, and anything queued on the
+   * context's input stream before the next ProcessBatch (a DeviceBatchCache's copies) reads
+   * them complete. */
   void ProcessBatch(const dmlc::RowBlock<feaid_t>& batch, int job_type, bool push_cnt,
-                    std::vector<real_t>* pred = nullptr);
+                    std::vector<real_t>* pred = nullptr, dfx_batch* dev_batch = nullptr);
   /** the fused path for a batch already on the device (DeviceBatchReader, device_reader.h):
    * dfx_train_step without the pinned copy; the batch's producer is the context's input
    * stream.  pred (optional) receives the predictions (joins the device). */
@@ -205,6 +209,31 @@ class GpuSGDLearner {
   int64_t feed_rows_ = 0, feed_nnz_ = 0;
   std::unique_ptr<DevArray<float>> dpred_;
   Progress prog_;
+};
+
+/** the device batch cache (dfx_batchcache_*, include/difacto_amd.h) of one context: lists of
+ * formed batches recorded in the first epoch a run executes and replayed in the later ones */
+class DeviceBatchCache {
+ public:
+  DeviceBatchCache(dfx_ctx* ctx, int64_t budget_bytes, int64_t block_bytes = 0);
+  ~DeviceBatchCache();
+  DeviceBatchCache(const DeviceBatchCache&) = delete;
+  DeviceBatchCache& operator=(const DeviceBatchCache&) = delete;
+  void Begin(int64_t list);
+  /** a copy of b into the open list; false: the list did not fit and was dropped */
+  bool Append(const dfx_batch& b);
+  /** closes the open list -> its batch count, -1 if it was dropped */
+  int64_t Seal();
+  /** a sealed list's batch count; -1 dropped, -2 never begun */
+  int64_t Count(int64_t list) const;
+  dfx_batch Get(int64_t list, int64_t i) const;
+  struct Stats {
+    int64_t sealed = 0, dropped = 0, batches = 0, bytes = 0;
+  };
+  Stats GetStats() const;
+
+ private:
+  dfx_batchcache* h_ = nullptr;
 };
 
 /** a libsvm reader ("label idx:val ..."): the thin CSR producer the path's caller uses */

@@ -5,8 +5,8 @@
 //                   [batch_size=100] [shuffle=10] [neg_sampling=1] [max_num_epochs=20]
 //                   [num_jobs_per_epoch=10] [stop_rel_objv=1e-5] [model_in=F] [model_out=F]
 //                   [load_epoch=-1] [has_aux=0] [task=0|2] [pred_out=F] [pred_prob=1]
-//                   [fused=1] [nthreads=8] [parse=host|device] [V_dim=..] [lr=..] [l1=..] ...
-//                   (SGDUpdaterParam)
+//                   [fused=1] [nthreads=8] [parse=host|device] [cache=none|device]
+//                   [cache_mb=16384] [V_dim=..] [lr=..] [l1=..] ...  (SGDUpdaterParam)
 //
 // parse=device (data_format=criteo|criteo_test, the single-GPU fused path: training, data_val
 // validation and task=2 prediction): the raw text is copied to pinned memory and uploaded, the
@@ -14,6 +14,18 @@
 // device_reader.h) — the same batches, so the same results, as the default parse=host.  With
 // any other format, fused=0 or the sharded runs it is an error (exit 2).  A chunk the device
 // hands back (needs_host) is parsed by the host; their count is printed per epoch if non-zero.
+//
+// cache=device (the single-GPU fused path with either parse and any data_format, training and
+// data_val validation; the sharded exchange=a2a runs): the first epoch the run executes (after
+// load_epoch: not epoch 0) also copies every batch it forms into a device batch cache
+// (DeviceBatchCache, gpu_adapters.h; dfx_batchcache_*), one list per job kind and part, within
+// cache_mb MB (per shard in a sharded run).  A reader lives for one part of one epoch and seeds
+// its shuffle and down-sampling afresh, so a part yields the same batches in every epoch: every
+// later epoch steps through the cached batches with no reader, no upload and no parse, and
+// computes the same losses and model.  A part whose batches did not fit is read as without the
+// cache.  After the recording epoch one line reports the batches and MB held and the parts not
+// cached.  With exchange=split or fused=0 it is an error (exit 2); task=2 is one pass over the
+// data, so there it is accepted and has no effect.
 //
 // Sharded store (KVStoreDist over GPUs, dist_host.h): `shards=N` holds N shards on this GPU
 // (loopback exchange, for tests); `shards=-1` or a launch with WORLD_SIZE > 1 (RANK / LOCAL_RANK as
@@ -66,6 +78,8 @@ struct Param {
   bool has_aux = false, pred_prob = true;
   double stop_rel_objv = 1e-5;
   std::string parse = "host";  // device: DeviceBatchReader (criteo text parsed on the GPU)
+  std::string cache = "none";  // device: formed batches kept in HBM, replayed after the first epoch
+  int64_t cache_mb = 16384;    // its budget (per shard)
 };
 
 // sgd_learner.h:65-69
@@ -91,16 +105,42 @@ std::string Text(const Progress& p) {
   return buf;
 }
 
+// the batch cache's list of a part: one per (job kind, part)
+int64_t CacheList(const Param& P, bool train, int part) {
+  return (int64_t)(train ? 0 : 1) * P.num_jobs_per_epoch + part;
+}
+
+// cache (optional): record = the recording pass, every batch is also appended to its part's
+// list (the step still takes the original batch); else a part whose list was sealed is replayed
+// from the cache with no reader, any other part is read as without the cache
+// after the recording epoch: what the batch cache holds (a sharded run: summed over the shards)
+void PrintCacheLine(double batches, double bytes, double dropped, double parts) {
+  std::printf("cache=device: %.0f batches, %.1f MB held, %.0f of %.0f parts not cached\n", batches,
+              bytes / (1 << 20), dropped, parts);
+}
+
 Progress RunEpoch(GpuSGDLearner* learner, const Param& P, int epoch, int job_type,
                   FILE* pred_file = nullptr, DeviceTextFeed* feed = nullptr,
-                  DeviceBatchReader::Times* times = nullptr, double* step_s = nullptr) {
+                  DeviceBatchReader::Times* times = nullptr, double* step_s = nullptr,
+                  DeviceBatchCache* cache = nullptr, bool record = false) {
   Progress prog;
   std::vector<real_t> pred;
   const bool train = job_type == GpuSGDLearner::kTraining;
   const std::string& path = train ? P.data_in : P.data_val;
   size_t fallback = 0;
   for (int part = 0; part < P.num_jobs_per_epoch; ++part) {
-    if (feed) {
+    const int64_t list = CacheList(P, train, part);
+    const bool rec = cache && record;
+    const int64_t n_cached = cache && !record ? cache->Count(list) : -1;
+    if (rec) cache->Begin(list);
+    if (n_cached >= 0) {
+      for (int64_t i = 0; i < n_cached; ++i) {
+        const dfx_batch b = cache->Get(list, i);
+        const double ts = Now();
+        learner->ProcessDeviceBatch(b, job_type, train && epoch == 0);
+        if (step_s) step_s[0] += Now() - ts;
+      }
+    } else if (feed) {
       // parse=device: the same parts, chunks and batches, formed on the device
       DeviceBatchReader reader(feed, path, P.data_format, part, P.num_jobs_per_epoch,
                                train ? P.batch_size : 0, train ? P.batch_size * P.shuffle : 0,
@@ -108,6 +148,7 @@ Progress RunEpoch(GpuSGDLearner* learner, const Param& P, int epoch, int job_typ
                                train ? (size_t)64 << 20 : (size_t)256 << 20);
       while (reader.Next()) {
         const dfx_batch& b = reader.Value();
+        if (rec) cache->Append(b);
         const double ts = Now();
         learner->ProcessDeviceBatch(b, job_type, train && epoch == 0,
                                     pred_file ? &pred : nullptr);
@@ -132,7 +173,9 @@ Progress RunEpoch(GpuSGDLearner* learner, const Param& P, int epoch, int job_typ
                                  P.batch_size * P.shuffle, P.neg_sampling, P.nthreads);
       while (reader.Next()) {
         const auto blk = reader.Value().GetBlock();
-        learner->ProcessBatch(blk, job_type, epoch == 0);
+        dfx_batch db;
+        learner->ProcessBatch(blk, job_type, epoch == 0, nullptr, rec ? &db : nullptr);
+        if (rec) cache->Append(db);
       }
     } else {
       // sgd_learner.cc:281-286: validation reads whole 256 MB chunks as one batch
@@ -140,12 +183,16 @@ Progress RunEpoch(GpuSGDLearner* learner, const Param& P, int epoch, int job_typ
       while (reader.Next()) {
         const auto& v = reader.Value();
         if (v.Size() == 0) continue;
-        learner->ProcessBatch(v.GetBlock(), job_type, false, pred_file ? &pred : nullptr);
+        dfx_batch db;
+        learner->ProcessBatch(v.GetBlock(), job_type, false, pred_file ? &pred : nullptr,
+                              rec ? &db : nullptr);
+        if (rec) cache->Append(db);
         for (size_t i = 0; pred_file && i < pred.size(); ++i)  // SavePred
           std::fprintf(pred_file, "%g\t%g\n", v.label[i],
                        P.pred_prob ? 1.0 / (1.0 + std::exp(-pred[i])) : (double)pred[i]);
       }
     }
+    if (rec) cache->Seal();
     const double tj = Now();
     const Progress p = learner->TakeProgress();
     if (step_s) step_s[1] += Now() - tj;
@@ -342,26 +389,40 @@ int RunSharded(const Param& P, const KWArgs& rest) {
     GpuShardedStore store(ex.get(), P.pipelined);
     std::vector<std::vector<DevBatch>> dev(nlocal);
     for (auto& v : dev) v.resize(3);
+    // cache=device: each local shard's batch cache on its own context (list = job), recorded in
+    // the first epoch this run executes; destroyed, joining its context, before the contexts
+    std::vector<std::unique_ptr<DeviceBatchCache>> caches(nlocal);
+    if (P.cache == "device")
+      for (int l = 0; l < nlocal; ++l)
+        caches[l].reset(new DeviceBatchCache(ctxs[l], P.cache_mb << 20));
     int ring = 0;
     const double t0 = Now();
     double pre_loss = 0;
-    for (int k = std::max(0, P.load_epoch > 0 ? P.load_epoch + 1 : 0); k < P.max_num_epochs; ++k) {
+    const int kfirst = std::max(0, P.load_epoch > 0 ? P.load_epoch + 1 : 0);
+    for (int k = kfirst; k < P.max_num_epochs; ++k) {
       const double te = Now();
+      const bool record = P.cache == "device" && k == kfirst;
       for (int job = 0; job < P.num_jobs_per_epoch; ++job) {
-        // shard r reads part job * nshards + r of num_jobs_per_epoch * nshards
+        // shard r reads part job * nshards + r of num_jobs_per_epoch * nshards, or replays the
+        // batches it uploaded for it in the recording epoch
         const int nparts = P.num_jobs_per_epoch * nshards;
         std::vector<std::unique_ptr<ThreadedBatchReader>> rd(nlocal);
-        for (int l = 0; l < nlocal; ++l)
-          rd[l].reset(new ThreadedBatchReader(P.data_in, P.data_format,
-                                              job * nshards + ex->rank(l), nparts, P.batch_size,
-                                              P.batch_size * P.shuffle, P.neg_sampling,
-                                              P.nthreads));
+        std::vector<int64_t> n_cached(nlocal, -1), pos(nlocal, 0);
+        for (int l = 0; l < nlocal; ++l) {
+          if (caches[l] && !record) n_cached[l] = caches[l]->Count(job);
+          if (n_cached[l] < 0)
+            rd[l].reset(new ThreadedBatchReader(P.data_in, P.data_format,
+                                                job * nshards + ex->rank(l), nparts, P.batch_size,
+                                                P.batch_size * P.shuffle, P.neg_sampling,
+                                                P.nthreads));
+          if (record) caches[l]->Begin(job);
+        }
         std::vector<bool> more(nlocal, true);
         for (;;) {
           std::vector<dfx_batch> bs(nlocal);
           std::vector<double> any(1, 0.0);
           for (int l = 0; l < nlocal; ++l) {
-            if (more[l]) more[l] = rd[l]->Next();
+            if (more[l]) more[l] = rd[l] ? rd[l]->Next() : pos[l] < n_cached[l];
             if (more[l]) any[0] += 1;
           }
           ex->AllReduceSum(&any);
@@ -369,13 +430,20 @@ int RunSharded(const Param& P, const KWArgs& rest) {
           for (int l = 0; l < nlocal; ++l) local_any = local_any || more[l];
           if (any[0] == 0 && !local_any) break;
           for (int l = 0; l < nlocal; ++l) {
+            if (more[l] && !rd[l]) {
+              bs[l] = caches[l]->Get(job, pos[l]++);
+              continue;
+            }
             DevBatch& db = dev[l][ring];
             db.Upload(ctxs[l], more[l] ? &rd[l]->Value() : nullptr);
             bs[l] = db.b;
+            if (record && more[l]) caches[l]->Append(db.b);
           }
           ring = (ring + 1) % 3;
           store.Submit(bs, GpuSGDLearner::kTraining, k == 0);
         }
+        if (record)
+          for (int l = 0; l < nlocal; ++l) caches[l]->Seal();
       }
       store.Flush();
       std::vector<double> pr(3, 0.0);
@@ -395,6 +463,18 @@ int RunSharded(const Param& P, const KWArgs& rest) {
       if (rank == 0)
         std::printf("Epoch[%d] Training: %s  (%.0f ex/s incl. parse+PCIe, %d shards, %.2f s)\n", k,
                     Text(tr).c_str(), tr.nrows / dt, nshards, Now() - t0);
+      if (record) {  // rank 0 prints the shards' sums
+        std::vector<double> cs(4, 0.0);
+        for (int l = 0; l < nlocal; ++l) {
+          const DeviceBatchCache::Stats s = caches[l]->GetStats();
+          cs[0] += (double)s.batches;
+          cs[1] += (double)s.bytes;
+          cs[2] += (double)s.dropped;
+          cs[3] += (double)(s.sealed + s.dropped);
+        }
+        ex->AllReduceSum(&cs);
+        if (rank == 0) PrintCacheLine(cs[0], cs[1], cs[2], cs[3]);
+      }
       std::fflush(stdout);
       const double eps = std::fabs(tr.loss - pre_loss) / pre_loss;
       if (eps < P.stop_rel_objv) break;
@@ -445,6 +525,8 @@ int main(int argc, char** argv) {
     else if (k == "exchange") P.exchange = v;
     else if (k == "model_in_parts") P.model_in_parts = std::stoi(v);
     else if (k == "parse") P.parse = v;
+    else if (k == "cache") P.cache = v;
+    else if (k == "cache_mb") P.cache_mb = std::stoll(v);
     else {
       fused_given = fused_given || k == "fused";
       rest.push_back({k, v});
@@ -476,12 +558,36 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
+  if (P.cache != "none" && P.cache != "device") {
+    std::fprintf(stderr, "cache must be none or device\n");
+    return 2;
+  }
+  if (P.cache == "device") {  // no silent run without the cache
+    bool fused = true;
+    for (const auto& kv : rest)
+      if (kv.first == "fused") fused = std::stoi(kv.second) != 0;
+    const char* why = nullptr;
+    if (!fused)
+      why = "the fused path (fused=1)";
+    else if (sharded && P.exchange == "split")
+      why = "exchange=a2a in a sharded run (exchange=split takes host row blocks)";
+    else if (P.cache_mb < 0)
+      why = "cache_mb >= 0";
+    if (why) {
+      std::fprintf(stderr, "cache=device needs %s\n", why);
+      return 2;
+    }
+  }
   if (sharded) return RunSharded(P, rest);
   if (!fused_given) rest.push_back({"fused", "1"});
   GpuSGDLearner learner(rest);
   std::unique_ptr<DeviceTextFeed> feed;
   if (P.parse == "device")
     feed.reset(new DeviceTextFeed(learner.context(), P.batch_size, P.batch_size * P.shuffle));
+  // (declared after the learner and the feed: destroyed, joining the context, before them)
+  std::unique_ptr<DeviceBatchCache> cache;
+  if (P.cache == "device" && P.task != 2)
+    cache.reset(new DeviceBatchCache(learner.context(), P.cache_mb << 20));
   int k0 = 0;
   if (!P.model_in.empty()) {  // sgd_learner.cc:58-67
     FileStream fi(ModelName(P.model_in, P.load_epoch > 0 ? P.load_epoch : -1).c_str(), "rb");
@@ -512,8 +618,9 @@ int main(int argc, char** argv) {
     const double te = Now();
     DeviceBatchReader::Times rt;
     double step_s[2] = {0, 0};  // inside dfx_train_step calls; the epoch's final join
-    const Progress tr =
-        RunEpoch(&learner, P, k, GpuSGDLearner::kTraining, nullptr, feed.get(), &rt, step_s);
+    const bool record = k == k0;  // the first epoch this run executes records
+    const Progress tr = RunEpoch(&learner, P, k, GpuSGDLearner::kTraining, nullptr, feed.get(),
+                                 &rt, step_s, cache.get(), record);
     const double dt = Now() - te;
     std::printf("Epoch[%d] Training: %s  (%.0f ex/s incl. parse+PCIe, %.2f s)\n", k,
                 Text(tr).c_str(), tr.nrows / dt, Now() - t0);
@@ -524,8 +631,14 @@ int main(int argc, char** argv) {
                   dt, rt.copy, rt.wait_text, rt.wait_parse, rt.wait_step, step_s[0], step_s[1]);
     Progress va;
     if (!P.data_val.empty()) {
-      va = RunEpoch(&learner, P, k, GpuSGDLearner::kValidation, nullptr, feed.get());
+      va = RunEpoch(&learner, P, k, GpuSGDLearner::kValidation, nullptr, feed.get(), nullptr,
+                    nullptr, cache.get(), record);
       std::printf("Epoch[%d] Validation: %s\n", k, Text(va).c_str());
+    }
+    if (cache && record) {
+      const DeviceBatchCache::Stats cs = cache->GetStats();
+      PrintCacheLine((double)cs.batches, (double)cs.bytes, (double)cs.dropped,
+                     (double)(cs.sealed + cs.dropped));
     }
     std::fflush(stdout);
     // stop criteria, sgd_learner.cc:89-108

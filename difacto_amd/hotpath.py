@@ -15,6 +15,7 @@ keys travel as int64 tensors holding the same bits, u32 as int32.  Every call go
 the C-ABI; a failing status raises DfxError (the reference would LOG(FATAL)).
 """
 import ctypes
+import weakref
 
 import numpy as np
 import torch
@@ -64,6 +65,8 @@ class Context:
 
     def close(self):
         if getattr(self, "h", None):
+            for bc in list(getattr(self, "_caches", ())):  # they join this context
+                bc.close()
             _lib.lib().dfx_ctx_destroy(self.h)
             self.h = None
 
@@ -255,6 +258,103 @@ def train_step(ctx, dblk, job_type=kTraining, push_cnt=False, max_index=MAX_INDE
     b = dblk.as_batch()
     check(_lib.lib().dfx_train_step(ctx.h, ctypes.byref(b), int(job_type), int(bool(push_cnt)),
                                     ctypes.c_uint64(max_index), _p(pred)))
+
+
+class CachedBatch:
+    """A batch held by a BatchCache: as_batch() like DeviceRowBlock (its pointers point into
+    the cache and stay valid until the cache is closed); arrays() downloads it."""
+
+    def __init__(self, ctx, b):
+        self.ctx = ctx
+        self.b = b
+        self.size = b.size
+        self.nnz = b.nnz
+
+    def as_batch(self):
+        b = self.b
+        return _lib.Batch(b.size, b.nnz, b.offset, b.index, b.value, b.label, b.weight)
+
+    def pointers(self):
+        """the device addresses of offset, index, value, label, weight (None: NULL)"""
+        b = self.b
+        return {"offs": b.offset, "ids": b.index, "vals": b.value, "labels": b.label,
+                "weights": b.weight}
+
+    def _download(self, ptr, n, dtype):
+        if ptr is None:
+            return None
+        out = np.empty(n, dtype)
+        if n:
+            check(_lib.lib().dfx_memcpy(self.ctx.h, ctypes.c_void_p(out.ctypes.data),
+                                        ctypes.c_void_p(ptr), out.nbytes, 1))
+        return out
+
+    def arrays(self):
+        """-> dict of host numpy arrays (None where the cached pointer is NULL); joins the
+        context stream, behind which the cache's copies ran when no input stream is set"""
+        b = self.b
+        return {"offs": self._download(b.offset, b.size + 1, np.uint64),
+                "ids": self._download(b.index, b.nnz, np.uint64),
+                "vals": self._download(b.value, b.nnz, np.float32),
+                "labels": self._download(b.label, b.size, np.float32),
+                "weights": self._download(b.weight, b.size, np.float32)}
+
+
+class BatchCache:
+    """The device batch cache (dfx_batchcache_*, include/difacto_amd.h): lists of formed
+    batches kept in device memory and replayed through train_step.  A list that does not fit
+    budget_bytes is dropped (append returns False, seal -1), never an error."""
+
+    def __init__(self, ctx, budget_bytes, block_bytes=0):
+        self.ctx = ctx
+        h = ctypes.c_void_p()
+        check(_lib.lib().dfx_batchcache_create(ctx.h, int(budget_bytes), int(block_bytes),
+                                               ctypes.byref(h)))
+        self.h = h
+        if not hasattr(ctx, "_caches"):
+            ctx._caches = weakref.WeakSet()  # Context.close closes its caches first
+        ctx._caches.add(self)
+
+    def begin(self, list_id):
+        check(_lib.lib().dfx_batchcache_begin(self.h, int(list_id)))
+
+    def append(self, dblk):
+        """copies dblk (anything with as_batch()) into the open list -> kept"""
+        b = dblk.as_batch()
+        kept = ctypes.c_int(0)
+        check(_lib.lib().dfx_batchcache_append(self.h, ctypes.byref(b), ctypes.byref(kept)))
+        return bool(kept.value)
+
+    def seal(self):
+        n = ctypes.c_int64(0)
+        check(_lib.lib().dfx_batchcache_seal(self.h, ctypes.byref(n)))
+        return n.value
+
+    def count(self, list_id):
+        n = ctypes.c_int64(0)
+        check(_lib.lib().dfx_batchcache_count(self.h, int(list_id), ctypes.byref(n)))
+        return n.value
+
+    def get(self, list_id, i):
+        b = _lib.Batch()
+        check(_lib.lib().dfx_batchcache_get(self.h, int(list_id), int(i), ctypes.byref(b)))
+        return CachedBatch(self.ctx, b)
+
+    def stats(self):
+        out = (ctypes.c_int64 * 4)()
+        check(_lib.lib().dfx_batchcache_stats(self.h, out))
+        return dict(zip(("sealed", "dropped", "batches", "bytes"), list(out)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            h, self.h = self.h, None
+            check(_lib.lib().dfx_batchcache_destroy(h))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def parse_criteo(ctx, data, is_train=True):

@@ -214,6 +214,47 @@ int dfx_textfeed_consumed(dfx_textfeed* f);
 int dfx_textfeed_slot_batch(dfx_textfeed* f, int slot, dfx_batch* out);
 int dfx_textfeed_slot_consumed(dfx_textfeed* f, int slot);
 
+/* ---- device batch cache (difacto_amd/csrc/batchcache.hip) --------------------------------
+ * Formed batches kept in device memory, so that every epoch after the first replays them with
+ * no reader, no upload and no parse: a reader lives for one part of one epoch and seeds its
+ * shuffle and down-sampling afresh (batch_reader.cc:12-27), so a part yields the same batches
+ * in every epoch.  A list is an ordered sequence of batches under a caller-chosen id >= 0 (the
+ * driver: one per job kind and part).
+ *   dfx_batchcache_begin   opens a list for recording (one at a time; an id only once)
+ *   dfx_batchcache_append  adds a copy of *src: byte for byte its offset[B+1], index[nnz] and
+ *                          label[B], and value[nnz] / weight[B] when it has them (NULL stays
+ *                          NULL); *kept = 1.  Device-to-device copies, asynchronous on the
+ *                          context's input stream (dfx_ctx_set_input_stream; none: the context
+ *                          stream): behind the producer of *src, before that stream reuses its
+ *                          buffers, no host wait
+ *   dfx_batchcache_seal    closes the open list; *n_batches its length, -1 if it was dropped
+ *   dfx_batchcache_count   *n_batches of a sealed list, -1 dropped, -2 never begun
+ *   dfx_batchcache_get     batch i of a sealed list, its pointers into the cache: valid until
+ *                          destroy, ready by the input stream's order, and good for
+ *                          dfx_train_step, dfx_dist_localize, ... any number of times
+ *   dfx_batchcache_stats   out[4] = {lists sealed, lists dropped, batches held, bytes allocated}
+ * Memory: device blocks of block_bytes (0: 64 MiB), each owned by one list and never moved; an
+ * array larger than a block has an allocation of its own; every array starts on a 256-byte
+ * boundary, as allocations do (the step's kernels read them with vector loads).  budget_bytes
+ * bounds the sum of the allocations, and a hipMalloc out of memory counts as over budget.  An
+ * append that does not fit drops the open list: *kept = 0 with DFX_OK (so do later appends),
+ * its blocks are freed after joining the stream that copies into them, get on it is
+ * DFX_ERR_ARG; sealed lists are untouched and a later list may use the freed budget.  Training
+ * never fails because the cache could not grow.  destroy joins the context (dfx_sync) first.
+ * DFX_ERR_ARG: append / seal with no open list, begin while one is open or of an id already
+ * sealed or dropped, get of an open list or with i out of range, negative sizes, a batch with
+ * rows but no offset or label. */
+typedef struct dfx_batchcache dfx_batchcache;
+int dfx_batchcache_create(dfx_ctx* ctx, int64_t budget_bytes, int64_t block_bytes,
+                          dfx_batchcache** out);
+int dfx_batchcache_destroy(dfx_batchcache* bc);
+int dfx_batchcache_begin(dfx_batchcache* bc, int64_t list);
+int dfx_batchcache_append(dfx_batchcache* bc, const dfx_batch* src, int* kept);
+int dfx_batchcache_seal(dfx_batchcache* bc, int64_t* n_batches);
+int dfx_batchcache_count(dfx_batchcache* bc, int64_t list, int64_t* n_batches);
+int dfx_batchcache_get(dfx_batchcache* bc, int64_t list, int64_t i, dfx_batch* out);
+int dfx_batchcache_stats(dfx_batchcache* bc, int64_t* out); /* out[4] */
+
 /* ---- Localizer::Compact (localizer.h:41-51) -------------------------------------------
  * keys = ReverseBytes(index % max_index); uniq[U] ascending, cnt[U] occurrence counts
  * (float, may be NULL), col[nnz] = rank of each nnz's key (the u32 CSR index).  Offsets,
