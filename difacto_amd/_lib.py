@@ -60,6 +60,8 @@ _SIGS = {
     "dfx_memcpy": (ctypes.c_int, [vp, vp, vp, ctypes.c_size_t, ctypes.c_int]),
     "dfx_reserve": (ctypes.c_int, [vp, c_i64, c_i64]),
     "dfx_localize": (ctypes.c_int, [vp, c_i64, c_i64, vp, vp, c_u64, vp, vp, vp, i64p]),
+    "dfx_localize_occ": (ctypes.c_int, [vp, c_i64, c_i64, vp, vp, vp, c_u64, ctypes.c_int, vp, vp,
+                                        vp, vp, vp, vp, vp, i64p]),
     "dfx_fm_predict": (ctypes.c_int, [vp, c_i64, c_i64, vp, vp, vp, vp, vp, vp, c_i64,
                                       ctypes.c_int, vp]),
     "dfx_fm_calcgrad": (ctypes.c_int, [vp, c_i64, c_i64, vp, vp, vp, vp, vp, vp, vp, vp, c_i64,

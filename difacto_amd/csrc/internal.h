@@ -261,6 +261,9 @@ struct Context {
   int lb_hnt = 0;         // kwarg lb_hnt: the bucket Localizer's histogram / scatter block (0 auto)
   int lb_diag = 0;        // kwarg lb_diag (MEASUREMENT ONLY, wrong results): bucket kernel parts off
   int lb_skip = 0;        // lb_diag's launch-skip bits, armed once a workspace holds a batch
+  // the last bucket Localizer's launch plan (host values, dfx_localize_occ's stats): bucket
+  // bits, row tiles, rows per tile, 1 when the per-bucket sort was launched in its unpacked form
+  int64_t lb_plan[4] = {0, 0, 0, 0};
   int diag = 0;           // kwarg diag (measurement only): bit 0 no AUC lane, bit 1 Localizer once
   bool loc_done[2] = {false, false};  // diag bit 1: the parity's Localizer output exists
   const uint2* loc_rowof[2] = {nullptr, nullptr};  // (lb_gather=2) the parity's {row, value} by position
@@ -434,6 +437,8 @@ struct LocOut {
   // (fused step, lb_gather=2) set by the bucket Localizer when it left each occurrence's input
   // position in occ_row and its {row, value} here for the backward to read (else nullptr)
   const uint2** rowof_out = nullptr;
+  // (dfx_localize_occ) set to whether the bucket Localizer took the batch (else the radix sort)
+  bool* used_bucket = nullptr;
 };
 int localize_run(Context* c, const Lane& L, int64_t B, int64_t nnz, const uint64_t* offset,
                  const uint64_t* index, uint64_t max_index, const LocOut& o);

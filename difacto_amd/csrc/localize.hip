@@ -358,6 +358,7 @@ int localize_run(Context* c, const Lane& L, int64_t B, int64_t nnz, const uint64
   DevState* ds = L.ds;
   DFX_CHECK_ARG(max_index != 0, "localize: max_index must be > 0");
   DFX_CHECK_ARG(nnz < (int64_t)0xFFFFFFFFll, "localize: nnz must fit u32 (localizer.cc:16)");
+  if (o.used_bucket) *o.used_bucket = false;
   if (B <= 0 || nnz <= 0) {
     hipLaunchKernelGGL(k_set_u, dim3(1), dim3(1), 0, L.stream, ds, 0u);
     if (o.segstart) DFX_HIP(hipMemsetAsync(o.segstart, 0, sizeof(uint32_t), L.stream));
@@ -374,6 +375,7 @@ int localize_run(Context* c, const Lane& L, int64_t B, int64_t nnz, const uint64
     ob.segstart = segs;
     bool used = false;
     DFX_TRY(localize_bucket(c, L, B, nnz, offset, index, max_index, ob, &used));
+    if (o.used_bucket) *o.used_bucket = used;
     if (used) {
       if (o.cnt)
         hipLaunchKernelGGL(k_loc_cnt, dim3((nnz + 255) / 256), dim3(256), 0, L.stream, ds, segs,
@@ -473,5 +475,74 @@ extern "C" int dfx_localize(dfx_ctx* ctx, int64_t B, int64_t nnz, const uint64_t
     DFX_HIP(hipStreamSynchronize(c->stream));
     *n_uniq = u;
   }
+  return DFX_OK;
+}
+
+// What the fused step's Localizer lane and the split owner hand to the forward / backward, run
+// on the main lane exactly as they run it (loc_reserve, localize_run without col, chunk_plan),
+// so the workspace's hint words and the lane's device state carry from call to call as they do
+// per lane in training; then a synchronise and the results copied out (the tests' view).
+extern "C" int dfx_localize_occ(dfx_ctx* ctx, int64_t B, int64_t nnz, const uint64_t* offset,
+                                const uint64_t* index, const float* value, uint64_t max_index,
+                                int keys_ready, uint64_t* uniq, uint32_t* segstart,
+                                uint32_t* occ_row, float* occ_x, uint32_t* choff,
+                                uint32_t* chunk_seg, uint32_t* rowof, int64_t* stats) {
+  DFX_CHECK_ARG(ctx, "null ctx");
+  Context* c = &ctx->c;
+  DFX_CHECK_ARG(B >= 0 && nnz >= 0, "localize_occ: negative sizes");
+  DFX_CHECK_ARG(stats && segstart, "localize_occ: null stats / segstart");
+  DFX_CHECK_ARG(nnz == 0 || (offset && index && uniq && occ_row && choff && chunk_seg),
+                "localize_occ: null buffer");
+  DFX_CHECK_ARG(!value || nnz == 0 || (occ_x && rowof),
+                "localize_occ: valued without occ_x / rowof");
+  const Lane L = main_lane(c);
+  Workspace& ws = c->ws;
+  DFX_TRY(loc_reserve(ws, nnz, L.stream));
+  LocOut o;
+  o.uniq = ws.uniq.as<uint64_t>();
+  o.segstart = ws.segstart.as<uint32_t>();
+  o.value = value;
+  o.occ_row = ws.occ_row.as<uint32_t>();
+  o.occ_x = value ? ws.occ_x.as<float>() : nullptr;
+  o.keys_ready = keys_ready != 0;
+  const uint2* ro = nullptr;
+  bool used = false;
+  o.rowof_out = &ro;
+  o.used_bucket = &used;
+  uint32_t* ws_choff = ws.flags.as<uint32_t>();
+  uint32_t* ws_cseg = ws.rowtmp.as<uint32_t>();
+  DFX_TRY(localize_run(c, L, B, nnz, offset, index, max_index, o));
+  DFX_TRY(chunk_plan(L, nnz, o.segstart, ws_choff, ws_cseg, &L.ds->totals[1]));
+  DevState h;
+  DFX_HIP(hipMemcpyAsync(&h, L.ds, sizeof(DevState), hipMemcpyDeviceToHost, L.stream));
+  DFX_HIP(hipStreamSynchronize(L.stream));
+  const int64_t U = h.u_count, nch = h.totals[1];
+  DFX_CHECK_ARG(U <= nnz && nch <= max_chunks(nnz), "localize_occ: U / n_chunks out of range");
+  const auto d2d = hipMemcpyDeviceToDevice;
+  if (U > 0) DFX_HIP(hipMemcpyAsync(uniq, o.uniq, U * 8, d2d, L.stream));
+  DFX_HIP(hipMemcpyAsync(segstart, o.segstart, (U + 1) * 4, d2d, L.stream));
+  if (nnz > 0 && B > 0) {
+    DFX_HIP(hipMemcpyAsync(occ_row, o.occ_row, nnz * 4, d2d, L.stream));
+    if (value && !ro) DFX_HIP(hipMemcpyAsync(occ_x, o.occ_x, nnz * 4, d2d, L.stream));
+    if (ro) DFX_HIP(hipMemcpyAsync(rowof, ro, nnz * 8, d2d, L.stream));
+  }
+  if (nch > 0) {
+    DFX_HIP(hipMemcpyAsync(choff, ws_choff, U * 4, d2d, L.stream));
+    DFX_HIP(hipMemcpyAsync(chunk_seg, ws_cseg, nch * 4, d2d, L.stream));
+  }
+  // the main lane's n_init is also the fused backward's InitV gate: left clear
+  DFX_HIP(hipMemsetAsync(&L.ds->n_init, 0, sizeof(unsigned), L.stream));
+  DFX_HIP(hipStreamSynchronize(L.stream));
+  const unsigned int* hint = ws.lb_hint;
+  stats[0] = U;
+  stats[1] = nch;
+  stats[2] = h.n_init;
+  stats[3] = used ? 1 : 0;
+  for (int i = 0; i < 4; ++i) stats[4 + i] = hint ? (int64_t)hint[i] : 0;
+  stats[8] = h.lb_over;
+  stats[9] = h.lb_map_steps;
+  stats[10] = ro ? 1 : 0;
+  stats[11] = h.pk_valid;
+  for (int i = 0; i < 4; ++i) stats[12 + i] = used ? c->lb_plan[i] : 0;
   return DFX_OK;
 }

@@ -1435,6 +1435,7 @@ int localize_bucket(Context* c, const Lane& L, int64_t B, int64_t nnz, const uin
   // the LDS form of the per-bucket sort follows the last batch's item form (a batch whose items
   // do not pack while the launch expected packed ones sorts through global memory: correct)
   const bool q_lds = hint[2] == 2u;
+  c->lb_plan[0] = wbits; c->lb_plan[1] = ntiles; c->lb_plan[2] = rt; c->lb_plan[3] = q_lds ? 1 : 0;
   const dim3 bg(nbk), bb(kLbNT);
   const bool carry = valued && !gather;  // side payloads through the sort
   if (carry)

@@ -144,6 +144,60 @@ class Localizer:
         return col[:nnz], uniq[:U], (cnt[:U] if want_cnt else None)
 
 
+LOC_STATS = ("U", "n_chunks", "n_init", "used", "hint0", "hint1", "hint2", "hint3", "lb_over",
+             "lb_map_steps", "deferred", "pk_valid", "wbits", "ntiles", "rt", "q_lds")
+
+
+def localize_occ(ctx, offs, ids, vals=None, max_index=MAX_INDEX, keys_ready=False):
+    """dfx_localize_occ: what the fused step's Localizer lane (and the split owner, keys_ready)
+    leaves for the forward / backward, as host numpy arrays: uniq[U], segstart[U + 1],
+    occ_row[nnz], occ_x[nnz] (uint32 bit patterns; None for binary data), n_chunks, choff[U]
+    and chunk_seg[n_chunks] (None without chunks), and the stats by name (LOC_STATS) plus
+    ``mapped``: this batch was placed by the hot-key map.  With lb_gather=2 the occurrences'
+    rows and values are resolved through the {row, value}-by-position array, as the backward
+    reads them."""
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    ids = np.ascontiguousarray(ids, dtype=np.uint64)
+    B, nnz = max(len(offs) - 1, 0), len(ids)
+    dev = ctx.device
+
+    def buf(n, dt):
+        return torch.empty(max(int(n), 1), dtype=dt, device=dev)
+
+    d_offs = ctx.tensor(offs, torch.int64) if len(offs) else None
+    d_ids = ctx.tensor(ids, torch.int64) if nnz else None
+    d_vals = ctx.tensor(np.ascontiguousarray(vals, dtype=np.float32), torch.float32) \
+        if vals is not None and nnz else None
+    valued = vals is not None
+    uniq, seg = buf(nnz, torch.int64), buf(nnz + 1, torch.int32)
+    occ_row, choff = buf(nnz, torch.int32), buf(nnz, torch.int32)
+    occ_x = buf(nnz, torch.int32) if valued else None
+    rowof = buf(2 * nnz, torch.int32) if valued else None
+    cseg = buf(nnz // 128 + nnz // 129 + 2, torch.int32)
+    stats = (ctypes.c_int64 * len(LOC_STATS))()
+    torch.cuda.current_stream(dev).synchronize()  # the inputs, for the context's own stream
+    check(_lib.lib().dfx_localize_occ(ctx.h, B, nnz, _p(d_offs), _p(d_ids), _p(d_vals),
+                                      ctypes.c_uint64(max_index), int(bool(keys_ready)),
+                                      _p(uniq), _p(seg), _p(occ_row), _p(occ_x), _p(choff),
+                                      _p(cseg), _p(rowof), stats))
+    st = dict(zip(LOC_STATS, (int(v) for v in stats)))
+    prev = getattr(ctx, "_lb_map_steps", 0)
+    st["mapped"] = st["lb_map_steps"] - prev
+    ctx._lb_map_steps = st["lb_map_steps"]
+    U, nch = st["U"], st["n_chunks"]
+    out = {"U": U, "n_chunks": nch, "stats": st,
+           "uniq": u64(uniq[:U]), "segstart": u32(seg[:U + 1])}
+    rows = u32(occ_row[:nnz])
+    xs = u32(occ_x[:nnz]) if valued else None
+    if st["deferred"]:
+        rv = u32(rowof[:2 * nnz]).reshape(nnz, 2)
+        rows, xs = rv[rows, 0].copy(), rv[rows, 1].copy()
+    out["occ_row"], out["occ_x"] = rows, xs
+    out["choff"] = u32(choff[:U]) if nch > 0 else None
+    out["chunk_seg"] = u32(cseg[:nch]) if nch > 0 else None
+    return out
+
+
 class FMLoss:
     """FMLoss (src/loss/fm_loss.h); V_dim == 0 is LogitLoss (src/loss/logit_loss.h)."""
 

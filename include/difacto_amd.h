@@ -263,6 +263,28 @@ int dfx_batchcache_stats(dfx_batchcache* bc, int64_t* out); /* out[4] */
 int dfx_localize(dfx_ctx* ctx, int64_t B, int64_t nnz, const uint64_t* offset,
                  const uint64_t* index, uint64_t max_index, uint64_t* uniq, float* cnt,
                  uint32_t* col, int64_t* n_uniq);
+/* The Localizer as dfx_train_step's lane and dfx_split_owner_begin run it (no col; the bucket
+ * sort unless loc_bucket=0 or its hints choose the radix sort), with the long segments' chunk
+ * plan, on the context's main lane — whose hints and device state carry from call to call as a
+ * lane's do in training — then copied out; synchronises.  For tests: the fused step reads
+ * these arrays in place.  value NULL: binary.  keys_ready: index holds the final keys (the
+ * split owner's form; max_index ~0).  Device buffers: uniq[nnz], segstart[nnz + 1],
+ * occ_row[nnz], occ_x[nnz] (valued), choff[nnz], chunk_seg[nnz / 128 + nnz / 129 + 2],
+ * rowof[2 * nnz] (valued).  Written: uniq[U] ascending, segstart[U + 1], per occurrence in
+ * (key, position) order its row and value; when the plan holds chunks, choff[U] (a segment's
+ * first chunk) and chunk_seg[n_chunks].  With lb_gather=2 a valued bucket batch leaves each
+ * occurrence's input position in occ_row and {row, value bits} by position in rowof
+ * (stats[10] = 1), as the backward reads them; occ_x is then not written.
+ * stats[16] (host): U, n_chunks, the plan's gate, 1 when the bucket sort ran, the
+ * workspace's four hint words (oversize buckets of its last bucket sort, radix sorts since,
+ * item form 1 packed / 2 not, hot-key map built), oversize buckets of this batch (bucket sort
+ * only), batches placed by the hot-key map so far, rowof written, a key map fitted; of the
+ * bucket sort's launch: bucket bits, row tiles, rows per tile, 1 for the unpacked sort form. */
+int dfx_localize_occ(dfx_ctx* ctx, int64_t B, int64_t nnz, const uint64_t* offset,
+                     const uint64_t* index, const float* value, uint64_t max_index,
+                     int keys_ready, uint64_t* uniq, uint32_t* segstart, uint32_t* occ_row,
+                     float* occ_x, uint32_t* choff, uint32_t* chunk_seg, uint32_t* rowof,
+                     int64_t* stats);
 
 /* ---- FMLoss / LogitLoss ----------------------------------------------------------------
  * weights: the interleaved Pull layout [w | V(V_dim)] addressed by w_pos / V_pos
