@@ -29,11 +29,12 @@ GENBIN = build/gen_criteo
 CONVBIN = build/dfx_convert
 RBENCH = build/reader_bench
 TPBIN = build/textparse_tests
+LSBIN = build/libsvmparse_tests
 
 DISTLIB = difacto_amd/libdfx_dist.so
 
 all: $(LIB) $(DISTLIB) oracle $(HOSTBIN) $(TRAINBIN) $(READERBIN) $(GENBIN) $(CONVBIN) $(RBENCH) \
-  $(TPBIN) build/expf_check build/locbench
+  $(TPBIN) $(LSBIN) build/expf_check build/strtof_check build/gen_libsvm build/locbench
 
 $(RBENCH): difacto_amd/host/reader.cc tools/reader_bench.cc difacto_amd/host/reader.h $(CITYHDR)
 	@mkdir -p build
@@ -62,6 +63,23 @@ $(TPBIN): $(HOSTLIB) tests/host/textparse_tests.cc $(HOSTHDR) $(LIB)
 	@mkdir -p build
 	g++ $(HOSTFLAGS) -o $@ $(HOSTLIB) tests/host/textparse_tests.cc -Ldifacto_amd -ldifacto_amd \
 	  -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN/../difacto_amd' -Wl,-rpath,/opt/rocm/lib
+
+# the device libsvm parser, the valued row gather and DeviceBatchReader("libsvm") against the
+# host reader (dfx_parse_libsvm / dfx_gather_rows_valued vs ParseLibSVM / GatherRows /
+# BatchReader), plus the CPU mode: the batch planner on valued rows with the flag mirroring
+$(LSBIN): $(HOSTLIB) tests/host/libsvmparse_tests.cc $(HOSTHDR) $(CSRC)/strtof.h $(LIB)
+	@mkdir -p build
+	g++ $(HOSTFLAGS) -o $@ $(HOSTLIB) tests/host/libsvmparse_tests.cc -Ldifacto_amd -ldifacto_amd \
+	  -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN/../difacto_amd' -Wl,-rpath,/opt/rocm/lib
+
+# test infrastructure: csrc/strtof.h (the device parser's numbers) against the host's strtof
+build/strtof_check: tools/strtof_check.cc $(CSRC)/strtof.h
+	@mkdir -p build
+	g++ -std=c++14 -O2 -Wall -o $@ $<
+
+build/gen_libsvm: tools/gen_libsvm.cc
+	@mkdir -p build
+	g++ -O2 -o $@ $<
 
 # C++ host adapters (the reference's Loss/Updater/Store over the C-ABI) + their test driver;
 # plain g++ against the C-ABI (the sharded store's exchange, dist_host.o, links RCCL)

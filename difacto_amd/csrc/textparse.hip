@@ -3,9 +3,12 @@
 //
 //   dfx_parse_criteo   ParseCriteo (difacto_amd/host/reader.cc; criteo_parser.h:40-92) over a
 //                      chunk of whole lines already in device memory
-//   dfx_gather_rows    GatherRows (reader.cc; the row copies of batch_reader.cc:29-78)
+//   dfx_gather_rows    GatherRows (reader.cc; the row copies of batch_reader.cc:29-78);
+//                      dfx_gather_rows_valued: the same kernels with values and row flags
 //   dfx_textfeed_*     pinned text slots, a loader stream, parsed chunks, a shuffle buffer and
-//                      a ring of device batches (the producer half of sgd_learner.cc:289-314)
+//                      a ring of device batches (the producer half of sgd_learner.cc:289-314);
+//                      its libsvm mode (dfx_parse_libsvm, libsvmparse.hip) is at the end
+// The scans (block_scan, k_scan_*) are csrc/textscan.h, shared with libsvmparse.hip.
 //
 // The parser is parallel over bytes and cells, never one lane per row:
 //   k_tp_tiles      every thread takes 16 bytes and marks its terminators ('\t', '\n'); a tile
@@ -43,17 +46,14 @@
 
 #include "cityhash.h"
 #include "internal.h"
+#include "textscan.h"
 
 using namespace dfx;
 
 namespace {
 
-constexpr int kNT = 256;               // threads of the tile kernels
-constexpr int kTpBytes = 16;           // text bytes per thread
-constexpr int kTpTile = kNT * kTpBytes;
 constexpr int kCols = 39;              // criteo feature columns (13 integer + 26 categorical)
 constexpr int kLineSlots = 40;         // cells kept per line: a label and 39 columns
-constexpr int kWavesPerBlock = kNT / 64;
 
 constexpr unsigned kFlagLabel = 1, kFlagCR = 2, kFlagEmptyLine = 4, kFlagTail = 8;
 
@@ -69,21 +69,6 @@ struct TpOp {
     return TpT{a.nl + b.nl, b.last1 ? b.last1 : a.last1, b.nl ? b.cafter : a.cafter + b.cafter};
   }
 };
-struct MaxOp {
-  using T = uint32_t;
-  __device__ static T id() { return 0; }
-  __device__ static T f(T a, T b) { return a > b ? a : b; }
-};
-struct AddOp {
-  using T = uint32_t;
-  __device__ static T id() { return 0; }
-  __device__ static T f(T a, T b) { return a + b; }
-};
-struct Add2Op {
-  using T = uint2;
-  __device__ static T id() { return make_uint2(0, 0); }
-  __device__ static T f(const T& a, const T& b) { return make_uint2(a.x + b.x, a.y + b.y); }
-};
 
 // the parser's device counters (zeroed per call)
 struct TpStat {
@@ -93,91 +78,6 @@ struct TpStat {
   unsigned int flags;  // kFlag* bits: needs_host
   TpT total;           // the byte pass's grand total
   uint2 rows_nnz;      // the line scan's grand total
-};
-
-// inclusive / exclusive scan of one value per thread over a block of NT threads (Hillis-Steele
-// through lds[2 * NT]); every thread also gets the block's total
-template <class Op, int NT>
-__device__ inline void block_scan(typename Op::T v, typename Op::T* lds, typename Op::T* incl,
-                                  typename Op::T* excl, typename Op::T* total) {
-  using T = typename Op::T;
-  const int t = threadIdx.x;
-  int cur = 0;
-  lds[t] = v;
-  __syncthreads();
-  for (int d = 1; d < NT; d <<= 1) {
-    T x = lds[cur * NT + t];
-    if (t >= d) x = Op::f(lds[cur * NT + t - d], x);
-    cur ^= 1;
-    lds[cur * NT + t] = x;
-    __syncthreads();
-  }
-  *incl = lds[cur * NT + t];
-  *excl = t ? lds[cur * NT + t - 1] : Op::id();
-  *total = lds[cur * NT + NT - 1];
-  __syncthreads();
-}
-
-// ---- the plain multi-launch scan: tile totals, a scan of the totals, apply ------------------
-// n = min(*n_dev, n_cap) when the length is only known on the device
-__device__ inline uint32_t scan_len(const uint32_t* n_dev, uint32_t n_cap) {
-  if (!n_dev) return n_cap;
-  const uint32_t n = *n_dev;
-  return n < n_cap ? n : n_cap;
-}
-
-template <class Op, class Load>
-__global__ __launch_bounds__(kNT) void k_scan_reduce(Load load, const uint32_t* n_dev,
-                                                     uint32_t n_cap, typename Op::T* tot) {
-  using T = typename Op::T;
-  __shared__ T lds[2 * kNT];
-  const uint32_t n = scan_len(n_dev, n_cap);
-  if ((uint64_t)blockIdx.x * kNT >= n) return;
-  const uint32_t i = blockIdx.x * kNT + threadIdx.x;
-  T incl, excl, total;
-  block_scan<Op, kNT>(i < n ? load(i) : Op::id(), lds, &incl, &excl, &total);
-  if (threadIdx.x == 0) tot[blockIdx.x] = total;
-}
-
-// exclusive scan, in place, of the ceil(n / tile) tile totals by one block; the grand total
-// goes to *total_out
-template <class Op>
-__global__ __launch_bounds__(1024) void k_scan_totals(typename Op::T* tot, const uint32_t* n_dev,
-                                                      uint32_t n_cap, uint32_t tile,
-                                                      typename Op::T* total_out) {
-  using T = typename Op::T;
-  __shared__ T lds[2 * 1024];
-  const uint32_t n = scan_len(n_dev, n_cap);
-  const uint32_t nt = n / tile + (n % tile ? 1 : 0);
-  T carry = Op::id();
-  for (uint32_t base = 0; base < nt; base += 1024) {
-    const uint32_t i = base + threadIdx.x;
-    T incl, excl, total;
-    block_scan<Op, 1024>(i < nt ? tot[i] : Op::id(), lds, &incl, &excl, &total);
-    if (i < nt) tot[i] = Op::f(carry, excl);
-    carry = Op::f(carry, total);
-  }
-  if (total_out && threadIdx.x == 0) *total_out = carry;
-}
-
-template <class Op, class Load, bool kInclusive>
-__global__ __launch_bounds__(kNT) void k_scan_apply(Load load, const uint32_t* n_dev,
-                                                    uint32_t n_cap, const typename Op::T* tot,
-                                                    typename Op::T* out) {
-  using T = typename Op::T;
-  __shared__ T lds[2 * kNT];
-  const uint32_t n = scan_len(n_dev, n_cap);
-  if ((uint64_t)blockIdx.x * kNT >= n) return;
-  const uint32_t i = blockIdx.x * kNT + threadIdx.x;
-  T incl, excl, total;
-  block_scan<Op, kNT>(i < n ? load(i) : Op::id(), lds, &incl, &excl, &total);
-  if (i < n) out[i] = Op::f(tot[blockIdx.x], kInclusive ? incl : excl);
-}
-
-template <class T>
-struct PtrLoad {
-  const T* p;
-  __device__ T operator()(uint32_t i) const { return p[i]; }
 };
 
 // ---- the byte passes --------------------------------------------------------------------------
@@ -402,12 +302,17 @@ struct LenLoad {
   }
 };
 
-// one wave per row: ids, label, the row's end offset rebased onto the destination's end
+// one wave per row: ids, label, the row's end offset rebased onto the destination's end;
+// kValued: the values too (a source without values reads as ones, GatherRows's rule; no
+// destination: dropped) and the row's flag byte
+template <bool kValued>
 __global__ __launch_bounds__(kNT) void k_tg_copy(const uint64_t* src_off, const uint64_t* src_idx,
                                                  const float* src_lab, const uint32_t* rows,
                                                  uint64_t begin, uint32_t n, const uint32_t* ex,
                                                  uint64_t* dst_off, uint64_t* dst_idx,
-                                                 float* dst_lab, uint64_t r0) {
+                                                 float* dst_lab, uint64_t r0,
+                                                 const float* src_val, float* dst_val,
+                                                 const uint8_t* src_flag, uint8_t* dst_flag) {
   const uint64_t i64 = (uint64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
   const uint32_t lane = threadIdx.x & 63;
   if (i64 >= n) return;
@@ -417,20 +322,23 @@ __global__ __launch_bounds__(kNT) void k_tg_copy(const uint64_t* src_off, const 
   const uint64_t s0 = src_off[j], d0 = base + ex[i];
   const uint32_t len = ex[i + 1] - ex[i];
   for (uint32_t k = lane; k < len; k += 64) dst_idx[d0 + k] = src_idx[s0 + k];
+  if (kValued && dst_val)
+    for (uint32_t k = lane; k < len; k += 64) dst_val[d0 + k] = src_val ? src_val[s0 + k] : 1.f;
   if (lane == 0) {
     dst_off[r0 + i + 1] = base + ex[i + 1];
     dst_lab[r0 + i] = src_lab[j];
+    if (kValued && dst_flag) dst_flag[r0 + i] = src_flag ? src_flag[j] : 0;
     if (r0 == 0 && i == 0) dst_off[0] = 0;
   }
 }
 
-inline hipStream_t input_stream(Context* c) { return c->has_in_stream ? c->in_stream : c->stream; }
-inline unsigned blocks_for(uint64_t n, uint64_t per) { return (unsigned)((n + per - 1) / per); }
-
+template <bool kValued>
 int gather_rows_on(Context* c, hipStream_t st, const uint64_t* src_offset,
                    const uint64_t* src_index, const float* src_label, const uint32_t* rows_dev,
                    int64_t begin, int64_t n, uint64_t* dst_offset, uint64_t* dst_index,
-                   float* dst_label, int64_t r0) {
+                   float* dst_label, int64_t r0, const float* src_value = nullptr,
+                   float* dst_value = nullptr, const uint8_t* src_flag = nullptr,
+                   uint8_t* dst_flag = nullptr) {
   DFX_CHECK_ARG(n >= 0 && n < (1ll << 31) && begin >= 0 && r0 >= 0, "gather_rows: bad range");
   if (n == 0) return DFX_OK;  // GatherRows: nothing appended, nothing touched
   DFX_CHECK_ARG(src_offset && src_index && src_label && dst_offset && dst_index && dst_label,
@@ -447,9 +355,10 @@ int gather_rows_on(Context* c, hipStream_t st, const uint64_t* src_offset,
                      (const uint32_t*)nullptr, n1, (uint32_t)kNT, (uint32_t*)nullptr);
   hipLaunchKernelGGL((k_scan_apply<AddOp, LenLoad, false>), dim3(blocks_for(n1, kNT)), dim3(kNT),
                      0, st, load, (const uint32_t*)nullptr, n1, (const uint32_t*)tot, ex);
-  hipLaunchKernelGGL(k_tg_copy, dim3(blocks_for((uint64_t)n, kWavesPerBlock)), dim3(kNT), 0, st,
-                     src_offset, src_index, src_label, rows_dev, (uint64_t)begin, (uint32_t)n,
-                     (const uint32_t*)ex, dst_offset, dst_index, dst_label, (uint64_t)r0);
+  hipLaunchKernelGGL(k_tg_copy<kValued>, dim3(blocks_for((uint64_t)n, kWavesPerBlock)), dim3(kNT),
+                     0, st, src_offset, src_index, src_label, rows_dev, (uint64_t)begin,
+                     (uint32_t)n, (const uint32_t*)ex, dst_offset, dst_index, dst_label,
+                     (uint64_t)r0, src_value, dst_value, src_flag, dst_flag);
   DFX_HIP(hipGetLastError());
   return DFX_OK;
 }
@@ -575,17 +484,64 @@ extern "C" int dfx_gather_rows(dfx_ctx* ctx, const uint64_t* src_offset, const u
                                float* dst_label, int64_t r0) {
   DFX_CHECK_ARG(ctx, "null ctx");
   DFX_HIP(hipSetDevice(ctx->c.device));
-  return gather_rows_on(&ctx->c, input_stream(&ctx->c), src_offset, src_index, src_label,
-                        rows_dev, begin, n, dst_offset, dst_index, dst_label, r0);
+  return gather_rows_on<false>(&ctx->c, input_stream(&ctx->c), src_offset, src_index, src_label,
+                               rows_dev, begin, n, dst_offset, dst_index, dst_label, r0);
+}
+
+extern "C" int dfx_gather_rows_valued(dfx_ctx* ctx, const uint64_t* src_offset,
+                                      const uint64_t* src_index, const float* src_value,
+                                      const float* src_label, const uint8_t* src_rowflag,
+                                      const uint32_t* rows_dev, int64_t begin, int64_t n,
+                                      uint64_t* dst_offset, uint64_t* dst_index, float* dst_value,
+                                      float* dst_label, uint8_t* dst_rowflag, int64_t r0) {
+  DFX_CHECK_ARG(ctx, "null ctx");
+  DFX_HIP(hipSetDevice(ctx->c.device));
+  return gather_rows_on<true>(&ctx->c, input_stream(&ctx->c), src_offset, src_index, src_label,
+                              rows_dev, begin, n, dst_offset, dst_index, dst_label, r0, src_value,
+                              dst_value, src_rowflag, dst_rowflag);
 }
 
 // ---- the text feeder ----------------------------------------------------------------------------
-// A CSR of criteo rows on the device: at most 39 ids per row, so rows alone size it.
+// A CSR of criteo rows on the device: at most 39 ids per row, so rows alone size it.  In the
+// libsvm mode (ensure_valued) it also holds values and row flags and has an nnz capacity of its
+// own, which grows on demand.
 namespace {
 struct DevCsr {
   uint64_t *off = nullptr, *idx = nullptr;
   float* lab = nullptr;
   int64_t cap = 0;  // rows
+  float* val = nullptr;  // the libsvm mode
+  uint8_t* flag = nullptr;
+  int64_t nnz_cap = 0;
+  // room for rows / nnz; growth is x1.25 and keeps the first keep_rows rows and keep_nnz
+  // features: copied on st, in order behind whatever st holds that reads or writes the old
+  // arrays, and joined before they are freed
+  int ensure_valued(int64_t rows, int64_t nnz, hipStream_t st = nullptr, int64_t keep_rows = 0,
+                    int64_t keep_nnz = 0) {
+    if (off && val && rows <= cap && nnz <= nnz_cap) return DFX_OK;
+    const int64_t nr = off && rows <= cap ? cap : std::max<int64_t>(rows + rows / 4, 16);
+    const int64_t nn = val && nnz <= nnz_cap ? nnz_cap : std::max<int64_t>(nnz + nnz / 4, 64);
+    DevCsr n;
+    DFX_HIP(hipMalloc(&n.off, (size_t)(nr + 1) * 8));
+    DFX_HIP(hipMalloc(&n.idx, (size_t)nn * 8));
+    DFX_HIP(hipMalloc(&n.lab, (size_t)nr * 4));
+    DFX_HIP(hipMalloc(&n.val, (size_t)nn * 4));
+    DFX_HIP(hipMalloc(&n.flag, (size_t)nr));
+    n.cap = nr;
+    n.nnz_cap = nn;
+    if (st && off && val && (keep_rows || keep_nnz)) {
+      const hipMemcpyKind k = hipMemcpyDeviceToDevice;
+      DFX_HIP(hipMemcpyAsync(n.off, off, (size_t)(keep_rows + 1) * 8, k, st));
+      if (keep_rows) DFX_HIP(hipMemcpyAsync(n.lab, lab, (size_t)keep_rows * 4, k, st));
+      if (keep_rows) DFX_HIP(hipMemcpyAsync(n.flag, flag, (size_t)keep_rows, k, st));
+      if (keep_nnz) DFX_HIP(hipMemcpyAsync(n.idx, idx, (size_t)keep_nnz * 8, k, st));
+      if (keep_nnz) DFX_HIP(hipMemcpyAsync(n.val, val, (size_t)keep_nnz * 4, k, st));
+    }
+    if (st) DFX_HIP(hipStreamSynchronize(st));
+    release();
+    *this = n;
+    return DFX_OK;
+  }
   int ensure(int64_t rows) {
     if (rows <= cap && off) return DFX_OK;
     release();
@@ -597,11 +553,12 @@ struct DevCsr {
     return DFX_OK;
   }
   void release() {
-    for (void* p : {(void*)off, (void*)idx, (void*)lab})
+    for (void* p : {(void*)off, (void*)idx, (void*)lab, (void*)val, (void*)flag})
       if (p) (void)hipFree(p);
     off = idx = nullptr;
-    lab = nullptr;
-    cap = 0;
+    lab = val = nullptr;
+    flag = nullptr;
+    cap = nnz_cap = 0;
   }
 };
 }  // namespace
@@ -620,6 +577,7 @@ struct dfx_textfeed {
     DevCsr csr;
     uint64_t* h_off = nullptr;  // pinned mirrors of the parsed offsets / labels / counts
     float* h_lab = nullptr;
+    uint8_t* h_flag = nullptr;  // the libsvm mode: the row flags
     int64_t mirror_cap = 0;
     int64_t *d_stat = nullptr, *h_stat = nullptr;
     int64_t rows = 0, nnz = 0;
@@ -629,13 +587,16 @@ struct dfx_textfeed {
     DevCsr csr;
     uint32_t *h_rows = nullptr, *d_rows = nullptr;  // the batch's row lists, appended
     int64_t used = 0;
+    int64_t nnz = 0;  // the libsvm mode: features gathered into the batch so far
     hipEvent_t consumed = nullptr;
   };
   std::vector<Slot> slot;
   std::vector<Ring> ring;
   DevCsr shuf;
+  int64_t shuf_nnz = 0;  // the libsvm mode: features in the shuffle buffer
   int64_t batch_rows = 0;
   int cur = -1;
+  int format = DFX_TEXT_CRITEO;
 };
 
 extern "C" int dfx_textfeed_destroy(dfx_textfeed* f) {
@@ -645,7 +606,8 @@ extern "C" int dfx_textfeed_destroy(dfx_textfeed* f) {
   (void)hipDeviceSynchronize();
   for (DevBuf& b : f->tp) b.release();
   for (auto& s : f->slot) {
-    for (void* p : {(void*)s.h_text, (void*)s.h_off, (void*)s.h_lab, (void*)s.h_stat})
+    for (void* p : {(void*)s.h_text, (void*)s.h_off, (void*)s.h_lab, (void*)s.h_stat,
+                    (void*)s.h_flag})
       if (p) (void)hipHostFree(p);
     for (void* p : {(void*)s.d_text, (void*)s.d_stat})
       if (p) (void)hipFree(p);
@@ -667,14 +629,17 @@ extern "C" int dfx_textfeed_destroy(dfx_textfeed* f) {
   return DFX_OK;
 }
 
-extern "C" int dfx_textfeed_create(dfx_ctx* ctx, int nslots, int nring, int64_t batch_rows,
-                                   int64_t shuf_rows, dfx_textfeed** out) {
+extern "C" int dfx_textfeed_create_fmt(dfx_ctx* ctx, int nslots, int nring, int64_t batch_rows,
+                                       int64_t shuf_rows, int format, dfx_textfeed** out) {
   DFX_CHECK_ARG(ctx && out && nslots >= 2 && nslots <= 8 && nring >= 2 && nring <= 8 &&
-                    batch_rows > 0 && batch_rows < (1ll << 31) && shuf_rows >= 0,
+                    batch_rows > 0 && batch_rows < (1ll << 31) && shuf_rows >= 0 &&
+                    (format == DFX_TEXT_CRITEO || format == DFX_TEXT_LIBSVM),
                 "textfeed_create: bad argument");
   DFX_HIP(hipSetDevice(ctx->c.device));
   dfx_textfeed* f = new dfx_textfeed();
   f->ctx = ctx;
+  f->format = format;
+  const bool valued = format == DFX_TEXT_LIBSVM;
   f->batch_rows = batch_rows;
   f->slot.resize((size_t)nslots);
   f->ring.resize((size_t)nring);
@@ -698,12 +663,16 @@ extern "C" int dfx_textfeed_create(dfx_ctx* ctx, int nslots, int nring, int64_t 
   for (auto& r : f->ring) {
     if (hipEventCreateWithFlags(&r.consumed, hipEventDisableTiming) != hipSuccess)
       return fail("event");
-    if (r.csr.ensure(batch_rows) != DFX_OK) return fail("device batch");
+    if ((valued ? r.csr.ensure_valued(batch_rows, batch_rows * kCols)
+                : r.csr.ensure(batch_rows)) != DFX_OK)
+      return fail("device batch");
     if (hipHostMalloc(&r.h_rows, (size_t)batch_rows * 4, hipHostMallocDefault) != hipSuccess ||
         hipMalloc(&r.d_rows, (size_t)batch_rows * 4) != hipSuccess)
       return fail("row lists");
   }
-  if (shuf_rows > 0 && f->shuf.ensure(shuf_rows) != DFX_OK) return fail("shuffle buffer");
+  if (shuf_rows > 0 && (valued ? f->shuf.ensure_valued(shuf_rows, shuf_rows * kCols)
+                               : f->shuf.ensure(shuf_rows)) != DFX_OK)
+    return fail("shuffle buffer");
   int rc = dfx_ctx_set_input_stream(ctx, f->stream);
   if (rc != DFX_OK) {
     dfx_textfeed_destroy(f);
@@ -713,8 +682,15 @@ extern "C" int dfx_textfeed_create(dfx_ctx* ctx, int nslots, int nring, int64_t 
   return DFX_OK;
 }
 
+extern "C" int dfx_textfeed_create(dfx_ctx* ctx, int nslots, int nring, int64_t batch_rows,
+                                   int64_t shuf_rows, dfx_textfeed** out) {
+  return dfx_textfeed_create_fmt(ctx, nslots, nring, batch_rows, shuf_rows, DFX_TEXT_CRITEO, out);
+}
+
 #define DFX_FEED_SLOT(f, s, what) \
   DFX_CHECK_ARG((f) && (s) >= 0 && (s) < (int)(f)->slot.size(), what ": bad slot")
+#define DFX_FEED_FMT(f, fmt, what) \
+  DFX_CHECK_ARG((f) && (f)->format == (fmt), what ": not this feed's format")
 
 extern "C" int dfx_textfeed_text(dfx_textfeed* f, int slot, int64_t bytes, char** pinned) {
   DFX_FEED_SLOT(f, slot, "textfeed_text");
@@ -754,6 +730,7 @@ static int feed_slot_rows(dfx_textfeed* f, dfx_textfeed::Slot& s, int64_t rows) 
 extern "C" int dfx_textfeed_submit(dfx_textfeed* f, int slot, int64_t nbytes, int is_train,
                                    int64_t max_rows) {
   DFX_FEED_SLOT(f, slot, "textfeed_submit");
+  DFX_FEED_FMT(f, DFX_TEXT_CRITEO, "textfeed_submit");
   auto& s = f->slot[slot];
   DFX_CHECK_ARG(nbytes >= 0 && nbytes <= s.text_cap && max_rows >= 0,
                 "textfeed_submit: more bytes than dfx_textfeed_text reserved");
@@ -797,6 +774,7 @@ extern "C" int dfx_textfeed_upload(dfx_textfeed* f, int slot, int64_t rows, int6
                                    const uint64_t* offset, const uint64_t* index,
                                    const float* label) {
   DFX_FEED_SLOT(f, slot, "textfeed_upload");
+  DFX_FEED_FMT(f, DFX_TEXT_CRITEO, "textfeed_upload");
   DFX_CHECK_ARG(rows >= 0 && nnz >= 0 && nnz <= rows * kCols && offset && (index || !nnz) &&
                     (label || !rows),
                 "textfeed_upload: bad argument");
@@ -839,6 +817,7 @@ extern "C" int dfx_textfeed_gather(dfx_textfeed* f, int src, int to_batch, const
                 "textfeed_gather: bad argument");
   DFX_CHECK_ARG(!to_batch || f->cur >= 0, "textfeed_gather: no batch begun");
   DFX_CHECK_ARG(src >= 0 || to_batch, "textfeed_gather: the shuffle buffer onto itself");
+  DFX_FEED_FMT(f, DFX_TEXT_CRITEO, "textfeed_gather");
   if (n == 0) return DFX_OK;
   DFX_HIP(hipSetDevice(f->ctx->c.device));
   const DevCsr& S = src >= 0 ? f->slot[src].csr : f->shuf;
@@ -856,8 +835,8 @@ extern "C" int dfx_textfeed_gather(dfx_textfeed* f, int src, int to_batch, const
     r.used += n;
   }
   if (src >= 0) DFX_HIP(hipStreamWaitEvent(f->stream, f->slot[src].parsed, 0));
-  DFX_TRY(gather_rows_on(&f->ctx->c, f->stream, S.off, S.idx, S.lab, rows_dev, begin, n, D.off,
-                         D.idx, D.lab, r0));
+  DFX_TRY(gather_rows_on<false>(&f->ctx->c, f->stream, S.off, S.idx, S.lab, rows_dev, begin, n,
+                                D.off, D.idx, D.lab, r0));
   if (src >= 0) DFX_HIP(hipEventRecord(f->slot[src].gathered, f->stream));
   return DFX_OK;
 }
@@ -898,5 +877,155 @@ extern "C" int dfx_textfeed_slot_batch(dfx_textfeed* f, int slot, dfx_batch* out
 extern "C" int dfx_textfeed_slot_consumed(dfx_textfeed* f, int slot) {
   DFX_FEED_SLOT(f, slot, "textfeed_slot_consumed");
   DFX_HIP(hipEventRecord(f->slot[slot].consumed, f->ctx->c.stream));
+  return DFX_OK;
+}
+
+// ---- the libsvm mode ------------------------------------------------------------------------------
+// The same slots, shuffle buffer and ring with values and row flags beside the ids.  A row has
+// any number of features, so every CSR has an nnz capacity of its own: a slot's is the caller's
+// bound for its chunk, the shuffle buffer's and a ring entry's grow on demand (x1.25) and keep
+// their contents.
+static int feed_slot_valued(dfx_textfeed::Slot& s, int64_t rows, int64_t nnz) {
+  DFX_TRY(s.csr.ensure_valued(rows, nnz));
+  if (s.csr.cap > s.mirror_cap || !s.h_off || !s.h_flag) {
+    for (void* p : {(void*)s.h_off, (void*)s.h_lab, (void*)s.h_flag})
+      if (p) DFX_HIP(hipHostFree(p));
+    s.h_off = nullptr;
+    s.h_lab = nullptr;
+    s.h_flag = nullptr;
+    s.mirror_cap = 0;
+    DFX_HIP(hipHostMalloc(&s.h_off, (size_t)(s.csr.cap + 1) * 8, hipHostMallocDefault));
+    DFX_HIP(hipHostMalloc(&s.h_lab, (size_t)s.csr.cap * 4, hipHostMallocDefault));
+    DFX_HIP(hipHostMalloc(&s.h_flag, (size_t)s.csr.cap, hipHostMallocDefault));
+    s.mirror_cap = s.csr.cap;
+  }
+  return DFX_OK;
+}
+
+extern "C" int dfx_textfeed_submit_libsvm(dfx_textfeed* f, int slot, int64_t nbytes,
+                                          int64_t max_rows, int64_t max_nnz) {
+  DFX_FEED_SLOT(f, slot, "textfeed_submit_libsvm");
+  DFX_FEED_FMT(f, DFX_TEXT_LIBSVM, "textfeed_submit_libsvm");
+  auto& s = f->slot[slot];
+  DFX_CHECK_ARG(nbytes >= 0 && nbytes <= s.text_cap && max_rows >= 0 && max_nnz >= 0,
+                "textfeed_submit_libsvm: more bytes than dfx_textfeed_text reserved");
+  DFX_HIP(hipSetDevice(f->ctx->c.device));
+  DFX_TRY(feed_slot_valued(s, max_rows, max_nnz));
+  hipStream_t up = f->up_stream;
+  DFX_HIP(hipStreamWaitEvent(up, s.gathered, 0));
+  DFX_HIP(hipStreamWaitEvent(up, s.consumed, 0));
+  if (nbytes)
+    DFX_HIP(hipMemcpyAsync(s.d_text, s.h_text, (size_t)nbytes, hipMemcpyHostToDevice, up));
+  DFX_TRY(parse_libsvm_on(&f->tp[0], &f->tp[5], up, s.d_text, nbytes, max_rows, max_nnz,
+                          s.csr.off, s.csr.idx, s.csr.val, s.csr.lab, s.csr.flag, s.d_stat));
+  // offsets, labels and row flags (13 bytes a row) for the batch planner, the counts
+  DFX_HIP(hipMemcpyAsync(s.h_off, s.csr.off, (size_t)(max_rows + 1) * 8, hipMemcpyDeviceToHost,
+                         up));
+  if (max_rows) {
+    DFX_HIP(hipMemcpyAsync(s.h_lab, s.csr.lab, (size_t)max_rows * 4, hipMemcpyDeviceToHost, up));
+    DFX_HIP(hipMemcpyAsync(s.h_flag, s.csr.flag, (size_t)max_rows, hipMemcpyDeviceToHost, up));
+  }
+  DFX_HIP(hipMemcpyAsync(s.h_stat, s.d_stat, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, up));
+  DFX_HIP(hipEventRecord(s.parsed, up));
+  return DFX_OK;
+}
+
+extern "C" int dfx_textfeed_wait_valued(dfx_textfeed* f, int slot, int64_t* stat,
+                                        const uint64_t** offset_host, const float** label_host,
+                                        const uint8_t** rowflag_host) {
+  DFX_FEED_SLOT(f, slot, "textfeed_wait_valued");
+  if (rowflag_host) *rowflag_host = f->slot[slot].h_flag;
+  return dfx_textfeed_wait(f, slot, stat, offset_host, label_host);
+}
+
+extern "C" int dfx_textfeed_upload_valued(dfx_textfeed* f, int slot, int64_t rows, int64_t nnz,
+                                          const uint64_t* offset, const uint64_t* index,
+                                          const float* value, const float* label) {
+  DFX_FEED_SLOT(f, slot, "textfeed_upload_valued");
+  DFX_FEED_FMT(f, DFX_TEXT_LIBSVM, "textfeed_upload_valued");
+  DFX_CHECK_ARG(rows >= 0 && nnz >= 0 && offset && ((index && value) || !nnz) &&
+                    (label || !rows) && offset[0] == 0 && (int64_t)offset[rows] == nnz,
+                "textfeed_upload_valued: bad argument");
+  auto& s = f->slot[slot];
+  DFX_HIP(hipSetDevice(f->ctx->c.device));
+  hipStream_t up = f->up_stream;
+  if (rows > s.csr.cap || nnz > s.csr.nnz_cap || !s.h_flag) {
+    DFX_HIP(hipStreamSynchronize(up));
+    DFX_TRY(feed_slot_valued(s, rows, nnz));
+  }
+  // after the slot's own parse (dfx_textfeed_wait joined it); the gathers wait for `parsed`
+  std::copy(offset, offset + rows + 1, s.h_off);
+  if (rows) std::copy(label, label + rows, s.h_lab);
+  for (int64_t r = 0; r < rows; ++r) {  // the row flags: a value that is not 1.0f
+    uint8_t fl = 0;
+    for (uint64_t k = offset[r]; k < offset[r + 1] && !fl; ++k) fl = value[k] != 1.f;
+    s.h_flag[r] = fl;
+  }
+  DFX_HIP(hipMemcpyAsync(s.csr.off, s.h_off, (size_t)(rows + 1) * 8, hipMemcpyHostToDevice, up));
+  if (nnz) DFX_HIP(hipMemcpyAsync(s.csr.idx, index, (size_t)nnz * 8, hipMemcpyHostToDevice, up));
+  if (nnz)
+    DFX_HIP(hipMemcpyAsync(s.csr.val, value, (size_t)nnz * 4, hipMemcpyHostToDevice, up));
+  if (rows) {
+    DFX_HIP(hipMemcpyAsync(s.csr.lab, s.h_lab, (size_t)rows * 4, hipMemcpyHostToDevice, up));
+    DFX_HIP(hipMemcpyAsync(s.csr.flag, s.h_flag, (size_t)rows, hipMemcpyHostToDevice, up));
+  }
+  DFX_HIP(hipEventRecord(s.parsed, up));
+  s.rows = rows;
+  s.nnz = nnz;
+  return DFX_OK;
+}
+
+extern "C" int dfx_textfeed_gather_valued(dfx_textfeed* f, int src, int to_batch,
+                                          const uint32_t* rows, int64_t begin, int64_t n,
+                                          int64_t r0, int64_t nnz) {
+  DFX_CHECK_ARG(f && src >= -1 && src < (int)f->slot.size() && n >= 0 && r0 >= 0 && begin >= 0 &&
+                    nnz >= 0,
+                "textfeed_gather_valued: bad argument");
+  DFX_FEED_FMT(f, DFX_TEXT_LIBSVM, "textfeed_gather_valued");
+  DFX_CHECK_ARG(!to_batch || f->cur >= 0, "textfeed_gather_valued: no batch begun");
+  DFX_CHECK_ARG(src >= 0 || to_batch, "textfeed_gather_valued: the shuffle buffer onto itself");
+  if (n == 0) return DFX_OK;
+  DFX_HIP(hipSetDevice(f->ctx->c.device));
+  const DevCsr& S = src >= 0 ? f->slot[src].csr : f->shuf;
+  DevCsr& D = to_batch ? f->ring[f->cur].csr : f->shuf;
+  int64_t& used = to_batch ? f->ring[f->cur].nnz : f->shuf_nnz;
+  DFX_CHECK_ARG(r0 + n <= D.cap, "textfeed_gather_valued: more rows than the destination holds");
+  if (r0 == 0) used = 0;
+  // the copies of a growth run on the gathers' stream: behind the gathers that filled the old
+  // arrays and, for the shuffle buffer, behind the gathers that read them
+  DFX_TRY(D.ensure_valued(D.cap, used + nnz, f->stream, r0, used));
+  used += nnz;
+  const uint32_t* rows_dev = nullptr;
+  if (rows) {
+    DFX_CHECK_ARG(to_batch, "textfeed_gather_valued: row lists go to the batch");
+    auto& r = f->ring[f->cur];
+    DFX_CHECK_ARG(r.used + n <= f->batch_rows,
+                  "textfeed_gather_valued: row lists past the batch size");
+    std::copy(rows, rows + n, r.h_rows + r.used);
+    DFX_HIP(hipMemcpyAsync(r.d_rows + r.used, r.h_rows + r.used, (size_t)n * 4,
+                           hipMemcpyHostToDevice, f->stream));
+    rows_dev = r.d_rows + r.used;
+    r.used += n;
+  }
+  if (src >= 0) DFX_HIP(hipStreamWaitEvent(f->stream, f->slot[src].parsed, 0));
+  DFX_TRY(gather_rows_on<true>(&f->ctx->c, f->stream, S.off, S.idx, S.lab, rows_dev, begin, n,
+                               D.off, D.idx, D.lab, r0, S.val, D.val, S.flag, D.flag));
+  if (src >= 0) DFX_HIP(hipEventRecord(f->slot[src].gathered, f->stream));
+  return DFX_OK;
+}
+
+extern "C" int dfx_textfeed_batch_end_valued(dfx_textfeed* f, int64_t rows, int64_t nnz,
+                                             int valued, dfx_batch* out) {
+  DFX_TRY(dfx_textfeed_batch_end(f, rows, nnz, out));
+  DFX_FEED_FMT(f, DFX_TEXT_LIBSVM, "textfeed_batch_end_valued");
+  out->value = valued ? f->ring[f->cur].csr.val : nullptr;
+  return DFX_OK;
+}
+
+extern "C" int dfx_textfeed_slot_batch_valued(dfx_textfeed* f, int slot, int valued,
+                                              dfx_batch* out) {
+  DFX_TRY(dfx_textfeed_slot_batch(f, slot, out));
+  DFX_FEED_FMT(f, DFX_TEXT_LIBSVM, "textfeed_slot_batch_valued");
+  out->value = valued ? f->slot[slot].csr.val : nullptr;
   return DFX_OK;
 }

@@ -14,34 +14,58 @@ static double Seconds() {
       .count();
 }
 
-DeviceTextFeed::DeviceTextFeed(dfx_ctx* ctx, size_t batch_size, size_t shuf_buf)
-    : batch_size_(batch_size ? batch_size : 1), shuf_buf_(shuf_buf) {
-  DfxCheck(dfx_textfeed_create(ctx, kSlots, kRing, (int64_t)batch_size_, (int64_t)shuf_buf_, &h_),
-           "dfx_textfeed_create");
+DeviceTextFeed::DeviceTextFeed(dfx_ctx* ctx, size_t batch_size, size_t shuf_buf,
+                               const std::string& format)
+    : batch_size_(batch_size ? batch_size : 1), shuf_buf_(shuf_buf), libsvm_(format == "libsvm") {
+  DfxCheck(dfx_textfeed_create_fmt(ctx, kSlots, kRing, (int64_t)batch_size_, (int64_t)shuf_buf_,
+                                   libsvm_ ? DFX_TEXT_LIBSVM : DFX_TEXT_CRITEO, &h_),
+           "dfx_textfeed_create_fmt");
 }
 
 DeviceTextFeed::~DeviceTextFeed() {
   if (h_) dfx_textfeed_destroy(h_);
 }
 
-// src -> dst over up to nthreads threads; returns the number of '\n' bytes copied
-static size_t CopyCountLines(char* dst, const char* src, size_t bytes, int nthreads) {
-  auto part = [](char* d, const char* s, size_t n) {
+// src -> dst over up to nthreads threads; returns the number of '\n' bytes copied; blanks
+// (libsvm): also counts the ' ' and '\t' bytes, which bound the chunk's features
+static size_t CopyCountLines(char* dst, const char* src, size_t bytes, int nthreads,
+                             size_t* blanks = nullptr) {
+  std::vector<size_t> nblank(std::max(nthreads, 1), 0);
+  size_t* const nb = blanks ? nblank.data() : nullptr;
+  auto part = [nb](char* d, const char* s, size_t n, int t = 0) {
     std::memcpy(d, s, n);
     size_t c = 0;
+    if (nb) {
+      size_t b = 0;
+      for (const char *p = d, *e = d + n; p < e; ++p) {
+        c += *p == '\n';
+        b += (*p == ' ') | (*p == '\t');
+      }
+      nb[t] = b;
+      return c;
+    }
     for (const char *p = d, *e = d + n; p < e; ++p, ++c) {
       p = static_cast<const char*>(std::memchr(p, '\n', e - p));
       if (!p) break;
     }
     return c;
   };
+  struct Sum {  // the blanks of the parts, on every way out
+    std::vector<size_t>& v;
+    size_t* out;
+    ~Sum() {
+      if (!out) return;
+      *out = 0;
+      for (size_t x : v) *out += x;
+    }
+  } sum{nblank, blanks};
   const int T = (int)std::min<size_t>(std::max(nthreads, 1), 1 + bytes / (1 << 20));
   if (T <= 1) return part(dst, src, bytes);
   std::vector<size_t> cnt(T, 0);
   std::vector<std::thread> th;
   for (int t = 0; t < T; ++t) {
     const size_t a = bytes * t / T, b = bytes * (t + 1) / T;
-    th.emplace_back([&, t, a, b]() { cnt[t] = part(dst + a, src + a, b - a); });
+    th.emplace_back([&, t, a, b]() { cnt[t] = part(dst + a, src + a, b - a, t); });
   }
   size_t total = 0;
   for (int t = 0; t < T; ++t) {
@@ -58,10 +82,12 @@ DeviceBatchReader::DeviceBatchReader(DeviceTextFeed* feed, const std::string& pa
     : f_(feed->h()),
       reader_(path, format, part, nparts, chunk_bytes, nthreads, 0),
       train_(format != "criteo_test"),
+      libsvm_(format == "libsvm"),
       batch_size_(batch_size),
       nthreads_(nthreads < 1 ? 1 : nthreads) {
-  DFX_HOST_CHECK(format == "criteo" || format == "criteo_test",
-                 "the device reader parses criteo and criteo_test, not " + format);
+  DFX_HOST_CHECK(format == "criteo" || format == "criteo_test" || format == "libsvm",
+                 "the device reader parses criteo, criteo_test and libsvm, not " + format);
+  DFX_HOST_CHECK(libsvm_ == feed->libsvm(), "the text feed was created for another format");
   DFX_HOST_CHECK(batch_size <= feed->batch_size() && shuf_buf <= feed->shuf_buf(),
                  "batch or shuffle buffer larger than the text feed's");
   if (batch_size_) {
@@ -71,6 +97,7 @@ DeviceBatchReader::DeviceBatchReader(DeviceTextFeed* feed, const std::string& pa
           return FetchChunk(rows, off, lab);
         },
         [this](const GatherOp& op) {
+          if (libsvm_) return Gather(op);
           const int src = op.src == GatherOp::kShuffle ? -1 : seq_slot_[op.src];
           DfxCheck(dfx_textfeed_gather(f_, src, op.to_batch ? 1 : 0,
                                        op.rows.empty() ? nullptr : op.rows.data(),
@@ -119,11 +146,12 @@ void DeviceBatchReader::Load() {
     char* dst = nullptr;
     DfxCheck(dfx_textfeed_text(f_, slot, (int64_t)size, &dst), "dfx_textfeed_text");
     const double t0 = Seconds();
-    const size_t nl = CopyCountLines(dst, data, size, nthreads_);
+    size_t blanks = 0;
+    const size_t nl = CopyCountLines(dst, data, size, nthreads_, libsvm_ ? &blanks : nullptr);
     {
       std::lock_guard<std::mutex> lk(mu_);
       times_.copy += Seconds() - t0;
-      filled_.push_back(Filled{slot, size, nl});
+      filled_.push_back(Filled{slot, size, nl, blanks});
     }
     cv_.notify_all();
   }
@@ -141,10 +169,16 @@ void DeviceBatchReader::SubmitFilled(bool wait) {
     take.swap(filled_);
   }
   for (const Filled& c : take) {
-    // rows <= lines <= newlines: whole lines, the last one terminated (TextReader::NextRaw)
-    DfxCheck(dfx_textfeed_submit(f_, c.slot, (int64_t)c.bytes, train_ ? 1 : 0,
-                                 (int64_t)c.newlines),
-             "dfx_textfeed_submit");
+    // rows <= lines <= newlines: whole lines, the last one terminated (TextReader::NextRaw);
+    // libsvm: a feature follows a blank
+    if (libsvm_)
+      DfxCheck(dfx_textfeed_submit_libsvm(f_, c.slot, (int64_t)c.bytes, (int64_t)c.newlines,
+                                          (int64_t)c.blanks),
+               "dfx_textfeed_submit_libsvm");
+    else
+      DfxCheck(dfx_textfeed_submit(f_, c.slot, (int64_t)c.bytes, train_ ? 1 : 0,
+                                   (int64_t)c.newlines),
+               "dfx_textfeed_submit");
     submitted_.push_back(c);
   }
 }
@@ -170,7 +204,12 @@ bool DeviceBatchReader::FetchChunk(size_t* rows, const uint64_t** off, const flo
   submitted_.pop_front();
   int64_t stat[4];
   const double t0 = Seconds();
-  DfxCheck(dfx_textfeed_wait(f_, c.slot, stat, off, lab), "dfx_textfeed_wait");
+  chunk_flag_ = nullptr;
+  if (libsvm_)
+    DfxCheck(dfx_textfeed_wait_valued(f_, c.slot, stat, off, lab, &chunk_flag_),
+             "dfx_textfeed_wait_valued");
+  else
+    DfxCheck(dfx_textfeed_wait(f_, c.slot, stat, off, lab), "dfx_textfeed_wait");
   times_.wait_parse += Seconds() - t0;
   SubmitFilled(false);  // slots filled meanwhile: their parses run beside this chunk's batches
   *rows = (size_t)stat[0];
@@ -180,11 +219,24 @@ bool DeviceBatchReader::FetchChunk(size_t* rows, const uint64_t** off, const flo
     DfxCheck(dfx_textfeed_text(f_, c.slot, (int64_t)c.bytes, &text), "dfx_textfeed_text");
     reader_.ParseChunk(text, c.bytes, &host_blk_);
     static_assert(sizeof(size_t) == sizeof(uint64_t), "size_t offsets");
-    DfxCheck(dfx_textfeed_upload(f_, c.slot, (int64_t)host_blk_.Size(),
-                                 (int64_t)host_blk_.index.size(),
-                                 reinterpret_cast<const uint64_t*>(host_blk_.offset.data()),
-                                 host_blk_.index.data(), host_blk_.label.data()),
-             "dfx_textfeed_upload");
+    if (libsvm_) {
+      DfxCheck(dfx_textfeed_upload_valued(
+                   f_, c.slot, (int64_t)host_blk_.Size(), (int64_t)host_blk_.index.size(),
+                   reinterpret_cast<const uint64_t*>(host_blk_.offset.data()),
+                   host_blk_.index.data(), host_blk_.value.data(), host_blk_.label.data()),
+               "dfx_textfeed_upload_valued");
+      host_flag_.assign(host_blk_.Size(), 0);
+      for (size_t r = 0; r < host_blk_.Size(); ++r)
+        for (size_t k = host_blk_.offset[r]; k < host_blk_.offset[r + 1] && !host_flag_[r]; ++k)
+          host_flag_[r] = host_blk_.value[k] != 1.f;
+      chunk_flag_ = host_flag_.data();
+    } else {
+      DfxCheck(dfx_textfeed_upload(f_, c.slot, (int64_t)host_blk_.Size(),
+                                   (int64_t)host_blk_.index.size(),
+                                   reinterpret_cast<const uint64_t*>(host_blk_.offset.data()),
+                                   host_blk_.index.data(), host_blk_.label.data()),
+               "dfx_textfeed_upload");
+    }
     *rows = host_blk_.Size();
     *off = reinterpret_cast<const uint64_t*>(host_blk_.offset.data());
     *lab = host_blk_.label.data();
@@ -192,7 +244,42 @@ bool DeviceBatchReader::FetchChunk(size_t* rows, const uint64_t** off, const flo
   cur_slot_ = c.slot;
   seq_slot_.push_back(c.slot);
   chunk_lab_ = *lab;
+  chunk_off_ = *off;
+  chunk_rows_ = *rows;
   return true;
+}
+
+// libsvm: the copy's nnz from the mirrored row lengths, the flags carried along
+void DeviceBatchReader::Gather(const GatherOp& op) {
+  const bool from_shuf = op.src == GatherOp::kShuffle;
+  auto len = [&](size_t j) {
+    return from_shuf ? (size_t)shuf_len_[j] : (size_t)(chunk_off_[j + 1] - chunk_off_[j]);
+  };
+  auto flag = [&](size_t j) { return from_shuf ? shuf_flag_[j] : chunk_flag_[j]; };
+  if (op.r0 == 0) {
+    if (op.to_batch) {
+      batch_valued_ = false;
+    } else {
+      shuf_len_.clear();
+      shuf_flag_.clear();
+    }
+  }
+  size_t nnz = 0;
+  for (size_t i = 0; i < op.n; ++i) {
+    const size_t j = op.rows.empty() ? op.begin + i : op.rows[i];
+    nnz += len(j);
+    if (op.to_batch) {
+      batch_valued_ = batch_valued_ || flag(j);
+    } else {
+      shuf_len_.push_back((uint32_t)len(j));
+      shuf_flag_.push_back(flag(j));
+    }
+  }
+  DfxCheck(dfx_textfeed_gather_valued(f_, from_shuf ? -1 : seq_slot_[op.src], op.to_batch ? 1 : 0,
+                                      op.rows.empty() ? nullptr : op.rows.data(),
+                                      (int64_t)op.begin, (int64_t)op.n, (int64_t)op.r0,
+                                      (int64_t)nnz),
+           "dfx_textfeed_gather_valued");
 }
 
 bool DeviceBatchReader::Next() {
@@ -203,7 +290,14 @@ bool DeviceBatchReader::Next() {
     do {
       if (!FetchChunk(&rows, &off, &lab)) return false;
     } while (rows == 0);
-    DfxCheck(dfx_textfeed_slot_batch(f_, cur_slot_, &batch_), "dfx_textfeed_slot_batch");
+    if (libsvm_) {
+      bool valued = false;
+      for (size_t r = 0; r < chunk_rows_ && !valued; ++r) valued = chunk_flag_[r];
+      DfxCheck(dfx_textfeed_slot_batch_valued(f_, cur_slot_, valued ? 1 : 0, &batch_),
+               "dfx_textfeed_slot_batch_valued");
+    } else {
+      DfxCheck(dfx_textfeed_slot_batch(f_, cur_slot_, &batch_), "dfx_textfeed_slot_batch");
+    }
     slot_batch_ = true;
     return true;
   }
@@ -211,9 +305,15 @@ bool DeviceBatchReader::Next() {
   DfxCheck(dfx_textfeed_batch_begin(f_), "dfx_textfeed_batch_begin");
   times_.wait_step += Seconds() - t0;
   size_t rows, nnz;
+  batch_valued_ = false;
   if (!planner_->Next(&rows, &nnz)) return false;
-  DfxCheck(dfx_textfeed_batch_end(f_, (int64_t)rows, (int64_t)nnz, &batch_),
-           "dfx_textfeed_batch_end");
+  if (libsvm_)
+    DfxCheck(dfx_textfeed_batch_end_valued(f_, (int64_t)rows, (int64_t)nnz, batch_valued_ ? 1 : 0,
+                                           &batch_),
+             "dfx_textfeed_batch_end_valued");
+  else
+    DfxCheck(dfx_textfeed_batch_end(f_, (int64_t)rows, (int64_t)nnz, &batch_),
+             "dfx_textfeed_batch_end");
   slot_batch_ = false;
   return true;
 }

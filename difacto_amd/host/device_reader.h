@@ -1,4 +1,4 @@
-// device_reader.h — Criteo minibatches formed on the device from raw text.
+// device_reader.h — Criteo and libsvm minibatches formed on the device from raw text.
 //
 // The host reader (reader.h) tokenises, hashes and copies every row on CPU threads.  Here the
 // host's per-byte work is one copy of the raw chunk into pinned memory; the device parses it
@@ -15,7 +15,16 @@
 //
 // A chunk the device flags (needs_host: the forms listed in include/difacto_amd.h) is parsed
 // by ParseCriteo on the host and uploaded into the same device arrays; FallbackChunks counts
-// them.  criteo and criteo_test only.
+// them.
+//
+// libsvm (dfx_parse_libsvm, the feed's libsvm mode): rows have any number of features and carry
+// values.  The loader also counts the chunk's blanks, which bound its features; the reader
+// mirrors row lengths and the parser's row flags (a row holding a value that is not 1.0f)
+// through the GatherOps it carries out, chunk -> shuffle buffer -> batch, so it knows every
+// copy's nnz (the feed sizes its arrays by it) and hands a batch out with values iff one of its
+// rows is flagged: BatchReader::Next's all-ones test (batch_reader.cc:71-73) with no device
+// read-back.  A flagged chunk goes through ParseLibSVM and is uploaded values included.
+// criteo, criteo_test and libsvm only.
 #ifndef DIFACTO_AMD_HOST_DEVICE_READER_H_
 #define DIFACTO_AMD_HOST_DEVICE_READER_H_
 
@@ -38,17 +47,21 @@ namespace difacto {
 class DeviceTextFeed {
  public:
   static constexpr int kSlots = 3, kRing = 3;
-  DeviceTextFeed(dfx_ctx* ctx, size_t batch_size, size_t shuf_buf);
+  /** format: "libsvm" takes the feed's libsvm mode, anything else the Criteo mode */
+  DeviceTextFeed(dfx_ctx* ctx, size_t batch_size, size_t shuf_buf,
+                 const std::string& format = "criteo");
   ~DeviceTextFeed();
   DeviceTextFeed(const DeviceTextFeed&) = delete;
   DeviceTextFeed& operator=(const DeviceTextFeed&) = delete;
   dfx_textfeed* h() const { return h_; }
   size_t batch_size() const { return batch_size_; }
   size_t shuf_buf() const { return shuf_buf_; }
+  bool libsvm() const { return libsvm_; }
 
  private:
   dfx_textfeed* h_ = nullptr;
   size_t batch_size_, shuf_buf_;
+  bool libsvm_;
 };
 
 class DeviceBatchReader {
@@ -82,15 +95,16 @@ class DeviceBatchReader {
  private:
   struct Filled {
     int slot;
-    size_t bytes, newlines;
+    size_t bytes, newlines, blanks;
   };
+  void Gather(const GatherOp& op);  // libsvm: one copy of the plan, lengths and flags mirrored
   void Load();                  // the loader thread
   void SubmitFilled(bool wait); // queue the parses of the filled slots
   bool FetchChunk(size_t* rows, const uint64_t** off, const float** lab);
   void ReleaseChunk();
   dfx_textfeed* f_;
   TextReader reader_;
-  bool train_;
+  bool train_, libsvm_;
   size_t batch_size_;
   int nthreads_;
   std::unique_ptr<BatchPlanner> planner_;
@@ -105,6 +119,14 @@ class DeviceBatchReader {
   std::vector<int> seq_slot_;       // chunk sequence number -> slot
   RowBlockContainer<feaid_t> host_blk_;  // a flagged chunk, parsed on the host
   const float* chunk_lab_ = nullptr;
+  // libsvm: the current chunk's offsets and row flags, the shuffle buffer's row lengths and
+  // flags, whether a flagged row went into the batch being formed
+  const uint64_t* chunk_off_ = nullptr;
+  const uint8_t* chunk_flag_ = nullptr;
+  size_t chunk_rows_ = 0;
+  std::vector<uint8_t> host_flag_, shuf_flag_;
+  std::vector<uint32_t> shuf_len_;
+  bool batch_valued_ = false;
   size_t fallback_ = 0;
   Times times_;  // copy: written by the loader thread, read after it has ended or between chunks
   dfx_batch batch_{};

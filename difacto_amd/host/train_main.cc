@@ -5,7 +5,7 @@
 //                   [batch_size=100] [shuffle=10] [neg_sampling=1] [max_num_epochs=20]
 //                   [num_jobs_per_epoch=10] [stop_rel_objv=1e-5] [model_in=F] [model_out=F]
 //                   [load_epoch=-1] [has_aux=0] [task=0|2] [pred_out=F] [pred_prob=1]
-//                   [fused=1] [nthreads=8] [parse=host|device] [cache=none|device]
+//                   [fused=1] [nthreads=8] [parse=host|device|auto] [cache=none|device]
 //                   [cache_mb=16384] [V_dim=..] [lr=..] [l1=..] ...  (SGDUpdaterParam)
 //
 // parse=device (data_format=criteo|criteo_test, the single-GPU fused path: training, data_val
@@ -14,6 +14,12 @@
 // device_reader.h) — the same batches, so the same results, as the default parse=host.  With
 // any other format, fused=0 or the sharded runs it is an error (exit 2).  A chunk the device
 // hands back (needs_host) is parsed by the host; their count is printed per epoch if non-zero.
+//
+// parse=auto takes the device parser when the format has one (criteo, criteo_test: as above;
+// libsvm: dfx_parse_libsvm, values included, the batches valued exactly where BatchReader's
+// are) and the run is the single-GPU fused path, else the host reader; one line at the start
+// says which and why, e.g. "parse: device (libsvm)" or "parse: host (exchange=split)".
+// parse=device keeps its contract: Criteo formats only, anything else is an error.
 //
 // cache=device (the single-GPU fused path with either parse and any data_format, training and
 // data_val validation; the sharded exchange=a2a runs): the first epoch the run executes (after
@@ -77,7 +83,7 @@ struct Param {
   std::string exchange = "a2a";  // a2a: GpuShardedStore (KVStoreDist); split: GpuSplitLearner
   bool has_aux = false, pred_prob = true;
   double stop_rel_objv = 1e-5;
-  std::string parse = "host";  // device: DeviceBatchReader (criteo text parsed on the GPU)
+  std::string parse = "host";  // device: DeviceBatchReader (text parsed on the GPU); auto
   std::string cache = "none";  // device: formed batches kept in HBM, replayed after the first epoch
   int64_t cache_mb = 16384;    // its budget (per shard)
 };
@@ -538,9 +544,27 @@ int main(int argc, char** argv) {
   }
   const char* ws = std::getenv("WORLD_SIZE");
   const bool sharded = P.shards != 0 || (ws && std::atoi(ws) > 1);
-  if (P.parse != "host" && P.parse != "device") {
-    std::fprintf(stderr, "parse must be host or device\n");
+  if (P.parse != "host" && P.parse != "device" && P.parse != "auto") {
+    std::fprintf(stderr, "parse must be host, device or auto\n");
     return 2;
+  }
+  if (P.parse == "auto") {  // the device parser where there is one, and a line saying which
+    bool fused = true;
+    for (const auto& kv : rest)
+      if (kv.first == "fused") fused = std::stoi(kv.second) != 0;
+    std::string why;
+    if (sharded)
+      why = P.exchange == "split" ? "exchange=split" : "a sharded run";
+    else if (!fused)
+      why = "fused=0";
+    else if (P.data_format != "criteo" && P.data_format != "criteo_test" &&
+             P.data_format != "libsvm")
+      why = "data_format=" + P.data_format;
+    const bool dev = why.empty();
+    std::printf("parse: %s (%s)\n", dev ? "device" : "host",
+                dev ? P.data_format.c_str() : why.c_str());
+    std::fflush(stdout);
+    P.parse = dev ? "auto-device" : "host";
   }
   if (P.parse == "device") {  // no silent fall-back to the host reader
     bool fused = true;
@@ -582,8 +606,9 @@ int main(int argc, char** argv) {
   if (!fused_given) rest.push_back({"fused", "1"});
   GpuSGDLearner learner(rest);
   std::unique_ptr<DeviceTextFeed> feed;
-  if (P.parse == "device")
-    feed.reset(new DeviceTextFeed(learner.context(), P.batch_size, P.batch_size * P.shuffle));
+  if (P.parse == "device" || P.parse == "auto-device")
+    feed.reset(new DeviceTextFeed(learner.context(), P.batch_size, P.batch_size * P.shuffle,
+                                  P.data_format));
   // (declared after the learner and the feed: destroyed, joining the context, before them)
   std::unique_ptr<DeviceBatchCache> cache;
   if (P.cache == "device" && P.task != 2)

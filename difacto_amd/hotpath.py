@@ -436,6 +436,53 @@ def parse_criteo(ctx, data, is_train=True):
     return RowBlock(u64(offs[:rows + 1]), u64(ids[:nnz]), None, labels[:rows].cpu().numpy()), False
 
 
+def parse_libsvm(ctx, data):
+    """libsvm text (whole lines, bytes) parsed on the device (dfx_parse_libsvm, replacing the
+    host reader's ParseLibSVM) -> (offs, ids, vals, labels, rowflag, stat): numpy arrays (uint64
+    offsets and ids, float32 values and labels, uint8 row flags: 1 iff the row holds a value
+    whose bits are not 1.0f's) and stat = {rows, nnz, needs_host}.  needs_host: the chunk holds
+    a form the device leaves to the host parser (include/difacto_amd.h lists them); the arrays
+    are then None."""
+    data = bytes(data)
+    max_rows = data.count(b"\n") + 1
+    max_nnz = data.count(b" ") + data.count(b"\t") + 1  # a feature follows a blank
+    dev = ctx.device
+    text = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev) if data else None
+    offs = torch.empty(max_rows + 1, dtype=torch.int64, device=dev)
+    ids = torch.empty(max_nnz, dtype=torch.int64, device=dev)
+    vals = torch.empty(max_nnz, dtype=torch.float32, device=dev)
+    labels = torch.empty(max_rows, dtype=torch.float32, device=dev)
+    rowflag = torch.empty(max_rows, dtype=torch.uint8, device=dev)
+    stat_dev = torch.empty(4, dtype=torch.int64, device=dev)
+    check(_lib.lib().dfx_parse_libsvm(ctx.h, _p(text), len(data), max_rows, max_nnz, _p(offs),
+                                      _p(ids), _p(vals), _p(labels), _p(rowflag), _p(stat_dev)))
+    st = (ctypes.c_int64 * 4)()
+    check(_lib.lib().dfx_parse_criteo_wait(ctx.h, _p(stat_dev), st))
+    rows, nnz = st[0], st[1]
+    stat = {"rows": rows, "nnz": nnz, "needs_host": bool(st[2])}
+    if stat["needs_host"]:
+        return None, None, None, None, None, stat
+    return (u64(offs[:rows + 1]), u64(ids[:nnz]), vals[:nnz].cpu().numpy(),
+            labels[:rows].cpu().numpy(), rowflag[:rows].cpu().numpy(), stat)
+
+
+def gather_rows_valued(ctx, src, rows=None, begin=0, n=None, dst=None, r0=0):
+    """dfx_gather_rows_valued (the host reader's GatherRows with values and row flags) on device
+    tensors.  src / dst: dicts of offs, ids (int64 holding the uint64 bits), vals (float32 or
+    None), labels (float32), rowflag (uint8 or None); rows: an int32 device tensor holding the
+    uint32 row list, or None for the range [begin, begin + n).  Appends at row r0 of dst (the
+    caller sizes it) and joins the input stream."""
+    if rows is not None:
+        n = rows.numel()
+    check(_lib.lib().dfx_gather_rows_valued(
+        ctx.h, _p(src["offs"]), _p(src["ids"]), _p(src.get("vals")), _p(src["labels"]),
+        _p(src.get("rowflag")), _p(rows), int(begin), int(n), _p(dst["offs"]), _p(dst["ids"]),
+        _p(dst.get("vals")), _p(dst["labels"]), _p(dst.get("rowflag")), int(r0)))
+    stat_dev = torch.zeros(4, dtype=torch.int64, device=ctx.device)
+    st = (ctypes.c_int64 * 4)()
+    check(_lib.lib().dfx_parse_criteo_wait(ctx.h, _p(stat_dev), st))
+
+
 # main-stream phases of dfx_train_step (the Localizer runs on its own lane; "localize" is
 # the part of it the main stream waits for)
 PHASES = ("localize", "probe_pull", "feacnt", "forward", "eval_auc", "backward_update", "initv")

@@ -179,6 +179,42 @@ int dfx_gather_rows(dfx_ctx* ctx, const uint64_t* src_offset, const uint64_t* sr
                     const float* src_label, const uint32_t* rows_dev, int64_t begin, int64_t n,
                     uint64_t* dst_offset, uint64_t* dst_index, float* dst_label, int64_t r0);
 
+/* ---- libsvm text on the device (difacto_amd/csrc/libsvmparse.hip) ------------------------
+ * dfx_parse_libsvm replaces the libsvm branch of TextReader::ParseChunk (the host reader's
+ * ParseLibSVM, difacto_amd/host/reader.cc; libsvm is the reference's default data_format,
+ * sgd_param.h:57) for a chunk of whole lines text_dev[0, nbytes) in device memory:
+ * offset[rows + 1] (offset[0] == 0), index[nnz], value[nnz] (always written: 1.0f for a bare
+ * id, as ParseLibSVM does), label[rows], and rowflag[rows] (bytes): 1 iff the row holds a value
+ * whose bits are not 1.0f's, so a batch has values iff one of its rows is flagged
+ * (BatchReader::Next's all-ones test, batch_reader.cc:71-73, with no read-back).
+ * Numbers are converted by csrc/strtof.h: glibc strtof's correctly rounded result bit for bit
+ * inside its fast grammar  [+-]? (digits ('.' digits?)? | '.' digits) ([eE] [+-]? digits{1,3})?
+ * with at most 19 digits after the leading zeros and |exponent - fraction digits| <= 27.
+ * Parsed on the device: lines  label (blank+ feature)* blank* '\n',  blank = ' ' | '\t',
+ * blanks before the label allowed, feature = digits | digits ':' number, label and number in
+ * the fast grammar; an id is any run of digits and saturates to 2^64 - 1 as strtoull does;
+ * rows with no feature.  The result equals ParseLibSVM's byte for byte, or the chunk is
+ * flagged: stat_dev[4] (device) = {rows, nnz, needs_host, overflow}, as dfx_parse_criteo's.
+ * needs_host == 1: the outputs are undefined and the host parses the chunk.  Only these forms
+ * may raise it: a label or value outside the fast grammar; a feature that is not digits or
+ * digits ':' number; a token longer than 64 bytes; a '\r' byte anywhere; an empty or
+ * blank-only line; a last byte that is not '\n'.
+ * overflow == 1: the chunk needs more than max_rows rows or max_nnz features; rows / nnz hold
+ * the needed counts and nothing was written.  No byte outside the text is read, nothing past
+ * the capacities is written.  nbytes >= 2^31 is DFX_ERR_ARG.  Asynchronous on the context's
+ * input stream; dfx_parse_criteo_wait serves as the wait.
+ * dfx_gather_rows_valued is dfx_gather_rows with the values and the row flags gathered
+ * alongside.  src_value NULL: the source is binary and reads as ones (GatherRows's rule);
+ * dst_value NULL: values are dropped; src_rowflag NULL: flags 0; dst_rowflag NULL: none kept. */
+int dfx_parse_libsvm(dfx_ctx* ctx, const char* text_dev, int64_t nbytes, int64_t max_rows,
+                     int64_t max_nnz, uint64_t* offset, uint64_t* index, float* value,
+                     float* label, uint8_t* rowflag, int64_t* stat_dev);
+int dfx_gather_rows_valued(dfx_ctx* ctx, const uint64_t* src_offset, const uint64_t* src_index,
+                           const float* src_value, const float* src_label,
+                           const uint8_t* src_rowflag, const uint32_t* rows_dev, int64_t begin,
+                           int64_t n, uint64_t* dst_offset, uint64_t* dst_index, float* dst_value,
+                           float* dst_label, uint8_t* dst_rowflag, int64_t r0);
+
 /* The text feeder: raw text to device batches (src/reader/reader.h:18-55 + batch_reader.cc
  * with the parsing and the row copies on the device).  nslots pinned text slots, a loader
  * stream that becomes the context's input stream, one parsed chunk (device CSR + pinned
@@ -213,6 +249,34 @@ int dfx_textfeed_batch_end(dfx_textfeed* f, int64_t rows, int64_t nnz, dfx_batch
 int dfx_textfeed_consumed(dfx_textfeed* f);
 int dfx_textfeed_slot_batch(dfx_textfeed* f, int slot, dfx_batch* out);
 int dfx_textfeed_slot_consumed(dfx_textfeed* f, int slot);
+/* The libsvm mode (dfx_textfeed_create_fmt with DFX_TEXT_LIBSVM; dfx_textfeed_create is the
+ * DFX_TEXT_CRITEO mode, whose entry points above reject a libsvm feed and the other way round).
+ * Every CSR also holds values and row flags (dfx_parse_libsvm) and has an nnz capacity of its
+ * own: a slot's is the submit's max_nnz (the chunk's blanks bound its features), the shuffle
+ * buffer's and a ring entry's grow on demand (x 1.25) keeping their contents.
+ *   dfx_textfeed_submit_libsvm  upload + dfx_parse_libsvm + the copies back, asynchronous
+ *   dfx_textfeed_wait_valued    dfx_textfeed_wait, and the pinned row flags
+ *   dfx_textfeed_upload_valued  a chunk the host parsed, values included; flags from the values
+ *   dfx_textfeed_gather_valued  dfx_textfeed_gather with values and flags; nnz: the features
+ *                          the copy appends (the caller knows the row lengths)
+ *   dfx_textfeed_batch_end_valued / _slot_batch_valued   valued == 0 hands out value == NULL:
+ *                          the caller found no flagged row in the batch (batch_reader.cc:71-73) */
+enum { DFX_TEXT_CRITEO = 0, DFX_TEXT_LIBSVM = 1 };
+int dfx_textfeed_create_fmt(dfx_ctx* ctx, int nslots, int nring, int64_t batch_rows,
+                            int64_t shuf_rows, int format, dfx_textfeed** out);
+int dfx_textfeed_submit_libsvm(dfx_textfeed* f, int slot, int64_t nbytes, int64_t max_rows,
+                               int64_t max_nnz);
+int dfx_textfeed_wait_valued(dfx_textfeed* f, int slot, int64_t* stat,
+                             const uint64_t** offset_host, const float** label_host,
+                             const uint8_t** rowflag_host);
+int dfx_textfeed_upload_valued(dfx_textfeed* f, int slot, int64_t rows, int64_t nnz,
+                               const uint64_t* offset, const uint64_t* index, const float* value,
+                               const float* label);
+int dfx_textfeed_gather_valued(dfx_textfeed* f, int src, int to_batch, const uint32_t* rows,
+                               int64_t begin, int64_t n, int64_t r0, int64_t nnz);
+int dfx_textfeed_batch_end_valued(dfx_textfeed* f, int64_t rows, int64_t nnz, int valued,
+                                  dfx_batch* out);
+int dfx_textfeed_slot_batch_valued(dfx_textfeed* f, int slot, int valued, dfx_batch* out);
 
 /* ---- device batch cache (difacto_amd/csrc/batchcache.hip) --------------------------------
  * Formed batches kept in device memory, so that every epoch after the first replays them with

@@ -1,0 +1,271 @@
+"""libsvm text parsed and batched on the device (difacto_amd/csrc/libsvmparse.hip, the feed's
+libsvm mode in textparse.hip, difacto_amd/host/device_reader.cc) against the host reader, which
+is the yardstick everywhere: ParseLibSVM, GatherRows, BatchReader and TextReader of
+difacto_amd/host/reader.cc, and libc's strtof / strtoull through ctypes.  Every comparison is
+exact.  The C++ driver is tests/host/libsvmparse_tests.cc (build/libsvmparse_tests)."""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIN = os.path.join(ROOT, "build", "libsvmparse_tests")
+TRAIN_BIN = os.path.join(ROOT, "build", "dfx_train")
+GEN_BIN = os.path.join(ROOT, "build", "gen_libsvm")
+RCV1 = os.path.join(ROOT, "tests", "golden", "rcv1_100.libsvm")
+
+
+def _gen(path, rows, seed, *shape):
+    assert os.path.exists(GEN_BIN), "build/gen_libsvm missing: run make"
+    subprocess.check_call([GEN_BIN, str(path), str(rows), str(seed)] + [str(s) for s in shape])
+    return str(path)
+
+
+def _run(*args, timeout=120):
+    assert os.path.exists(BIN), "build/libsvmparse_tests missing: run make"
+    r = subprocess.run([BIN] + [str(a) for a in args], capture_output=True, text=True,
+                       timeout=timeout)
+    print(r.stdout[-6000:])
+    print(r.stderr[-2000:])
+    assert r.returncode == 0 and "ALL PASSED" in r.stdout, r.stdout[-6000:] + r.stderr[-2000:]
+    return r.stdout
+
+
+@pytest.mark.gpu
+def test_parse_equals_host_parser():
+    """dfx_parse_libsvm == ParseLibSVM exactly (offset, index, value, label, row flags) with
+    needs_host == 0: rcv1-100 whole, the smallest texts, every part of a feature on the 16-byte
+    and 4 KiB boundaries, a line over three tiles, the 64 / 65-byte token, blank runs, the strtof
+    edges as labels and values, long ids, more than 1024 tiles, capacities one too small"""
+    out = _run("parse", RCV1)
+    for tag in ("(a)", "(b)", "(c)", "(d)", "(e)", "(f)", "(g)", "(h)", "(i)", "(j)", "(k)"):
+        assert "parse " + tag in out, tag
+
+
+@pytest.mark.gpu
+def test_fallback_forms_flagged_or_equal():
+    """CRLF, blank lines, inf / nan / hex, "1e", "3:" + blank, abc, 25 digits, q = 28, a signed
+    id, an unterminated last line: none is required to stay on the device; each result is
+    needs_host == 1 or exactly ParseLibSVM's output, and the two forms ParseLibSVM does not
+    terminate on ("1e", abc) are flagged"""
+    out = _run("fallback")
+    assert "fallback value 1e: needs_host" in out and "fallback label abc: needs_host" in out
+
+
+@pytest.mark.gpu
+def test_gather_valued_equals_host_gather():
+    """dfx_gather_rows_valued == GatherRows: a range, a permuted list, gaps, n = 0, r0 > 0,
+    zero-length rows, value NULL on either side, the row flags carried"""
+    _run("gather")
+
+
+@pytest.mark.gpu
+def test_device_batch_reader_libsvm_equals_batch_reader(tmp_path):
+    """DeviceBatchReader("libsvm") == BatchReader batch by batch, valued-or-not included, on the
+    CPU planner test's file and grid, every chunk as one batch, a file whose 50,000-feature rows
+    make the ring entry and the shuffle buffer grow mid-run, and a file with flagged chunks"""
+    out = _run("batches", _gen(tmp_path / "mixed.libsvm", 5000, 7, 5, 15, 24, 3), tmp_path)
+    assert out.count("batches (") == 8 and "chunks parsed by the host ok" in out
+    assert out.count("grow file") == 2
+
+
+# ---- the driver ----------------------------------------------------------------------------
+def _train(args, timeout=120):
+    r = subprocess.run([TRAIN_BIN] + args, capture_output=True, text=True, timeout=timeout)
+    assert r.returncode == 0, r.stdout + r.stderr
+    return r.stdout
+
+
+def _fields(out, tag):
+    """the printed "Rows = .., loss = .., AUC = .." of every line of a kind"""
+    got = [l.split(tag + ": ")[1].split("  (")[0] for l in out.splitlines() if tag + ":" in l]
+    assert got, out
+    return got
+
+
+def _keys(path):
+    """the store's keys of a file's feature ids (the Localizer's byte-reversed ids)"""
+    from oracle import oracle as O
+    offs, ids = [0], []
+    for line in open(path):
+        ids.extend(int(t.split(":")[0]) for t in line.split()[1:])
+        offs.append(len(ids))
+    return O.localize(np.array(offs, np.uint64), np.array(ids, np.uint64))[0]
+
+
+def _same_models(tmp_path, a, b, keys, **cfg):
+    """the same keys, bit-equal entries (slot order is not part of the contract)"""
+    from oracle import oracle as O
+    ups = []
+    for name in (a, b):
+        ups.append(O.Updater(**cfg))
+        ups[-1].load(str(tmp_path / name) + "_part-0")
+    assert ups[0].size() == ups[1].size() > 0
+    n = 0
+    for k in keys:
+        x, y = ups[0].entry(k), ups[1].entry(k)
+        assert (x is None) == (y is None), k
+        if x is None:
+            continue
+        n += 1
+        assert x[0].tobytes() == y[0].tobytes(), k
+        assert (x[1] is None) == (y[1] is None), k
+        if x[1] is not None:
+            assert x[1].tobytes() == y[1].tobytes(), k
+    assert n == ups[0].size()
+
+
+def _auto_equals_host(tmp_path, data, rows, kw, tag, extra_auto=()):
+    outs = {}
+    for parse in ("host", "auto"):
+        outs[parse] = _train(["data_in=" + data, "data_val=" + data, "parse=" + parse,
+                              "data_format=libsvm",
+                              "model_out=" + str(tmp_path / ("m_%s_%s" % (tag, parse)))] + kw +
+                             (list(extra_auto) if parse == "auto" else []))
+    assert "parse: device (libsvm)" in outs["auto"].splitlines()[0], outs["auto"][:200]
+    assert "parse:" not in outs["host"]
+    for kind in ("Training", "Validation"):
+        a, b = _fields(outs["host"], kind), _fields(outs["auto"], kind)
+        assert len(a) == 2 and a == b, (kind, a, b)
+    assert "parsed by the host" not in outs["auto"]
+    _same_models(tmp_path, "m_%s_host" % tag, "m_%s_auto" % tag, _keys(data), V_dim=4,
+                 V_threshold=1)
+    pred = {}
+    for parse in ("host", "auto"):
+        p = str(tmp_path / ("pred_%s_%s" % (tag, parse)))
+        out = _train(["task=2", "data_val=" + data,
+                      "model_in=" + str(tmp_path / ("m_%s_host" % tag)), "pred_out=" + p,
+                      "num_jobs_per_epoch=2", "parse=" + parse, "V_dim=4", "V_threshold=1",
+                      "data_format=libsvm", "max_keys=262144"])
+        assert "Prediction:" in out
+        pred[parse] = open(p + "_part-0", "rb").read()
+    assert len(pred["host"].splitlines()) == rows
+    assert pred["host"] == pred["auto"]
+    return outs
+
+
+COMMON = ["V_dim=4", "V_threshold=1", "num_jobs_per_epoch=2", "max_num_epochs=2",
+          "stop_rel_objv=0", "max_keys=262144", "has_aux=1"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shuffle", [0, 3])
+def test_driver_parse_auto_equals_parse_host_on_rcv1(tmp_path, shuffle):
+    """dfx_train parse=auto data_format=libsvm against parse=host on rcv1-100 (batch_size=7,
+    neg_sampling=0.7, validation, 2 epochs): the same printed Training / Validation fields,
+    models with the same keys and bit-equal entries, byte-identical task=2 prediction files; the
+    start line says device (libsvm) and no chunk goes back to the host"""
+    _auto_equals_host(tmp_path, RCV1, 100,
+                      COMMON + ["batch_size=7", "shuffle=%d" % shuffle, "neg_sampling=0.7"],
+                      "rcv1")
+
+
+@pytest.mark.gpu
+def test_driver_parse_auto_equals_parse_host_on_generated_rows(tmp_path):
+    """the same on 3,000 generated valued rows (5-15 features, %.15g values), shuffled and
+    down-sampled; and parse=auto cache=device equals cache=none"""
+    data = _gen(tmp_path / "g.libsvm", 3000, 11, 5, 15, 20, 1)
+    kw = COMMON + ["batch_size=250", "shuffle=3", "neg_sampling=0.7"]
+    outs = _auto_equals_host(tmp_path, data, 3000, kw, "gen")
+    cached = _train(["data_in=" + data, "data_val=" + data, "parse=auto", "cache=device",
+                     "data_format=libsvm", "model_out=" + str(tmp_path / "m_gen_cache")] + kw)
+    assert "parse: device (libsvm)" in cached and "cache=device:" in cached
+    for kind in ("Training", "Validation"):
+        assert _fields(cached, kind) == _fields(outs["auto"], kind), kind
+    _same_models(tmp_path, "m_gen_auto", "m_gen_cache", _keys(data), V_dim=4, V_threshold=1)
+
+
+@pytest.mark.gpu
+def test_driver_parse_auto_takes_the_host_reader_where_no_device_parser_runs(tmp_path):
+    """parse=auto data_format=adfea and parse=auto shards=2 run on the host reader and the start
+    line says so; parse=device data_format=libsvm keeps exiting 2"""
+    adfea = tmp_path / "a.adfea"
+    adfea.write_text("".join("%d 3 %d 11:1 12:2 %d:3\n" % (i, i % 2, 13 + i % 5) for i in range(40)))
+    kw = ["V_dim=4", "V_threshold=1", "max_keys=262144", "max_num_epochs=1",
+          "num_jobs_per_epoch=1", "batch_size=10"]
+    out = _train(["data_in=" + str(adfea), "data_format=adfea", "parse=auto"] + kw)
+    assert out.splitlines()[0] == "parse: host (data_format=adfea)" and "Training:" in out
+    out = _train(["data_in=" + RCV1, "data_format=libsvm", "parse=auto", "shards=2"] + kw)
+    assert out.splitlines()[0] == "parse: host (a sharded run)" and "Training:" in out
+    r = subprocess.run([TRAIN_BIN, "data_in=" + RCV1, "parse=device", "data_format=libsvm"],
+                       capture_output=True, text=True, timeout=60)
+    assert r.returncode == 2 and "parse=device" in r.stderr
+
+
+# ---- Python --------------------------------------------------------------------------------
+def _libc_reference(data):
+    """the tokens of clean libsvm text through libc's strtof / strtoull (never float())"""
+    libc = ctypes.CDLL(None)
+    libc.strtof.restype = ctypes.c_float
+    libc.strtof.argtypes = [ctypes.c_char_p, ctypes.c_void_p]
+    libc.strtoull.restype = ctypes.c_uint64
+    libc.strtoull.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_int]
+    offs, ids, vals, labels = [0], [], [], []
+    for line in data.split(b"\n")[:-1]:
+        tok = line.split()
+        labels.append(libc.strtof(tok[0], None))
+        for t in tok[1:]:
+            k, _, v = t.partition(b":")
+            ids.append(libc.strtoull(k, None, 10))
+            vals.append(libc.strtof(v, None) if v else 1.0)
+        offs.append(len(ids))
+    vals = np.array(vals, np.float32)
+    flag = np.array([int((vals[a:b].view(np.uint32) != 0x3f800000).any())
+                     for a, b in zip(offs[:-1], offs[1:])], np.uint8)
+    return (np.array(offs, np.uint64), np.array(ids, np.uint64), vals,
+            np.array(labels, np.float32), flag)
+
+
+@pytest.mark.gpu
+def test_hotpath_parse_libsvm(tmp_path):
+    """hotpath.parse_libsvm on rcv1-100 and on 300 generated rows with 64-bit ids against libc's
+    strtof / strtoull applied to the split tokens, bit for bit; a CRLF chunk is handed back"""
+    from difacto_amd import hotpath as H
+    ctx = H.Context(0, V_dim=0, max_keys=1024)
+    gen = open(_gen(tmp_path / "g.libsvm", 300, 3, 0, 9, 64, 3), "rb").read()
+    for data in (open(RCV1, "rb").read(), gen, b"1 5 6:1 7:1.0\n-1\n0.5 3:2\n"):
+        want = _libc_reference(data)
+        offs, ids, vals, labels, rowflag, stat = H.parse_libsvm(ctx, data)
+        assert not stat["needs_host"] and stat["rows"] == len(want[3])
+        assert stat["nnz"] == len(want[1])
+        assert np.array_equal(offs, want[0]) and np.array_equal(ids, want[1])
+        assert vals.tobytes() == want[2].tobytes() and labels.tobytes() == want[3].tobytes()
+        assert np.array_equal(rowflag, want[4])
+    assert H.parse_libsvm(ctx, b"1 5:2\r\n")[5]["needs_host"]
+    ctx.close()
+
+
+@pytest.mark.gpu
+def test_hotpath_gather_rows_valued():
+    """hotpath.gather_rows_valued: a row list gathered behind a range, against numpy"""
+    import torch
+    from difacto_amd import hotpath as H
+    ctx = H.Context(0, V_dim=0, max_keys=1024)
+    data = open(RCV1, "rb").read()
+    offs, ids, vals, labels, rowflag, _ = H.parse_libsvm(ctx, data)
+    dev = ctx.device
+    src = {"offs": torch.from_numpy(offs.view(np.int64)).to(dev),
+           "ids": torch.from_numpy(ids.view(np.int64)).to(dev),
+           "vals": torch.from_numpy(vals).to(dev), "labels": torch.from_numpy(labels).to(dev),
+           "rowflag": torch.from_numpy(rowflag).to(dev)}
+    dst = {"offs": torch.zeros(101, dtype=torch.int64, device=dev),
+           "ids": torch.zeros(len(ids), dtype=torch.int64, device=dev),
+           "vals": torch.zeros(len(ids), dtype=torch.float32, device=dev),
+           "labels": torch.zeros(100, dtype=torch.float32, device=dev),
+           "rowflag": torch.zeros(100, dtype=torch.uint8, device=dev)}
+    pick = np.array([99, 0, 57, 3, 3, 42], np.int32)
+    H.gather_rows_valued(ctx, src, begin=10, n=5, dst=dst)
+    H.gather_rows_valued(ctx, src, rows=torch.from_numpy(pick).to(dev), dst=dst, r0=5)
+    rows = list(range(10, 15)) + list(pick)
+    want_ids = np.concatenate([ids[offs[r]:offs[r + 1]] for r in rows])
+    want_vals = np.concatenate([vals[offs[r]:offs[r + 1]] for r in rows])
+    want_offs = np.concatenate([[0], np.cumsum([offs[r + 1] - offs[r] for r in rows])])
+    n = len(want_ids)
+    assert np.array_equal(H.u64(dst["offs"][:12]), want_offs.astype(np.uint64))
+    assert np.array_equal(H.u64(dst["ids"][:n]), want_ids)
+    assert dst["vals"][:n].cpu().numpy().tobytes() == want_vals.tobytes()
+    assert dst["labels"][:11].cpu().numpy().tobytes() == labels[rows].tobytes()
+    assert np.array_equal(dst["rowflag"][:11].cpu().numpy(), rowflag[rows])
+    ctx.close()
