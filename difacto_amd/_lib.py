@@ -31,6 +31,14 @@ class Batch(ctypes.Structure):
                 ("label", vp), ("weight", vp)]
 
 
+class Loc(ctypes.Structure):
+    """dfx_loc: the Localizer outputs a dfx_batchcache keeps with a batch"""
+    _fields_ = [("uniq", vp), ("segstart", vp), ("occ_row", vp), ("occ_x", vp), ("rowof", vp),
+                ("choff", vp), ("chunk_seg", vp), ("totals", vp), ("U", c_i64),
+                ("n_chunks", c_i64), ("size", c_i64), ("nnz", c_i64), ("max_index", c_u64),
+                ("form", ctypes.c_int32), ("reserved", ctypes.c_int32), ("served", vp)]
+
+
 class Progress(ctypes.Structure):
     _fields_ = [("nrows", ctypes.c_double), ("loss", ctypes.c_double), ("auc", ctypes.c_double),
                 ("penalty", ctypes.c_double), ("nnz_w", ctypes.c_double)]
@@ -139,6 +147,11 @@ _SIGS = {
     "dfx_batchcache_count": (ctypes.c_int, [vp, c_i64, i64p]),
     "dfx_batchcache_get": (ctypes.c_int, [vp, c_i64, c_i64, ctypes.POINTER(Batch)]),
     "dfx_batchcache_stats": (ctypes.c_int, [vp, i64p]),
+    "dfx_batchcache_append_loc": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int)]),
+    "dfx_batchcache_get_loc": (ctypes.c_int, [vp, c_i64, c_i64, ctypes.POINTER(Loc)]),
+    "dfx_batchcache_stats_loc": (ctypes.c_int, [vp, i64p]),
+    "dfx_train_step_loc": (ctypes.c_int, [vp, ctypes.POINTER(Batch), ctypes.POINTER(Loc),
+                                          ctypes.c_int, ctypes.c_int, c_u64, vp]),
     "dfx_dist_record_floats": (ctypes.c_int, [vp]),
     "dfx_dist_localize": (ctypes.c_int, [vp, ctypes.POINTER(Batch), c_u64, ctypes.c_int,
                                          ctypes.c_int, vp, vp]),

@@ -11,6 +11,14 @@
 // stream reuses the source buffers; a replayed batch is ready by the same stream order
 // (dfx_train_step's Localizer lane waits for the input stream).  A list that does not fit the
 // budget is dropped, never the run.
+//
+// Optionally (dfx_batchcache_append_loc) a batch's Localizer outputs are kept next to it — they
+// depend on the batch and max_index alone — and dfx_train_step_loc (step.hip) replays them with
+// no Localizer: uniq[U], segstart[U + 1], occ_row[nnz], occ_x[nnz] or rowof[2 nnz], choff[U] and
+// chunk_seg[n_chunks] when the plan holds chunks, and the totals record {U, n_chunks, gate, 0}.
+// Exact sizes, so ~16 B/nnz where U ~ nnz (the C3 shape) beside the batch's 8 B/nnz, about three
+// times the cache, and ~4 B/nnz on skewed data.  One k_loc_pack launch on the Localizer lane's
+// stream copies them, behind the lane and before that stream reuses the parity's buffers.
 #include <map>
 #include <vector>
 
@@ -30,6 +38,12 @@ struct List {
   int state = kOpen;
   std::vector<Alloc> allocs;
   std::vector<dfx_batch> batches;
+  // per batch, the Localizer outputs kept with it (uniq == NULL: none); what they hold and take;
+  // the batch append_loc was last called for; the lane stream the packs were queued on
+  std::vector<dfx_loc> locs;
+  int64_t n_loc = 0, loc_bytes = 0, loc_tried = -1;
+  hipStream_t loc_stream = nullptr;
+  bool loc_pending = false;  // packs queued and not joined by the host since
   char* cur = nullptr;   // the unused tail of the list's last block
   int64_t cur_left = 0;
   hipStream_t copy_stream = nullptr;  // the stream its copies were queued on
@@ -46,6 +60,11 @@ struct dfx_batchcache {
   std::map<int64_t, List> lists;
   int64_t open = -1;
   int64_t n_sealed = 0, n_dropped = 0, n_batches = 0;
+  // kept Localizer outputs (sealed lists): batches, bytes; steps dfx_train_step_loc served
+  int64_t n_loc = 0, loc_bytes = 0, served = 0;
+  uint64_t loc_seq = 0;               // the context step whose outputs append_loc took last
+  unsigned int* host_rec = nullptr;   // pinned: {U, n_chunks, gate, 0} of the lane just asked
+  hipEvent_t ev_rec = nullptr;        // ... written (the lane's stream)
 };
 
 using namespace dfx;
@@ -104,6 +123,15 @@ void release(dfx_batchcache* bc, List* l) {
     else
       (void)hipStreamSynchronize(l->copy_stream);
   }
+  // the packs of kept Localizer outputs write into the blocks from the lane's stream (a lane
+  // stream that was replaced since was joined when it was, dfx_ctx_set_lane_stream)
+  if (l->loc_pending && l->loc_stream == bc->ctx->c.loc_stream)
+    (void)hipStreamSynchronize(l->loc_stream);
+  l->loc_pending = false;
+  l->locs.clear();
+  l->locs.shrink_to_fit();
+  l->n_loc = 0;
+  l->loc_bytes = 0;
   for (const Alloc& a : l->allocs) {
     (void)hipFree(a.p);
     bc->allocated -= a.bytes;
@@ -117,6 +145,48 @@ void release(dfx_batchcache* bc, List* l) {
   l->copied = false;
 }
 }  // namespace
+
+// ---- the Localizer's outputs kept with a batch (dfx_batchcache_append_loc) -------------------
+namespace dfx {
+// the lane's sizes for the host, after the lane's last kernel: {U, n_chunks, the plan's gate}
+// into the pinned record (one thread; the kernel's end makes them visible to the waiting host)
+__global__ void k_loc_report(const DevState* __restrict__ ds, unsigned int* __restrict__ rec) {
+  rec[0] = ds->u_count;
+  rec[1] = ds->totals[1];
+  rec[2] = ds->n_init;
+  rec[3] = 0u;
+}
+
+// One launch copies every kept array of a batch: a by-value table of {source, destination,
+// bytes} (bytes a multiple of 4; both ends 16-byte aligned: workspace buffers and 256-byte cache
+// slots), moved as 16-byte vectors by a grid-stride loop, the at most three trailing words of an
+// array by the grid's first threads.  Plain loads and stores.  Thread 0 also writes the batch's
+// totals record {U, n_chunks, gate, 0} from the lane's device state.  Six to eight separate async
+// copies would cost the lane's queue microseconds each (profiles/r6/waitbench.txt).
+constexpr int kPackMax = 8, kPackNT = 256, kPackGridMax = 2048;
+struct PackTab {
+  const void* src[kPackMax];
+  void* dst[kPackMax];
+  int64_t bytes[kPackMax];
+  int n;
+  const DevState* ds;
+  uint4* totals;
+};
+__global__ __launch_bounds__(kPackNT) void k_loc_pack(PackTab t) {
+  const int64_t tid = (int64_t)blockIdx.x * kPackNT + threadIdx.x;
+  const int64_t nthr = (int64_t)gridDim.x * kPackNT;
+  for (int a = 0; a < t.n; ++a) {
+    const uint4* __restrict__ s = static_cast<const uint4*>(t.src[a]);
+    uint4* __restrict__ d = static_cast<uint4*>(t.dst[a]);
+    const int64_t nv = t.bytes[a] >> 4;
+    for (int64_t i = tid; i < nv; i += nthr) d[i] = s[i];
+    const int64_t w = nv * 4 + tid;  // a trailing word
+    if (w < (t.bytes[a] >> 2))
+      static_cast<uint32_t*>(t.dst[a])[w] = static_cast<const uint32_t*>(t.src[a])[w];
+  }
+  if (tid == 0) *t.totals = make_uint4(t.ds->u_count, t.ds->totals[1], t.ds->n_init, 0u);
+}
+}  // namespace dfx
 
 extern "C" int dfx_batchcache_create(dfx_ctx* ctx, int64_t budget_bytes, int64_t block_bytes,
                                      dfx_batchcache** out) {
@@ -138,6 +208,8 @@ extern "C" int dfx_batchcache_destroy(dfx_batchcache* bc) {
   (void)hipDeviceSynchronize();
   for (auto& kv : bc->lists)
     for (const Alloc& a : kv.second.allocs) (void)hipFree(a.p);
+  if (bc->host_rec) (void)hipHostFree(bc->host_rec);
+  if (bc->ev_rec) (void)hipEventDestroy(bc->ev_rec);
   delete bc;
   return rc;
 }
@@ -197,6 +269,7 @@ extern "C" int dfx_batchcache_append(dfx_batchcache* bc, const dfx_batch* src, i
   b.label = static_cast<const float*>(to[3]);
   b.weight = static_cast<const float*>(to[4]);
   l.batches.push_back(b);
+  l.locs.push_back(dfx_loc{});
   *kept = 1;
   return DFX_OK;
 }
@@ -215,6 +288,8 @@ extern "C" int dfx_batchcache_seal(dfx_batchcache* bc, int64_t* n_batches) {
   l.cur_left = 0;
   bc->n_sealed += 1;
   bc->n_batches += (int64_t)l.batches.size();
+  bc->n_loc += l.n_loc;
+  bc->loc_bytes += l.loc_bytes;
   *n_batches = (int64_t)l.batches.size();
   return DFX_OK;
 }
@@ -251,5 +326,153 @@ extern "C" int dfx_batchcache_stats(dfx_batchcache* bc, int64_t* out) {
   out[1] = bc->n_dropped;
   out[2] = bc->n_batches;
   out[3] = bc->allocated;
+  return DFX_OK;
+}
+
+extern "C" int dfx_batchcache_append_loc(dfx_batchcache* bc, int* kept) {
+  DFX_CHECK_ARG(bc && kept, "batchcache_append_loc: null argument");
+  DFX_CHECK_ARG(bc->open >= 0, "batchcache_append_loc: no open list (begin one first)");
+  List& l = bc->lists[bc->open];
+  *kept = 0;
+  if (l.state == kDropped) return DFX_OK;  // nothing to keep them with
+  DFX_CHECK_ARG(!l.batches.empty(), "batchcache_append_loc: nothing appended since begin");
+  const int64_t at = (int64_t)l.batches.size() - 1;
+  DFX_CHECK_ARG(l.loc_tried != at, "batchcache_append_loc: called twice for one batch");
+  Context& c = bc->ctx->c;
+  const Context::LastLoc ll = c.last_loc;
+  DFX_CHECK_ARG(ll.ran && c.loc_stream,
+                "batchcache_append_loc: the context's last step ran no Localizer (no "
+                "dfx_train_step yet, or a replayed one)");
+  DFX_CHECK_ARG(ll.seq != bc->loc_seq,
+                "batchcache_append_loc: that step's outputs were already kept (step the batch "
+                "last appended first)");
+  const dfx_batch& b = l.batches[(size_t)at];
+  DFX_CHECK_ARG(ll.B == b.size && ll.nnz == b.nnz,
+                "batchcache_append_loc: the context's last step was of a batch of another B or "
+                "nnz than the batch last appended");
+  DFX_CHECK_ARG((ll.form != 0) == (b.value != nullptr),
+                "batchcache_append_loc: the context's last step was valued and the batch last "
+                "appended is not (or the reverse)");
+  l.loc_tried = at;
+  bc->loc_seq = ll.seq;
+  DFX_HIP(hipSetDevice(c.device));
+  if (!bc->host_rec) {
+    DFX_HIP(hipHostMalloc(reinterpret_cast<void**>(&bc->host_rec), 4 * sizeof(unsigned int),
+                          hipHostMallocDefault));
+    DFX_HIP(hipEventCreateWithFlags(&bc->ev_rec, hipEventDisableTiming));
+  }
+  // the lane's sizes: written behind the lane's last kernel, awaited on the lane's stream alone
+  // (the lane itself waited for the step two back on the main stream, no more)
+  const hipStream_t st = c.loc_stream;
+  const DevState* ds = c.bds[ll.k];
+  const Workspace& w = c.bws[ll.k];
+  hipLaunchKernelGGL(k_loc_report, dim3(1), dim3(1), 0, st, ds, bc->host_rec);
+  DFX_HIP(hipGetLastError());
+  DFX_HIP(hipEventRecord(bc->ev_rec, st));
+  DFX_HIP(hipEventSynchronize(bc->ev_rec));
+  const volatile unsigned int* hr = bc->host_rec;
+  const int64_t B = b.size, nnz = b.nnz;
+  const int64_t U = hr[0], nch = hr[1];
+  if (U > (nnz > 0 ? nnz : 0) || nch > max_chunks(nnz)) {
+    set_error("batchcache_append_loc: the lane reports U / n_chunks out of range");
+    return DFX_ERR_CHECK;
+  }
+  const bool occ = B > 0 && nnz > 0;  // (an empty batch: the lane wrote U = 0 and segstart[0])
+  // {source, bytes} of uniq, segstart, occ_row, occ_x | rowof, choff, chunk_seg; then the totals
+  const void* from[kPackMax] = {w.uniq.p, w.segstart.p, w.occ_row.p,
+                                ll.form == 2 ? static_cast<const void*>(ll.rowof) : w.occ_x.p,
+                                w.flags.p, w.rowtmp.p};
+  const int64_t bytes[kPackMax] = {U * 8, (U + 1) * 4, occ ? nnz * 4 : 0,
+                                   !occ || ll.form == 0 ? 0 : (ll.form == 2 ? nnz * 8 : nnz * 4),
+                                   nch > 0 ? U * 4 : 0, nch > 0 ? nch * 4 : 0};
+  const bool want[6] = {true, true, true, ll.form != 0, nch > 0, nch > 0};
+  void* to[7] = {};
+  // all or nothing: what a refused set already took is given back (nothing was copied there)
+  const size_t allocs0 = l.allocs.size();
+  char* const cur0 = l.cur;
+  const int64_t left0 = l.cur_left;
+  int rc = 1;
+  for (int a = 0; a < 7 && rc == 1; ++a) {
+    if (a < 6 && !want[a]) continue;
+    const int64_t n = a < 6 ? bytes[a] : (int64_t)sizeof(uint4);
+    rc = place(bc, &l, n > 0 ? n : 1, &to[a]);
+  }
+  if (rc != 1) {
+    while (l.allocs.size() > allocs0) {
+      (void)hipFree(l.allocs.back().p);
+      bc->allocated -= l.allocs.back().bytes;
+      l.allocs.pop_back();
+    }
+    l.cur = cur0;
+    l.cur_left = left0;
+    return rc < 0 ? DFX_ERR_HIP : DFX_OK;  // over the budget: the batch stays, without outputs
+  }
+  PackTab t{};
+  int64_t vecs = 0;
+  for (int a = 0; a < 6; ++a) {
+    if (!to[a] || bytes[a] <= 0) continue;
+    t.src[t.n] = from[a];
+    t.dst[t.n] = to[a];
+    t.bytes[t.n] = bytes[a];
+    ++t.n;
+    vecs += bytes[a] / 16 + 1;
+  }
+  t.ds = ds;
+  t.totals = static_cast<uint4*>(to[6]);
+  // ~4 vectors a thread; a small batch gets one block
+  int64_t grid = (vecs + kPackNT * 4 - 1) / (kPackNT * 4);
+  grid = grid < 1 ? 1 : (grid > kPackGridMax ? kPackGridMax : grid);
+  hipLaunchKernelGGL(k_loc_pack, dim3((unsigned)grid), dim3(kPackNT), 0, st, t);
+  DFX_HIP(hipGetLastError());
+  l.loc_stream = st;
+  l.loc_pending = true;
+  dfx_loc o{};
+  o.uniq = static_cast<const uint64_t*>(to[0]);
+  o.segstart = static_cast<const uint32_t*>(to[1]);
+  o.occ_row = static_cast<const uint32_t*>(to[2]);
+  o.occ_x = ll.form == 1 ? static_cast<const float*>(to[3]) : nullptr;
+  o.rowof = ll.form == 2 ? static_cast<const uint32_t*>(to[3]) : nullptr;
+  o.choff = static_cast<const uint32_t*>(to[4]);
+  o.chunk_seg = static_cast<const uint32_t*>(to[5]);
+  o.totals = static_cast<const uint32_t*>(to[6]);
+  o.U = U;
+  o.n_chunks = nch;
+  o.size = B;
+  o.nnz = nnz;
+  o.max_index = ll.max_index;
+  o.form = ll.form;
+  o.served = &bc->served;
+  l.locs[(size_t)at] = o;
+  l.n_loc += 1;
+  // (what the arrays take of the blocks; a fresh block's unused tail counts with the batches)
+  for (int a = 0; a < 7; ++a)
+    if (to[a]) l.loc_bytes += round_up(a < 6 ? (bytes[a] > 0 ? bytes[a] : 1) : (int64_t)sizeof(uint4));
+  *kept = 1;
+  return DFX_OK;
+}
+
+extern "C" int dfx_batchcache_get_loc(dfx_batchcache* bc, int64_t list, int64_t i, dfx_loc* out) {
+  DFX_CHECK_ARG(bc && out, "batchcache_get_loc: null argument");
+  const auto it = bc->lists.find(list);
+  DFX_CHECK_ARG(it != bc->lists.end(), "batchcache_get_loc: no such list");
+  List& l = it->second;
+  DFX_CHECK_ARG(l.state != kOpen, "batchcache_get_loc: the list is still open (seal it)");
+  DFX_CHECK_ARG(l.state == kSealed, "batchcache_get_loc: the list was dropped (over budget)");
+  DFX_CHECK_ARG(i >= 0 && i < (int64_t)l.locs.size(), "batchcache_get_loc: batch index out of range");
+  // the packs ran on the lane's stream: joined once, so that any stream may read the arrays (a
+  // replayed step needs no join: its lane is queued behind them)
+  if (l.loc_pending) {
+    if (l.loc_stream == bc->ctx->c.loc_stream) DFX_HIP(hipStreamSynchronize(l.loc_stream));
+    l.loc_pending = false;
+  }
+  *out = l.locs[(size_t)i];
+  return DFX_OK;
+}
+
+extern "C" int dfx_batchcache_stats_loc(dfx_batchcache* bc, int64_t* out) {
+  DFX_CHECK_ARG(bc && out, "batchcache_stats_loc: null argument");
+  out[0] = bc->n_loc;
+  out[1] = bc->loc_bytes;
+  out[2] = bc->served;
   return DFX_OK;
 }

@@ -267,6 +267,16 @@ struct Context {
   int diag = 0;           // kwarg diag (measurement only): bit 0 no AUC lane, bit 1 Localizer once
   bool loc_done[2] = {false, false};  // diag bit 1: the parity's Localizer output exists
   const uint2* loc_rowof[2] = {nullptr, nullptr};  // (lb_gather=2) the parity's {row, value} by position
+  // the Localizer lane of the last fused step, for dfx_batchcache_append_loc (batchcache.hip):
+  // its parity, sizes and output form (0 binary, 1 occ_x, 2 rowof); ran: it ran localize_run and
+  // chunk_plan (false after a replayed step, dfx_train_step_loc); seq counts the fused steps
+  struct LastLoc {
+    bool ran = false;
+    int k = 0, form = 0;
+    int64_t B = 0, nnz = 0;
+    uint64_t max_index = 0, seq = 0;
+    const uint2* rowof = nullptr;
+  } last_loc;
   int sort_pack = 1;  // the Localizer's sort carries (key bits, row) as one u64 (kwarg)
   int auc_sort = 1;  // the AUC lane's sort (kwarg auc_sort): 3 wave buckets, 2 block buckets,
                      // 1 onesweep radix, 0 merge

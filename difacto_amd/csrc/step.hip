@@ -180,6 +180,22 @@ int probe_keys_run(Context* c, const Lane& L, int64_t bound, const uint64_t* uni
 }
 
 
+// A replayed step's whole Localizer lane (dfx_train_step_loc): the totals record kept with the
+// cached batch, {U, n_chunks, the chunk plan's gate, 0}, into the parity's device state — every
+// word of it that the main stream's kernels read (u_count: the probe, the count push, the chunk
+// kernels and the fused backward, InitV, the finalize; totals[1]: the chunk kernels) and the
+// gate, so that nothing of the batch that used this parity before is left in them.  One block,
+// one 16-byte load, plain stores; the kernel's end publishes them to the main stream through
+// ev_loc, as it does the Localizer's own writes.
+__global__ __launch_bounds__(kWave) void k_loc_install(const uint4* __restrict__ rec,
+                                                       DevState* bds) {
+  if (threadIdx.x != 0) return;
+  const uint4 r = *rec;
+  bds->u_count = r.x;
+  bds->totals[1] = r.y;
+  bds->n_init = r.z;
+}
+
 __global__ __launch_bounds__(kFinNT) void k_step_finalize(FinArgs f) {
   __shared__ double red[kFinNT / kWave];
   step_finalize_body<kFinNT>(f, 0u, red);
@@ -226,8 +242,13 @@ static int fold_stripes_on_error(Context* c, int rc) {
 //   aux lane   AUC of a snapshot of (pred, label) taken on the main stream, beside the
 //              backward; it adds into the progress itself and is joined by the next step's
 //              snapshot (and by dfx_progress_read / dfx_sync).
+//
+// loc (dfx_train_step_loc): the batch's Localizer outputs kept in a device batch cache.  The lane
+// then runs k_loc_install alone, behind the same waits and before the same join and record, and
+// the main stream's kernels read the cached arrays; the parity's workspace, hints and the rest
+// of its device state keep what the last batch that ran the Localizer there left.
 int train_step(Context* c, const dfx_batch* b, int job_type, int push_cnt, uint64_t max_index,
-               float* pred_out) {
+               float* pred_out, const dfx_loc* loc) {
   const int64_t B = b->size, nnz = b->nnz;
   const int d = c->P.V_dim;
   DFX_TRY(step_reserve(c, B, nnz));
@@ -249,11 +270,14 @@ int train_step(Context* c, const dfx_batch* b, int job_type, int push_cnt, uint6
   hipEvent_t ev_auc_mine = db ? c->ev_auc_p[ap] : c->ev_auc;
   if (db) c->auc_par ^= 1;
   const Lane AL{c->aux_stream, &aw, c->ads, &c->ds->err};
-  uint32_t* segstart = bw.segstart.as<uint32_t>();
-  uint64_t* uniq = bw.uniq.as<uint64_t>();     // per rank: the key
+  // the Localizer's outputs as the main stream reads them: this parity's, or the cache's
+  const uint32_t* segstart = loc ? loc->segstart : bw.segstart.as<uint32_t>();
+  const uint64_t* uniq = loc ? loc->uniq : bw.uniq.as<uint64_t>();  // per rank: the key
   uint32_t* segslot = bw.slot.as<uint32_t>();  // per rank: its model-table slot
-  uint32_t* occ_row = bw.occ_row.as<uint32_t>();
-  float* occ_x = b->value ? bw.occ_x.as<float>() : nullptr;
+  const uint32_t* occ_row = loc ? loc->occ_row : bw.occ_row.as<uint32_t>();
+  // (a replayed rowof form: occ_x is not read, occ_get; it stays a valid pointer as in the lane)
+  const float* occ_x = !b->value ? nullptr
+                       : (loc && loc->form == 1) ? loc->occ_x : bw.occ_x.as<float>();
   uint32_t* flags = ws.flags.as<uint32_t>();
   float* pred = pred_out ? pred_out : ws.pred.as<float>();
 
@@ -265,27 +289,45 @@ int train_step(Context* c, const dfx_batch* b, int job_type, int push_cnt, uint6
   // Localizer::Compact: sorted unique keys (segments in key order, the order Update walks
   // keys in — InitV draws — and, per key, the (row, nnz) order of its gradient sums)
   LocOut o;
-  o.segstart = segstart;
+  o.segstart = bw.segstart.as<uint32_t>();
   o.value = b->value;
-  o.occ_row = occ_row;
-  o.occ_x = occ_x;
+  o.occ_row = bw.occ_row.as<uint32_t>();
+  o.occ_x = b->value ? bw.occ_x.as<float>() : nullptr;
   o.col = nullptr;  // probe mode: the forward finds keys itself
-  o.uniq = uniq;
+  o.uniq = bw.uniq.as<uint64_t>();
   const uint2* rowof = c->loc_rowof[k];  // (lb_gather=2) kept with the parity's outputs
   o.rowof_out = &rowof;
   lane_mark(c, 0, c->loc_stream);
-  uint32_t* choff = bw.flags.as<uint32_t>();
-  uint32_t* chunk_seg = bw.rowtmp.as<uint32_t>();
+  // (a replayed plan without chunks: choff / chunk_seg are not read, they stay valid pointers)
+  const bool loc_chunks = loc && loc->n_chunks > 0;
+  const uint32_t* choff = loc_chunks ? loc->choff : bw.flags.as<uint32_t>();
+  const uint32_t* chunk_seg = loc_chunks ? loc->chunk_seg : bw.rowtmp.as<uint32_t>();
   uint32_t* nchunks = &bds->totals[1];
-  if (!((c->diag & 2) && c->loc_done[k])) {  // (diag: measurement only)
+  c->last_loc.ran = false;
+  ++c->last_loc.seq;
+  if (loc) {
+    rowof = loc->form == 2 ? reinterpret_cast<const uint2*>(loc->rowof) : nullptr;
+    hipLaunchKernelGGL(k_loc_install, dim3(1), dim3(kWave), 0, c->loc_stream,
+                       reinterpret_cast<const uint4*>(loc->totals), bds);
+    DFX_HIP(hipGetLastError());
+    if (loc->served) ++*loc->served;
+  } else if (!((c->diag & 2) && c->loc_done[k])) {  // (diag: measurement only)
     rowof = nullptr;
     c->lb_skip = c->loc_done[k] ? (c->lb_diag & (16 | 32 | 64 | 128 | 256 | 512)) : 0;  // (measurement only)
     DFX_TRY(localize_run(c, LL, B, nnz, b->offset, b->index, max_index, o));
     c->lb_skip = 0;
     c->loc_rowof[k] = rowof;
     // long segments (skewed keys) get reduced in chunks: plan them here, off the main stream
-    DFX_TRY(chunk_plan(LL, nnz, segstart, choff, chunk_seg, nchunks));
+    DFX_TRY(chunk_plan(LL, nnz, o.segstart, bw.flags.as<uint32_t>(), bw.rowtmp.as<uint32_t>(),
+                       nchunks));
     c->loc_done[k] = true;
+    c->last_loc.ran = true;
+    c->last_loc.k = k;
+    c->last_loc.form = !b->value ? 0 : (rowof ? 2 : 1);
+    c->last_loc.B = B;
+    c->last_loc.nnz = nnz;
+    c->last_loc.max_index = max_index;
+    c->last_loc.rowof = rowof;
   }
   lane_mark(c, 1, c->loc_stream);
   // the forward writes the AUC lane's snapshot of (pred, label), whose buffers are free once the
@@ -427,7 +469,34 @@ extern "C" int dfx_train_step(dfx_ctx* ctx, const dfx_batch* batch, int job_type
   DFX_CHECK_ARG(job_type == DFX_JOB_TRAINING || job_type == DFX_JOB_VALIDATION ||
                     job_type == DFX_JOB_PREDICTION,
                 "train_step: bad job type");
-  return train_step(&ctx->c, batch, job_type, push_cnt, max_index, pred_out);
+  return train_step(&ctx->c, batch, job_type, push_cnt, max_index, pred_out, nullptr);
+}
+
+extern "C" int dfx_train_step_loc(dfx_ctx* ctx, const dfx_batch* batch, const dfx_loc* loc,
+                                  int job_type, int push_cnt, uint64_t max_index,
+                                  float* pred_out) {
+  if (!loc || !loc->uniq)
+    return dfx_train_step(ctx, batch, job_type, push_cnt, max_index, pred_out);
+  DFX_CHECK_ARG(ctx && batch, "null argument");
+  DFX_CHECK_ARG(batch->size >= 0 && batch->nnz >= 0, "train_step: negative sizes");
+  DFX_CHECK_ARG(batch->size == 0 || (batch->offset && batch->label), "train_step: null buffer");
+  DFX_CHECK_ARG(batch->nnz == 0 || batch->index, "train_step: null index");
+  DFX_CHECK_ARG(job_type == DFX_JOB_TRAINING || job_type == DFX_JOB_VALIDATION ||
+                    job_type == DFX_JOB_PREDICTION,
+                "train_step: bad job type");
+  DFX_CHECK_ARG(loc->max_index == max_index,
+                "train_step_loc: the Localizer outputs were recorded with another max_index");
+  DFX_CHECK_ARG(loc->size == batch->size && loc->nnz == batch->nnz,
+                "train_step_loc: the Localizer outputs are of a batch of other sizes");
+  DFX_CHECK_ARG(loc->form >= 0 && loc->form <= 2 && (loc->form != 0) == (batch->value != nullptr),
+                "train_step_loc: valued outputs with a binary batch (or the reverse)");
+  DFX_CHECK_ARG(loc->segstart && loc->totals && (batch->nnz == 0 || loc->occ_row) &&
+                    (loc->form != 1 || loc->occ_x) && (loc->form != 2 || loc->rowof) &&
+                    (loc->n_chunks <= 0 || (loc->choff && loc->chunk_seg)) &&
+                    loc->U >= 0 && loc->U <= batch->nnz && loc->n_chunks >= 0 &&
+                    loc->n_chunks <= max_chunks(batch->nnz),
+                "train_step_loc: incomplete Localizer outputs");
+  return train_step(&ctx->c, batch, job_type, push_cnt, max_index, pred_out, loc);
 }
 
 // ---- phase timing ----------------------------------------------------------------------

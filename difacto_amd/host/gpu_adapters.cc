@@ -509,7 +509,7 @@ void GpuSGDLearner::ProcessBatch(const dmlc::RowBlock<feaid_t>& batch, int job_t
 }
 
 void GpuSGDLearner::ProcessDeviceBatch(const dfx_batch& batch, int job_type, bool push_cnt,
-                                       std::vector<real_t>* pred_out) {
+                                       std::vector<real_t>* pred_out, const dfx_loc* loc) {
   DFX_HOST_CHECK(fused_, "device batches run the fused path (fused=1)");
   push_cnt = push_cnt && job_type == kTraining && V_dim_ > 0;
   dfx_ctx* c = updater_->context()->h();
@@ -519,9 +519,14 @@ void GpuSGDLearner::ProcessDeviceBatch(const dfx_batch& batch, int job_type, boo
     dpred_->ensure((size_t)batch.size);
     dp = dpred_->get();
   }
-  DfxCheck(dfx_train_step(c, &batch, job_type, push_cnt ? 1 : 0,
-                          std::numeric_limits<uint64_t>::max(), dp),
-           "dfx_train_step");
+  if (loc)
+    DfxCheck(dfx_train_step_loc(c, &batch, loc, job_type, push_cnt ? 1 : 0,
+                                std::numeric_limits<uint64_t>::max(), dp),
+             "dfx_train_step_loc");
+  else
+    DfxCheck(dfx_train_step(c, &batch, job_type, push_cnt ? 1 : 0,
+                            std::numeric_limits<uint64_t>::max(), dp),
+             "dfx_train_step");
   if (pred_out) {
     pred_out->resize((size_t)batch.size);
     dpred_->download(pred_out->data(), (size_t)batch.size);
@@ -576,6 +581,28 @@ dfx_batch DeviceBatchCache::Get(int64_t list, int64_t i) const {
   dfx_batch b;
   DfxCheck(dfx_batchcache_get(h_, list, i, &b), "dfx_batchcache_get");
   return b;
+}
+
+bool DeviceBatchCache::AppendLoc() {
+  int kept = 0;
+  DfxCheck(dfx_batchcache_append_loc(h_, &kept), "dfx_batchcache_append_loc");
+  return kept != 0;
+}
+
+dfx_loc DeviceBatchCache::GetLoc(int64_t list, int64_t i) const {
+  dfx_loc l;
+  DfxCheck(dfx_batchcache_get_loc(h_, list, i, &l), "dfx_batchcache_get_loc");
+  return l;
+}
+
+DeviceBatchCache::LocStats DeviceBatchCache::GetLocStats() const {
+  int64_t s[3] = {0, 0, 0};
+  DfxCheck(dfx_batchcache_stats_loc(h_, s), "dfx_batchcache_stats_loc");
+  LocStats out;
+  out.batches = s[0];
+  out.bytes = s[1];
+  out.served = s[2];
+  return out;
 }
 
 DeviceBatchCache::Stats DeviceBatchCache::GetStats() const {

@@ -187,9 +187,10 @@ class GpuSGDLearner {
                     std::vector<real_t>* pred = nullptr, dfx_batch* dev_batch = nullptr);
   /** the fused path for a batch already on the device (DeviceBatchReader, device_reader.h):
    * dfx_train_step without the pinned copy; the batch's producer is the context's input
-   * stream.  pred (optional) receives the predictions (joins the device). */
+   * stream.  pred (optional) receives the predictions (joins the device).  loc (optional): the
+   * batch's Localizer outputs from a DeviceBatchCache (dfx_train_step_loc: no Localizer runs). */
   void ProcessDeviceBatch(const dfx_batch& batch, int job_type, bool push_cnt,
-                          std::vector<real_t>* pred = nullptr);
+                          std::vector<real_t>* pred = nullptr, const dfx_loc* loc = nullptr);
   /** the learner's device context (the fused path's; null when a Store was given) */
   dfx_ctx* context() const { return updater_ ? updater_->context()->h() : nullptr; }
   /** sgd::Progress accumulated since the last call (joins the device) */
@@ -231,6 +232,15 @@ class DeviceBatchCache {
     int64_t sealed = 0, dropped = 0, batches = 0, bytes = 0;
   };
   Stats GetStats() const;
+  /** after the step that consumed the batch last appended: keeps its Localizer outputs with
+   * it; false: they did not fit (the batch stays, the list is not dropped) */
+  bool AppendLoc();
+  /** the outputs kept with batch i of a sealed list (uniq == NULL: none) */
+  dfx_loc GetLoc(int64_t list, int64_t i) const;
+  struct LocStats {
+    int64_t batches = 0, bytes = 0, served = 0;
+  };
+  LocStats GetLocStats() const;
 
  private:
   dfx_batchcache* h_ = nullptr;

@@ -6,7 +6,8 @@
 //                   [num_jobs_per_epoch=10] [stop_rel_objv=1e-5] [model_in=F] [model_out=F]
 //                   [load_epoch=-1] [has_aux=0] [task=0|2] [pred_out=F] [pred_prob=1]
 //                   [fused=1] [nthreads=8] [parse=host|device|auto] [cache=none|device]
-//                   [cache_mb=16384] [V_dim=..] [lr=..] [l1=..] ...  (SGDUpdaterParam)
+//                   [cache_mb=16384] [cache_loc=0] [V_dim=..] [lr=..] [l1=..] ...
+//                   (SGDUpdaterParam)
 //
 // parse=device (data_format=criteo|criteo_test, the single-GPU fused path: training, data_val
 // validation and task=2 prediction): the raw text is copied to pinned memory and uploaded, the
@@ -32,6 +33,17 @@
 // cache.  After the recording epoch one line reports the batches and MB held and the parts not
 // cached.  With exchange=split or fused=0 it is an error (exit 2); task=2 is one pass over the
 // data, so there it is accepted and has no effect.
+//
+// cache_loc=1 (with cache=device, the single-GPU fused path, not task=2): the recording epoch
+// also keeps, next to every cached batch, the outputs of that batch's Localizer
+// (dfx_batchcache_append_loc after each step, training and data_val alike), and the replayed
+// epochs step from them with no Localizer at all (dfx_train_step_loc) — a batch's Localizer
+// output depends on the batch alone, so the losses and the model are the same bits.  It costs
+// ~16 B/nnz of the budget where nearly every key of a batch is distinct, beside the batch's
+// 8 B/nnz (about three times the cache), far less on skewed data; outputs that do not fit are
+// left out and their batches replay with the Localizer.  One more line after the cache's
+// reports the batches that hold outputs and their MB.  Without cache=device, with fused=0,
+// task=2 or in a sharded run it is an error (exit 2).  Default 0: the run as without it.
 //
 // Sharded store (KVStoreDist over GPUs, dist_host.h): `shards=N` holds N shards on this GPU
 // (loopback exchange, for tests); `shards=-1` or a launch with WORLD_SIZE > 1 (RANK / LOCAL_RANK as
@@ -86,6 +98,7 @@ struct Param {
   std::string parse = "host";  // device: DeviceBatchReader (text parsed on the GPU); auto
   std::string cache = "none";  // device: formed batches kept in HBM, replayed after the first epoch
   int64_t cache_mb = 16384;    // its budget (per shard)
+  bool cache_loc = false;      // the Localizer's outputs kept with the cached batches too
 };
 
 // sgd_learner.h:65-69
@@ -137,13 +150,17 @@ Progress RunEpoch(GpuSGDLearner* learner, const Param& P, int epoch, int job_typ
   for (int part = 0; part < P.num_jobs_per_epoch; ++part) {
     const int64_t list = CacheList(P, train, part);
     const bool rec = cache && record;
+    const bool rec_loc = rec && P.cache_loc;  // each step's Localizer outputs with its batch
     const int64_t n_cached = cache && !record ? cache->Count(list) : -1;
     if (rec) cache->Begin(list);
     if (n_cached >= 0) {
       for (int64_t i = 0; i < n_cached; ++i) {
         const dfx_batch b = cache->Get(list, i);
+        dfx_loc loc;
+        if (P.cache_loc) loc = cache->GetLoc(list, i);
         const double ts = Now();
-        learner->ProcessDeviceBatch(b, job_type, train && epoch == 0);
+        learner->ProcessDeviceBatch(b, job_type, train && epoch == 0, nullptr,
+                                    P.cache_loc ? &loc : nullptr);
         if (step_s) step_s[0] += Now() - ts;
       }
     } else if (feed) {
@@ -160,6 +177,7 @@ Progress RunEpoch(GpuSGDLearner* learner, const Param& P, int epoch, int job_typ
                                     pred_file ? &pred : nullptr);
         reader.Consumed();
         if (step_s) step_s[0] += Now() - ts;
+        if (rec_loc) cache->AppendLoc();
         const float* label = reader.HostLabels();
         for (size_t i = 0; pred_file && i < pred.size(); ++i)  // SavePred
           std::fprintf(pred_file, "%g\t%g\n", label[i],
@@ -182,6 +200,7 @@ Progress RunEpoch(GpuSGDLearner* learner, const Param& P, int epoch, int job_typ
         dfx_batch db;
         learner->ProcessBatch(blk, job_type, epoch == 0, nullptr, rec ? &db : nullptr);
         if (rec) cache->Append(db);
+        if (rec_loc) cache->AppendLoc();
       }
     } else {
       // sgd_learner.cc:281-286: validation reads whole 256 MB chunks as one batch
@@ -193,6 +212,7 @@ Progress RunEpoch(GpuSGDLearner* learner, const Param& P, int epoch, int job_typ
         learner->ProcessBatch(v.GetBlock(), job_type, false, pred_file ? &pred : nullptr,
                               rec ? &db : nullptr);
         if (rec) cache->Append(db);
+        if (rec_loc) cache->AppendLoc();
         for (size_t i = 0; pred_file && i < pred.size(); ++i)  // SavePred
           std::fprintf(pred_file, "%g\t%g\n", v.label[i],
                        P.pred_prob ? 1.0 / (1.0 + std::exp(-pred[i])) : (double)pred[i]);
@@ -533,6 +553,7 @@ int main(int argc, char** argv) {
     else if (k == "parse") P.parse = v;
     else if (k == "cache") P.cache = v;
     else if (k == "cache_mb") P.cache_mb = std::stoll(v);
+    else if (k == "cache_loc") P.cache_loc = std::stoi(v) != 0;
     else {
       fused_given = fused_given || k == "fused";
       rest.push_back({k, v});
@@ -585,6 +606,24 @@ int main(int argc, char** argv) {
   if (P.cache != "none" && P.cache != "device") {
     std::fprintf(stderr, "cache must be none or device\n");
     return 2;
+  }
+  if (P.cache_loc) {  // no silent run without the kept outputs
+    bool fused = true;
+    for (const auto& kv : rest)
+      if (kv.first == "fused") fused = std::stoi(kv.second) != 0;
+    const char* why = nullptr;
+    if (P.cache != "device")
+      why = "cache=device (the outputs are kept with the cached batches)";
+    else if (!fused)
+      why = "the fused path (fused=1)";
+    else if (P.task == 2)
+      why = "a training run (task=2 is one pass: nothing is replayed)";
+    else if (sharded)
+      why = "the single-GPU run (shards=0): the sharded paths localize per shard";
+    if (why) {
+      std::fprintf(stderr, "cache_loc=1 needs %s\n", why);
+      return 2;
+    }
   }
   if (P.cache == "device") {  // no silent run without the cache
     bool fused = true;
@@ -664,6 +703,14 @@ int main(int argc, char** argv) {
       const DeviceBatchCache::Stats cs = cache->GetStats();
       PrintCacheLine((double)cs.batches, (double)cs.bytes, (double)cs.dropped,
                      (double)(cs.sealed + cs.dropped));
+      if (P.cache_loc) {
+        const DeviceBatchCache::LocStats ls = cache->GetLocStats();
+        // (held counts whole blocks; the outputs' own bytes, each array rounded to 256)
+        std::printf("cache_loc=1: %lld of %lld batches hold Localizer outputs, %.1f MB of the "
+                    "%.1f MB held\n",
+                    (long long)ls.batches, (long long)cs.batches, (double)ls.bytes / (1 << 20),
+                    (double)cs.bytes / (1 << 20));
+      }
     }
     std::fflush(stdout);
     // stop criteria, sgd_learner.cc:89-108

@@ -306,12 +306,72 @@ class Store:
                 np.array(V, np.float32)[:2 * d].copy() if hv.value else None)
 
 
-def train_step(ctx, dblk, job_type=kTraining, push_cnt=False, max_index=MAX_INDEX, pred=None):
+def train_step(ctx, dblk, job_type=kTraining, push_cnt=False, max_index=MAX_INDEX, pred=None,
+               loc=None):
     """One fused minibatch (localize -> [feacnt] -> pull -> predict -> eval -> AUC ->
-    calcgrad -> push).  Progress accumulates on the device; read it with progress()."""
+    calcgrad -> push).  Progress accumulates on the device; read it with progress().
+    loc: the batch's Localizer outputs from BatchCache.get_loc (dfx_train_step_loc: the step
+    reads them from the cache and runs no Localizer); None, or one that holds none: as without."""
     b = dblk.as_batch()
-    check(_lib.lib().dfx_train_step(ctx.h, ctypes.byref(b), int(job_type), int(bool(push_cnt)),
-                                    ctypes.c_uint64(max_index), _p(pred)))
+    if loc is None:
+        check(_lib.lib().dfx_train_step(ctx.h, ctypes.byref(b), int(job_type),
+                                        int(bool(push_cnt)), ctypes.c_uint64(max_index),
+                                        _p(pred)))
+        return
+    check(_lib.lib().dfx_train_step_loc(ctx.h, ctypes.byref(b), ctypes.byref(loc.l),
+                                        int(job_type), int(bool(push_cnt)),
+                                        ctypes.c_uint64(max_index), _p(pred)))
+
+
+class CachedLoc:
+    """The Localizer outputs a BatchCache keeps with a batch (dfx_loc; its pointers point into
+    the cache).  held: False when the batch has none (train_step(loc=) then runs the
+    Localizer); arrays() downloads them."""
+
+    def __init__(self, ctx, l):
+        self.ctx = ctx
+        self.l = l
+        self.held = bool(l.uniq)
+        self.U, self.n_chunks, self.form = l.U, l.n_chunks, l.form
+        self.size, self.nnz, self.max_index = l.size, l.nnz, l.max_index
+
+    def pointers(self):
+        """the device addresses of the kept arrays (None: NULL)"""
+        l = self.l
+        return {"uniq": l.uniq, "segstart": l.segstart, "occ_row": l.occ_row, "occ_x": l.occ_x,
+                "rowof": l.rowof, "choff": l.choff, "chunk_seg": l.chunk_seg,
+                "totals": l.totals}
+
+    def _download(self, ptr, n, dtype):
+        out = np.empty(n, dtype)
+        if n:
+            check(_lib.lib().dfx_memcpy(self.ctx.h, ctypes.c_void_p(out.ctypes.data),
+                                        ctypes.c_void_p(ptr), out.nbytes, 1))
+        return out
+
+    def arrays(self):
+        """-> what localize_occ returns for the batch, from the cache: U, n_chunks, uniq[U],
+        segstart[U + 1], occ_row[nnz] and occ_x[nnz] (uint32 bit patterns, None for binary data;
+        the rowof form resolved through its {row, value}-by-position array as the backward reads
+        it), choff[U] and chunk_seg[n_chunks] (None without chunks); plus form and totals, the
+        record's four device words.  None when the batch holds no outputs."""
+        if not self.held:
+            return None
+        l = self.l
+        U, nch, nnz = l.U, l.n_chunks, l.nnz if l.size > 0 else 0
+        out = {"U": U, "n_chunks": nch, "form": l.form,
+               "uniq": self._download(l.uniq, U, np.uint64),
+               "segstart": self._download(l.segstart, U + 1, np.uint32),
+               "totals": self._download(l.totals, 4, np.uint32)}
+        rows = self._download(l.occ_row, nnz, np.uint32)
+        xs = self._download(l.occ_x, nnz, np.uint32) if l.form == 1 else None
+        if l.form == 2:
+            rv = self._download(l.rowof, 2 * nnz, np.uint32).reshape(nnz, 2)
+            rows, xs = rv[rows, 0].copy(), rv[rows, 1].copy()
+        out["occ_row"], out["occ_x"] = rows, xs
+        out["choff"] = self._download(l.choff, U, np.uint32) if nch > 0 else None
+        out["chunk_seg"] = self._download(l.chunk_seg, nch, np.uint32) if nch > 0 else None
+        return out
 
 
 class CachedBatch:
@@ -398,6 +458,26 @@ class BatchCache:
         out = (ctypes.c_int64 * 4)()
         check(_lib.lib().dfx_batchcache_stats(self.h, out))
         return dict(zip(("sealed", "dropped", "batches", "bytes"), list(out)))
+
+    def append_loc(self):
+        """after the train_step (on this cache's context) that consumed the batch last
+        appended: keeps that step's Localizer outputs with it -> kept (False: they did not fit
+        the budget; the batch stays cached without them, the list is not dropped)"""
+        kept = ctypes.c_int(0)
+        check(_lib.lib().dfx_batchcache_append_loc(self.h, ctypes.byref(kept)))
+        return bool(kept.value)
+
+    def get_loc(self, list_id, i):
+        """-> CachedLoc of batch i of a sealed list, for train_step(loc=)"""
+        l = _lib.Loc()
+        check(_lib.lib().dfx_batchcache_get_loc(self.h, int(list_id), int(i), ctypes.byref(l)))
+        return CachedLoc(self.ctx, l)
+
+    def stats_loc(self):
+        """-> (batches holding Localizer outputs, the bytes those take, steps served from them)"""
+        out = (ctypes.c_int64 * 3)()
+        check(_lib.lib().dfx_batchcache_stats_loc(self.h, out))
+        return tuple(out)
 
     def close(self):
         if getattr(self, "h", None):

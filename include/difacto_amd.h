@@ -319,6 +319,78 @@ int dfx_batchcache_count(dfx_batchcache* bc, int64_t list, int64_t* n_batches);
 int dfx_batchcache_get(dfx_batchcache* bc, int64_t list, int64_t i, dfx_batch* out);
 int dfx_batchcache_stats(dfx_batchcache* bc, int64_t* out); /* out[4] */
 
+/* ---- the Localizer's outputs kept with a cached batch (batchcache.hip, step.hip) ----------
+ * A batch's Localizer output depends on the batch and max_index alone, not on the model, so a
+ * replayed epoch's Localizer lane recomputes bit for bit what the recording epoch's computed.
+ * Opt-in: the recording epoch keeps, next to a cached batch, what the main stream of
+ * dfx_train_step reads of its lane's work (dfx_localize_occ's terms): uniq[U],
+ * segstart[U + 1], occ_row[nnz]; for a valued batch occ_x[nnz], or (lb_gather=2) rowof[2 nnz]
+ * with occ_row holding input positions — whichever form the lane produced, replayed as that
+ * form; when the chunk plan holds chunks, choff[U] and chunk_seg[n_chunks]; and the totals
+ * record, four device words {U, n_chunks, the plan's gate, 0}: every word of the lane's device
+ * state that the probe, the count push, the chunk kernels, the fused backward, InitV or the
+ * finalize read.  Not kept: the keys' table slots, the InitV flags and whatever else depends on
+ * the model — a table that grows between record and replay does not matter.
+ * Memory: exact sizes by what the lane produced (not the nnz bound), from the open list's
+ * blocks, each array on a 256-byte boundary, inside the same budget as the batches.  Where
+ * U ~ nnz (uniform keys, the C3 shape) that is ~16 B/nnz (8 uniq + 4 segstart + 4 occ_row)
+ * beside the batch's 8 B/nnz, about three times the cache without the outputs; on skewed data
+ * U << nnz and it is nearer 4 B/nnz.
+ *   dfx_batchcache_append_loc  after the dfx_train_step (on the cache's context) that consumed
+ *                          the batch last appended, from that batch's pointers or its
+ *                          source's: keeps that step's Localizer outputs with that batch;
+ *                          *kept = 1.  The lane's sizes {U, n_chunks, gate} reach a pinned host
+ *                          record by one small kernel queued on the lane's stream; the host
+ *                          waits for that lane alone, never for the context stream, then
+ *                          queues one kernel (k_loc_pack: a by-value table of {source,
+ *                          destination, bytes}, 16-byte vector moves) on the lane's stream,
+ *                          behind the lane and before that stream reuses the parity's buffers.
+ *                          Outputs that do not fit the budget: *kept = 0 with DFX_OK, the batch
+ *                          stays cached without them and the list is NOT dropped.
+ *                          DFX_ERR_ARG: no open list, nothing appended since begin, a second
+ *                          call for one batch or one step, the context's last step ran no
+ *                          Localizer (none yet, or a replayed one) or was of another B or nnz
+ *   dfx_batchcache_get_loc     batch i of a sealed list: *out, pointers into the cache as get's;
+ *                          out->uniq == NULL (DFX_OK) for a batch without outputs.  Callers
+ *                          pass the struct on and read only uniq (tests: its arrays)
+ *   dfx_train_step_loc         dfx_train_step whose lane does not run the Localizer and the
+ *                          chunk plan: on the same lane stream, behind the same waits (the
+ *                          input, the parity's last user) and before the same join and event
+ *                          record, one one-block kernel (k_loc_install) writes the totals record
+ *                          into the parity's device state, and the step's kernels read the
+ *                          arrays in the cache.  Same results, bit for bit, for every job type
+ *                          and with push_cnt (the counts are the segment lengths).  loc NULL or
+ *                          loc->uniq NULL: dfx_train_step.  DFX_ERR_ARG: max_index, B or nnz are
+ *                          not the recorded ones, or a valued loc with a binary batch.  The
+ *                          Localizer's own carried state (workspace hints, fitted key range,
+ *                          hot-key map) is not touched by a replayed step: the next batch that
+ *                          runs the lane uses the state of the last batch that ran it, which is
+ *                          allowed because the Localizer's outputs are the same bits on every
+ *                          path it may choose
+ *   dfx_batchcache_stats_loc   out[3] = {batches holding outputs (sealed lists), the bytes they
+ *                          take (rounded to 256 per array), steps dfx_train_step_loc served
+ *                          from outputs of this cache} */
+typedef struct {
+  const uint64_t* uniq;      /* [U]; NULL: the batch holds no outputs */
+  const uint32_t* segstart;  /* [U + 1] */
+  const uint32_t* occ_row;   /* [nnz] */
+  const float* occ_x;        /* [nnz] (form 1) */
+  const uint32_t* rowof;     /* [2 nnz] (form 2) */
+  const uint32_t* choff;     /* [U] (n_chunks > 0) */
+  const uint32_t* chunk_seg; /* [n_chunks] */
+  const uint32_t* totals;    /* device: {U, n_chunks, gate, 0} */
+  int64_t U, n_chunks, size, nnz;
+  uint64_t max_index;
+  int32_t form;              /* 0 binary, 1 valued with occ_x, 2 valued with rowof */
+  int32_t reserved;
+  int64_t* served;           /* the owning cache's count of steps served */
+} dfx_loc;
+int dfx_batchcache_append_loc(dfx_batchcache* bc, int* kept);
+int dfx_batchcache_get_loc(dfx_batchcache* bc, int64_t list, int64_t i, dfx_loc* out);
+int dfx_batchcache_stats_loc(dfx_batchcache* bc, int64_t* out); /* out[3] */
+int dfx_train_step_loc(dfx_ctx* ctx, const dfx_batch* batch, const dfx_loc* loc, int job_type,
+                       int push_cnt, uint64_t max_index, float* pred_out);
+
 /* ---- Localizer::Compact (localizer.h:41-51) -------------------------------------------
  * keys = ReverseBytes(index % max_index); uniq[U] ascending, cnt[U] occurrence counts
  * (float, may be NULL), col[nnz] = rank of each nnz's key (the u32 CSR index).  Offsets,
