@@ -111,32 +111,22 @@ _SIGS = {
     "dfx_gather_rows_valued": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, c_i64, c_i64, vp, vp,
                                               vp, vp, vp, c_i64]),
     "dfx_textfeed_create": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, c_i64, c_i64,
-                                           ctypes.POINTER(vp)]),
-    "dfx_textfeed_create_fmt": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, c_i64, c_i64,
-                                               ctypes.c_int, ctypes.POINTER(vp)]),
-    "dfx_textfeed_submit_libsvm": (ctypes.c_int, [vp, ctypes.c_int, c_i64, c_i64, c_i64]),
-    "dfx_textfeed_wait_valued": (ctypes.c_int, [vp, ctypes.c_int, i64p, ctypes.POINTER(vp),
-                                                ctypes.POINTER(vp), ctypes.POINTER(vp)]),
-    "dfx_textfeed_upload_valued": (ctypes.c_int, [vp, ctypes.c_int, c_i64, c_i64, vp, vp, vp,
-                                                  vp]),
-    "dfx_textfeed_gather_valued": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, c_i64,
-                                                  c_i64, c_i64, c_i64]),
-    "dfx_textfeed_batch_end_valued": (ctypes.c_int, [vp, c_i64, c_i64, ctypes.c_int,
-                                                     ctypes.POINTER(Batch)]),
-    "dfx_textfeed_slot_batch_valued": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int,
-                                                      ctypes.POINTER(Batch)]),
+                                           ctypes.c_int, ctypes.POINTER(vp)]),
     "dfx_textfeed_destroy": (ctypes.c_int, [vp]),
     "dfx_textfeed_text": (ctypes.c_int, [vp, ctypes.c_int, c_i64, ctypes.POINTER(vp)]),
-    "dfx_textfeed_submit": (ctypes.c_int, [vp, ctypes.c_int, c_i64, ctypes.c_int, c_i64]),
+    "dfx_textfeed_submit": (ctypes.c_int, [vp, ctypes.c_int, c_i64, ctypes.c_int, c_i64, c_i64]),
     "dfx_textfeed_wait": (ctypes.c_int, [vp, ctypes.c_int, i64p, ctypes.POINTER(vp),
-                                         ctypes.POINTER(vp)]),
-    "dfx_textfeed_upload": (ctypes.c_int, [vp, ctypes.c_int, c_i64, c_i64, vp, vp, vp]),
+                                         ctypes.POINTER(vp), ctypes.POINTER(vp)]),
+    "dfx_textfeed_upload": (ctypes.c_int, [vp, ctypes.c_int, c_i64, c_i64, vp, vp, vp, vp,
+                                           ctypes.POINTER(vp)]),
     "dfx_textfeed_batch_begin": (ctypes.c_int, [vp]),
     "dfx_textfeed_gather": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, c_i64, c_i64,
-                                           c_i64]),
-    "dfx_textfeed_batch_end": (ctypes.c_int, [vp, c_i64, c_i64, ctypes.POINTER(Batch)]),
+                                           c_i64, c_i64]),
+    "dfx_textfeed_batch_end": (ctypes.c_int, [vp, c_i64, c_i64, ctypes.c_int,
+                                              ctypes.POINTER(Batch)]),
     "dfx_textfeed_consumed": (ctypes.c_int, [vp]),
-    "dfx_textfeed_slot_batch": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(Batch)]),
+    "dfx_textfeed_slot_batch": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int,
+                                               ctypes.POINTER(Batch)]),
     "dfx_textfeed_slot_consumed": (ctypes.c_int, [vp, ctypes.c_int]),
     "dfx_batchcache_create": (ctypes.c_int, [vp, c_i64, c_i64, ctypes.POINTER(vp)]),
     "dfx_batchcache_destroy": (ctypes.c_int, [vp]),

@@ -238,20 +238,19 @@ __global__ __launch_bounds__(kNT) void k_ls_cells(const char* text, uint32_t nby
 
 }  // namespace
 
-int dfx::parse_libsvm_on(DevBuf* tiles_buf, DevBuf* stat_buf, hipStream_t st, const char* text,
-                    int64_t nbytes, int64_t max_rows, int64_t max_nnz, uint64_t* offset,
-                    uint64_t* index, float* value, float* label, uint8_t* rowflag,
-                    int64_t* stat_dev) {
+int dfx::parse_libsvm_on(const TpScratch& ws, hipStream_t st, const char* text, int64_t nbytes,
+                         int64_t max_rows, int64_t max_nnz, uint64_t* offset, uint64_t* index,
+                         float* value, float* label, uint8_t* rowflag, int64_t* stat_dev) {
   DFX_CHECK_ARG(nbytes >= 0 && nbytes < (1ll << 31),
                 "parse_libsvm: positions are 32-bit, nbytes must be in [0, 2^31)");
   DFX_CHECK_ARG(max_rows >= 0 && max_nnz >= 0 && offset && stat_dev && (text || nbytes == 0) &&
                     ((label && rowflag) || max_rows == 0) && ((index && value) || max_nnz == 0),
                 "parse_libsvm: bad argument");
   const uint32_t ntiles = blocks_for((uint64_t)nbytes, kTpTile);
-  DFX_TRY(tiles_buf->ensure((size_t)std::max(ntiles, 1u) * sizeof(LsT)));
-  DFX_TRY(stat_buf->ensure(sizeof(LsStat)));
-  LsT* tiles = tiles_buf->as<LsT>();
-  LsStat* ds = stat_buf->as<LsStat>();
+  DFX_TRY(ws.tiles->ensure((size_t)std::max(ntiles, 1u) * sizeof(LsT)));
+  DFX_TRY(ws.stat->ensure(sizeof(LsStat)));
+  LsT* tiles = ws.tiles->as<LsT>();
+  LsStat* ds = ws.stat->as<LsStat>();
   const int aligned = (reinterpret_cast<uintptr_t>(text) & 15) == 0;
   DFX_HIP(hipMemsetAsync(ds, 0, sizeof(LsStat), st));
   if (nbytes > 0) {
@@ -285,6 +284,6 @@ extern "C" int dfx_parse_libsvm(dfx_ctx* ctx, const char* text_dev, int64_t nbyt
   DFX_HIP(hipSetDevice(ctx->c.device));
   Context* c = &ctx->c;
   // the Criteo parser's tile and counter scratch: both run in the input stream's order
-  return parse_libsvm_on(&c->tp_tiles, &c->tp_stat, input_stream(c), text_dev, nbytes, max_rows,
-                         max_nnz, offset, index, value, label, rowflag, stat_dev);
+  return parse_libsvm_on(context_scratch(c), input_stream(c), text_dev, nbytes, max_rows, max_nnz,
+                         offset, index, value, label, rowflag, stat_dev);
 }

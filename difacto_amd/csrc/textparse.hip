@@ -1,14 +1,11 @@
-// Criteo text -> CSR on the device, the device form of the host reader's row gather, and the
-// text feeder that runs both beside the step.
+// Criteo text -> CSR on the device, and the device form of the host reader's row gather.
 //
 //   dfx_parse_criteo   ParseCriteo (difacto_amd/host/reader.cc; criteo_parser.h:40-92) over a
 //                      chunk of whole lines already in device memory
 //   dfx_gather_rows    GatherRows (reader.cc; the row copies of batch_reader.cc:29-78);
 //                      dfx_gather_rows_valued: the same kernels with values and row flags
-//   dfx_textfeed_*     pinned text slots, a loader stream, parsed chunks, a shuffle buffer and
-//                      a ring of device batches (the producer half of sgd_learner.cc:289-314);
-//                      its libsvm mode (dfx_parse_libsvm, libsvmparse.hip) is at the end
-// The scans (block_scan, k_scan_*) are csrc/textscan.h, shared with libsvmparse.hip.
+// The scans (block_scan, k_scan_*) are csrc/textscan.h, shared with libsvmparse.hip; the text
+// feed that runs the parsers and the gather beside the step is textfeed.hip.
 //
 // The parser is parallel over bytes and cells, never one lane per row:
 //   k_tp_tiles      every thread takes 16 bytes and marks its terminators ('\t', '\n'); a tile
@@ -52,7 +49,6 @@ using namespace dfx;
 
 namespace {
 
-constexpr int kCols = 39;              // criteo feature columns (13 integer + 26 categorical)
 constexpr int kLineSlots = 40;         // cells kept per line: a label and 39 columns
 
 constexpr unsigned kFlagLabel = 1, kFlagCR = 2, kFlagEmptyLine = 4, kFlagTail = 8;
@@ -332,13 +328,14 @@ __global__ __launch_bounds__(kNT) void k_tg_copy(const uint64_t* src_off, const 
   }
 }
 
+}  // namespace
+
 template <bool kValued>
-int gather_rows_on(Context* c, hipStream_t st, const uint64_t* src_offset,
-                   const uint64_t* src_index, const float* src_label, const uint32_t* rows_dev,
-                   int64_t begin, int64_t n, uint64_t* dst_offset, uint64_t* dst_index,
-                   float* dst_label, int64_t r0, const float* src_value = nullptr,
-                   float* dst_value = nullptr, const uint8_t* src_flag = nullptr,
-                   uint8_t* dst_flag = nullptr) {
+int dfx::gather_rows_on(Context* c, hipStream_t st, const uint64_t* src_offset,
+                        const uint64_t* src_index, const float* src_label,
+                        const uint32_t* rows_dev, int64_t begin, int64_t n, uint64_t* dst_offset,
+                        uint64_t* dst_index, float* dst_label, int64_t r0, const float* src_value,
+                        float* dst_value, const uint8_t* src_flag, uint8_t* dst_flag) {
   DFX_CHECK_ARG(n >= 0 && n < (1ll << 31) && begin >= 0 && r0 >= 0, "gather_rows: bad range");
   if (n == 0) return DFX_OK;  // GatherRows: nothing appended, nothing touched
   DFX_CHECK_ARG(src_offset && src_index && src_label && dst_offset && dst_index && dst_label,
@@ -363,15 +360,19 @@ int gather_rows_on(Context* c, hipStream_t st, const uint64_t* src_offset,
   return DFX_OK;
 }
 
-// the parser's scratch: the context's own set (dfx_parse_criteo, on the input stream) or a text
-// feeder's (its parses run on a stream of their own)
-struct TpScratch {
-  DevBuf *tiles, *cells, *lines, *pair, *tot, *stat;
-};
+// the feed (textfeed.hip) picks one of the two by its format
+#define DFX_GATHER_ROWS_ON(kValued)                                                              \
+  template int dfx::gather_rows_on<kValued>(                                                     \
+      Context*, hipStream_t, const uint64_t*, const uint64_t*, const float*, const uint32_t*,    \
+      int64_t, int64_t, uint64_t*, uint64_t*, float*, int64_t, const float*, float*,             \
+      const uint8_t*, uint8_t*)
+DFX_GATHER_ROWS_ON(false);
+DFX_GATHER_ROWS_ON(true);
+#undef DFX_GATHER_ROWS_ON
 
-int parse_criteo_on(const TpScratch& ws, hipStream_t st, const char* text, int64_t nbytes,
-                    int is_train, int64_t max_rows, int64_t max_nnz, uint64_t* offset,
-                    uint64_t* index, float* label, int64_t* stat_dev) {
+int dfx::parse_criteo_on(const TpScratch& ws, hipStream_t st, const char* text, int64_t nbytes,
+                         int is_train, int64_t max_rows, int64_t max_nnz, uint64_t* offset,
+                         uint64_t* index, float* label, int64_t* stat_dev) {
   DFX_CHECK_ARG(nbytes >= 0 && nbytes < (1ll << 31),
                 "parse_criteo: positions are 32-bit, nbytes must be in [0, 2^31)");
   DFX_CHECK_ARG(max_rows >= 0 && max_nnz >= 0 && offset && stat_dev && (text || nbytes == 0) &&
@@ -449,14 +450,12 @@ int parse_criteo_on(const TpScratch& ws, hipStream_t st, const char* text, int64
   return DFX_OK;
 }
 
-int capacity_status(const int64_t* stat) {
+int dfx::capacity_status(const int64_t* stat) {
   if (!stat[3]) return DFX_OK;
   set_error("parse_criteo: the chunk needs " + std::to_string(stat[0]) + " rows and " +
             std::to_string(stat[1]) + " ids, more than the caller's capacity");
   return DFX_ERR_CAPACITY;
 }
-
-}  // namespace
 
 extern "C" int dfx_parse_criteo(dfx_ctx* ctx, const char* text_dev, int64_t nbytes, int is_train,
                                 int64_t max_rows, int64_t max_nnz, uint64_t* offset,
@@ -464,10 +463,8 @@ extern "C" int dfx_parse_criteo(dfx_ctx* ctx, const char* text_dev, int64_t nbyt
   DFX_CHECK_ARG(ctx, "null ctx");
   DFX_HIP(hipSetDevice(ctx->c.device));
   Context* c = &ctx->c;
-  const TpScratch ws{&c->tp_tiles, &c->tp_cells, &c->tp_lines, &c->tp_pair, &c->tp_tot,
-                     &c->tp_stat};
-  return parse_criteo_on(ws, input_stream(c), text_dev, nbytes, is_train, max_rows, max_nnz,
-                         offset, index, label, stat_dev);
+  return parse_criteo_on(context_scratch(c), input_stream(c), text_dev, nbytes, is_train,
+                         max_rows, max_nnz, offset, index, label, stat_dev);
 }
 
 extern "C" int dfx_parse_criteo_wait(dfx_ctx* ctx, const int64_t* stat_dev, int64_t* stat) {
@@ -499,533 +496,4 @@ extern "C" int dfx_gather_rows_valued(dfx_ctx* ctx, const uint64_t* src_offset,
   return gather_rows_on<true>(&ctx->c, input_stream(&ctx->c), src_offset, src_index, src_label,
                               rows_dev, begin, n, dst_offset, dst_index, dst_label, r0, src_value,
                               dst_value, src_rowflag, dst_rowflag);
-}
-
-// ---- the text feeder ----------------------------------------------------------------------------
-// A CSR of criteo rows on the device: at most 39 ids per row, so rows alone size it.  In the
-// libsvm mode (ensure_valued) it also holds values and row flags and has an nnz capacity of its
-// own, which grows on demand.
-namespace {
-struct DevCsr {
-  uint64_t *off = nullptr, *idx = nullptr;
-  float* lab = nullptr;
-  int64_t cap = 0;  // rows
-  float* val = nullptr;  // the libsvm mode
-  uint8_t* flag = nullptr;
-  int64_t nnz_cap = 0;
-  // room for rows / nnz; growth is x1.25 and keeps the first keep_rows rows and keep_nnz
-  // features: copied on st, in order behind whatever st holds that reads or writes the old
-  // arrays, and joined before they are freed
-  int ensure_valued(int64_t rows, int64_t nnz, hipStream_t st = nullptr, int64_t keep_rows = 0,
-                    int64_t keep_nnz = 0) {
-    if (off && val && rows <= cap && nnz <= nnz_cap) return DFX_OK;
-    const int64_t nr = off && rows <= cap ? cap : std::max<int64_t>(rows + rows / 4, 16);
-    const int64_t nn = val && nnz <= nnz_cap ? nnz_cap : std::max<int64_t>(nnz + nnz / 4, 64);
-    DevCsr n;
-    DFX_HIP(hipMalloc(&n.off, (size_t)(nr + 1) * 8));
-    DFX_HIP(hipMalloc(&n.idx, (size_t)nn * 8));
-    DFX_HIP(hipMalloc(&n.lab, (size_t)nr * 4));
-    DFX_HIP(hipMalloc(&n.val, (size_t)nn * 4));
-    DFX_HIP(hipMalloc(&n.flag, (size_t)nr));
-    n.cap = nr;
-    n.nnz_cap = nn;
-    if (st && off && val && (keep_rows || keep_nnz)) {
-      const hipMemcpyKind k = hipMemcpyDeviceToDevice;
-      DFX_HIP(hipMemcpyAsync(n.off, off, (size_t)(keep_rows + 1) * 8, k, st));
-      if (keep_rows) DFX_HIP(hipMemcpyAsync(n.lab, lab, (size_t)keep_rows * 4, k, st));
-      if (keep_rows) DFX_HIP(hipMemcpyAsync(n.flag, flag, (size_t)keep_rows, k, st));
-      if (keep_nnz) DFX_HIP(hipMemcpyAsync(n.idx, idx, (size_t)keep_nnz * 8, k, st));
-      if (keep_nnz) DFX_HIP(hipMemcpyAsync(n.val, val, (size_t)keep_nnz * 4, k, st));
-    }
-    if (st) DFX_HIP(hipStreamSynchronize(st));
-    release();
-    *this = n;
-    return DFX_OK;
-  }
-  int ensure(int64_t rows) {
-    if (rows <= cap && off) return DFX_OK;
-    release();
-    rows = std::max<int64_t>(rows + rows / 4, 16);
-    DFX_HIP(hipMalloc(&off, (size_t)(rows + 1) * 8));
-    DFX_HIP(hipMalloc(&idx, (size_t)rows * kCols * 8));
-    DFX_HIP(hipMalloc(&lab, (size_t)rows * 4));
-    cap = rows;
-    return DFX_OK;
-  }
-  void release() {
-    for (void* p : {(void*)off, (void*)idx, (void*)lab, (void*)val, (void*)flag})
-      if (p) (void)hipFree(p);
-    off = idx = nullptr;
-    lab = val = nullptr;
-    flag = nullptr;
-    cap = nnz_cap = 0;
-  }
-};
-}  // namespace
-
-// Two streams: the gathers run on `stream`, the context's input stream, which a step waits
-// for; uploads, parses and the copies back run on `up_stream`, so a later chunk's upload does
-// not sit between a batch's gathers and its step.  Events order the two: a gather waits for
-// its source chunk's `parsed`, a parse into a slot for the slot's last gather (`gathered`).
-struct dfx_textfeed {
-  dfx_ctx* ctx = nullptr;
-  hipStream_t stream = nullptr, up_stream = nullptr;
-  DevBuf tp[6];  // the parser's scratch on up_stream
-  struct Slot {
-    char *h_text = nullptr, *d_text = nullptr;
-    int64_t text_cap = 0;
-    DevCsr csr;
-    uint64_t* h_off = nullptr;  // pinned mirrors of the parsed offsets / labels / counts
-    float* h_lab = nullptr;
-    uint8_t* h_flag = nullptr;  // the libsvm mode: the row flags
-    int64_t mirror_cap = 0;
-    int64_t *d_stat = nullptr, *h_stat = nullptr;
-    int64_t rows = 0, nnz = 0;
-    hipEvent_t parsed = nullptr, consumed = nullptr, gathered = nullptr;
-  };
-  struct Ring {
-    DevCsr csr;
-    uint32_t *h_rows = nullptr, *d_rows = nullptr;  // the batch's row lists, appended
-    int64_t used = 0;
-    int64_t nnz = 0;  // the libsvm mode: features gathered into the batch so far
-    hipEvent_t consumed = nullptr;
-  };
-  std::vector<Slot> slot;
-  std::vector<Ring> ring;
-  DevCsr shuf;
-  int64_t shuf_nnz = 0;  // the libsvm mode: features in the shuffle buffer
-  int64_t batch_rows = 0;
-  int cur = -1;
-  int format = DFX_TEXT_CRITEO;
-};
-
-extern "C" int dfx_textfeed_destroy(dfx_textfeed* f) {
-  if (!f) return DFX_OK;
-  if (f->stream) (void)hipStreamSynchronize(f->stream);
-  if (f->up_stream) (void)hipStreamSynchronize(f->up_stream);
-  (void)hipDeviceSynchronize();
-  for (DevBuf& b : f->tp) b.release();
-  for (auto& s : f->slot) {
-    for (void* p : {(void*)s.h_text, (void*)s.h_off, (void*)s.h_lab, (void*)s.h_stat,
-                    (void*)s.h_flag})
-      if (p) (void)hipHostFree(p);
-    for (void* p : {(void*)s.d_text, (void*)s.d_stat})
-      if (p) (void)hipFree(p);
-    s.csr.release();
-    for (hipEvent_t e : {s.parsed, s.consumed, s.gathered})
-      if (e) (void)hipEventDestroy(e);
-  }
-  for (auto& r : f->ring) {
-    r.csr.release();
-    if (r.h_rows) (void)hipHostFree(r.h_rows);
-    if (r.d_rows) (void)hipFree(r.d_rows);
-    if (r.consumed) (void)hipEventDestroy(r.consumed);
-  }
-  f->shuf.release();
-  if (f->ctx) (void)dfx_ctx_set_input_stream(f->ctx, nullptr);
-  if (f->stream) (void)hipStreamDestroy(f->stream);
-  if (f->up_stream) (void)hipStreamDestroy(f->up_stream);
-  delete f;
-  return DFX_OK;
-}
-
-extern "C" int dfx_textfeed_create_fmt(dfx_ctx* ctx, int nslots, int nring, int64_t batch_rows,
-                                       int64_t shuf_rows, int format, dfx_textfeed** out) {
-  DFX_CHECK_ARG(ctx && out && nslots >= 2 && nslots <= 8 && nring >= 2 && nring <= 8 &&
-                    batch_rows > 0 && batch_rows < (1ll << 31) && shuf_rows >= 0 &&
-                    (format == DFX_TEXT_CRITEO || format == DFX_TEXT_LIBSVM),
-                "textfeed_create: bad argument");
-  DFX_HIP(hipSetDevice(ctx->c.device));
-  dfx_textfeed* f = new dfx_textfeed();
-  f->ctx = ctx;
-  f->format = format;
-  const bool valued = format == DFX_TEXT_LIBSVM;
-  f->batch_rows = batch_rows;
-  f->slot.resize((size_t)nslots);
-  f->ring.resize((size_t)nring);
-  auto fail = [&](const char* what) {
-    set_error(std::string("textfeed_create: ") + what);
-    dfx_textfeed_destroy(f);
-    return DFX_ERR_HIP;
-  };
-  if (hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithFlags(&f->up_stream, hipStreamNonBlocking) != hipSuccess)
-    return fail("stream");
-  for (auto& s : f->slot) {
-    if (hipEventCreateWithFlags(&s.parsed, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&s.gathered, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&s.consumed, hipEventDisableTiming) != hipSuccess)
-      return fail("event");
-    if (hipMalloc(&s.d_stat, 4 * sizeof(int64_t)) != hipSuccess ||
-        hipHostMalloc(&s.h_stat, 4 * sizeof(int64_t), hipHostMallocDefault) != hipSuccess)
-      return fail("counters");
-  }
-  for (auto& r : f->ring) {
-    if (hipEventCreateWithFlags(&r.consumed, hipEventDisableTiming) != hipSuccess)
-      return fail("event");
-    if ((valued ? r.csr.ensure_valued(batch_rows, batch_rows * kCols)
-                : r.csr.ensure(batch_rows)) != DFX_OK)
-      return fail("device batch");
-    if (hipHostMalloc(&r.h_rows, (size_t)batch_rows * 4, hipHostMallocDefault) != hipSuccess ||
-        hipMalloc(&r.d_rows, (size_t)batch_rows * 4) != hipSuccess)
-      return fail("row lists");
-  }
-  if (shuf_rows > 0 && (valued ? f->shuf.ensure_valued(shuf_rows, shuf_rows * kCols)
-                               : f->shuf.ensure(shuf_rows)) != DFX_OK)
-    return fail("shuffle buffer");
-  int rc = dfx_ctx_set_input_stream(ctx, f->stream);
-  if (rc != DFX_OK) {
-    dfx_textfeed_destroy(f);
-    return rc;
-  }
-  *out = f;
-  return DFX_OK;
-}
-
-extern "C" int dfx_textfeed_create(dfx_ctx* ctx, int nslots, int nring, int64_t batch_rows,
-                                   int64_t shuf_rows, dfx_textfeed** out) {
-  return dfx_textfeed_create_fmt(ctx, nslots, nring, batch_rows, shuf_rows, DFX_TEXT_CRITEO, out);
-}
-
-#define DFX_FEED_SLOT(f, s, what) \
-  DFX_CHECK_ARG((f) && (s) >= 0 && (s) < (int)(f)->slot.size(), what ": bad slot")
-#define DFX_FEED_FMT(f, fmt, what) \
-  DFX_CHECK_ARG((f) && (f)->format == (fmt), what ": not this feed's format")
-
-extern "C" int dfx_textfeed_text(dfx_textfeed* f, int slot, int64_t bytes, char** pinned) {
-  DFX_FEED_SLOT(f, slot, "textfeed_text");
-  DFX_CHECK_ARG(pinned && bytes >= 0 && bytes < (1ll << 31), "textfeed_text: bad argument");
-  DFX_HIP(hipSetDevice(f->ctx->c.device));
-  auto& s = f->slot[slot];
-  if (bytes > s.text_cap || !s.h_text) {
-    if (s.h_text) DFX_HIP(hipHostFree(s.h_text));
-    if (s.d_text) DFX_HIP(hipFree(s.d_text));
-    s.h_text = s.d_text = nullptr;
-    s.text_cap = 0;
-    const int64_t cap = std::max<int64_t>(bytes + bytes / 8, 4096);
-    DFX_HIP(hipHostMalloc(&s.h_text, (size_t)cap, hipHostMallocDefault));
-    DFX_HIP(hipMalloc(&s.d_text, (size_t)cap));
-    s.text_cap = cap;
-  }
-  *pinned = s.h_text;
-  return DFX_OK;
-}
-
-static int feed_slot_rows(dfx_textfeed* f, dfx_textfeed::Slot& s, int64_t rows) {
-  DFX_TRY(s.csr.ensure(rows));
-  if (rows > s.mirror_cap || !s.h_off) {
-    if (s.h_off) DFX_HIP(hipHostFree(s.h_off));
-    if (s.h_lab) DFX_HIP(hipHostFree(s.h_lab));
-    s.h_off = nullptr;
-    s.h_lab = nullptr;
-    s.mirror_cap = 0;
-    DFX_HIP(hipHostMalloc(&s.h_off, (size_t)(s.csr.cap + 1) * 8, hipHostMallocDefault));
-    DFX_HIP(hipHostMalloc(&s.h_lab, (size_t)s.csr.cap * 4, hipHostMallocDefault));
-    s.mirror_cap = s.csr.cap;
-  }
-  (void)f;
-  return DFX_OK;
-}
-
-extern "C" int dfx_textfeed_submit(dfx_textfeed* f, int slot, int64_t nbytes, int is_train,
-                                   int64_t max_rows) {
-  DFX_FEED_SLOT(f, slot, "textfeed_submit");
-  DFX_FEED_FMT(f, DFX_TEXT_CRITEO, "textfeed_submit");
-  auto& s = f->slot[slot];
-  DFX_CHECK_ARG(nbytes >= 0 && nbytes <= s.text_cap && max_rows >= 0,
-                "textfeed_submit: more bytes than dfx_textfeed_text reserved");
-  DFX_HIP(hipSetDevice(f->ctx->c.device));
-  DFX_TRY(feed_slot_rows(f, s, max_rows));
-  hipStream_t up = f->up_stream;
-  // the gathers that read the slot's previous chunk, and a step that took it as its batch,
-  // must be past the device
-  DFX_HIP(hipStreamWaitEvent(up, s.gathered, 0));
-  DFX_HIP(hipStreamWaitEvent(up, s.consumed, 0));
-  if (nbytes)
-    DFX_HIP(hipMemcpyAsync(s.d_text, s.h_text, (size_t)nbytes, hipMemcpyHostToDevice, up));
-  const TpScratch ws{&f->tp[0], &f->tp[1], &f->tp[2], &f->tp[3], &f->tp[4], &f->tp[5]};
-  DFX_TRY(parse_criteo_on(ws, up, s.d_text, nbytes, is_train, max_rows, max_rows * kCols,
-                          s.csr.off, s.csr.idx, s.csr.lab, s.d_stat));
-  // offsets and labels (12 bytes a row) for the batch planner, the counts
-  DFX_HIP(hipMemcpyAsync(s.h_off, s.csr.off, (size_t)(max_rows + 1) * 8, hipMemcpyDeviceToHost,
-                         up));
-  if (max_rows)
-    DFX_HIP(hipMemcpyAsync(s.h_lab, s.csr.lab, (size_t)max_rows * 4, hipMemcpyDeviceToHost, up));
-  DFX_HIP(hipMemcpyAsync(s.h_stat, s.d_stat, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, up));
-  DFX_HIP(hipEventRecord(s.parsed, up));
-  return DFX_OK;
-}
-
-extern "C" int dfx_textfeed_wait(dfx_textfeed* f, int slot, int64_t* stat,
-                                 const uint64_t** offset_host, const float** label_host) {
-  DFX_FEED_SLOT(f, slot, "textfeed_wait");
-  DFX_CHECK_ARG(stat, "textfeed_wait: null argument");
-  auto& s = f->slot[slot];
-  DFX_HIP(hipEventSynchronize(s.parsed));
-  for (int i = 0; i < 4; ++i) stat[i] = s.h_stat[i];
-  s.rows = stat[0];
-  s.nnz = stat[1];
-  if (offset_host) *offset_host = s.h_off;
-  if (label_host) *label_host = s.h_lab;
-  return capacity_status(stat);
-}
-
-extern "C" int dfx_textfeed_upload(dfx_textfeed* f, int slot, int64_t rows, int64_t nnz,
-                                   const uint64_t* offset, const uint64_t* index,
-                                   const float* label) {
-  DFX_FEED_SLOT(f, slot, "textfeed_upload");
-  DFX_FEED_FMT(f, DFX_TEXT_CRITEO, "textfeed_upload");
-  DFX_CHECK_ARG(rows >= 0 && nnz >= 0 && nnz <= rows * kCols && offset && (index || !nnz) &&
-                    (label || !rows),
-                "textfeed_upload: bad argument");
-  auto& s = f->slot[slot];
-  DFX_HIP(hipSetDevice(f->ctx->c.device));
-  hipStream_t up = f->up_stream;
-  if (rows > s.csr.cap) {
-    DFX_HIP(hipStreamSynchronize(up));
-    DFX_TRY(feed_slot_rows(f, s, rows));
-  }
-  // after the slot's own parse (dfx_textfeed_wait joined it); the gathers wait for `parsed`
-  DFX_HIP(hipMemcpyAsync(s.csr.off, offset, (size_t)(rows + 1) * 8, hipMemcpyHostToDevice, up));
-  if (nnz) DFX_HIP(hipMemcpyAsync(s.csr.idx, index, (size_t)nnz * 8, hipMemcpyHostToDevice, up));
-  if (rows) {
-    DFX_HIP(hipMemcpyAsync(s.csr.lab, label, (size_t)rows * 4, hipMemcpyHostToDevice, up));
-    std::copy(label, label + rows, s.h_lab);
-  }
-  std::copy(offset, offset + rows + 1, s.h_off);
-  // the caller's arrays are pageable: staged before the calls return
-  DFX_HIP(hipEventRecord(s.parsed, up));
-  s.rows = rows;
-  s.nnz = nnz;
-  return DFX_OK;
-}
-
-extern "C" int dfx_textfeed_batch_begin(dfx_textfeed* f) {
-  DFX_CHECK_ARG(f, "textfeed_batch_begin: null argument");
-  f->cur = (f->cur + 1) % (int)f->ring.size();
-  auto& r = f->ring[f->cur];
-  // the step that consumed this ring entry a round ago must be past the device (its row lists
-  // are pinned host memory the gathers' copies read)
-  DFX_HIP(hipEventSynchronize(r.consumed));
-  r.used = 0;
-  return DFX_OK;
-}
-
-extern "C" int dfx_textfeed_gather(dfx_textfeed* f, int src, int to_batch, const uint32_t* rows,
-                                   int64_t begin, int64_t n, int64_t r0) {
-  DFX_CHECK_ARG(f && src >= -1 && src < (int)f->slot.size() && n >= 0 && r0 >= 0 && begin >= 0,
-                "textfeed_gather: bad argument");
-  DFX_CHECK_ARG(!to_batch || f->cur >= 0, "textfeed_gather: no batch begun");
-  DFX_CHECK_ARG(src >= 0 || to_batch, "textfeed_gather: the shuffle buffer onto itself");
-  DFX_FEED_FMT(f, DFX_TEXT_CRITEO, "textfeed_gather");
-  if (n == 0) return DFX_OK;
-  DFX_HIP(hipSetDevice(f->ctx->c.device));
-  const DevCsr& S = src >= 0 ? f->slot[src].csr : f->shuf;
-  const DevCsr& D = to_batch ? f->ring[f->cur].csr : f->shuf;
-  DFX_CHECK_ARG(r0 + n <= D.cap, "textfeed_gather: more rows than the destination holds");
-  const uint32_t* rows_dev = nullptr;
-  if (rows) {
-    DFX_CHECK_ARG(to_batch, "textfeed_gather: row lists go to the batch");
-    auto& r = f->ring[f->cur];
-    DFX_CHECK_ARG(r.used + n <= f->batch_rows, "textfeed_gather: row lists past the batch size");
-    std::copy(rows, rows + n, r.h_rows + r.used);
-    DFX_HIP(hipMemcpyAsync(r.d_rows + r.used, r.h_rows + r.used, (size_t)n * 4,
-                           hipMemcpyHostToDevice, f->stream));
-    rows_dev = r.d_rows + r.used;
-    r.used += n;
-  }
-  if (src >= 0) DFX_HIP(hipStreamWaitEvent(f->stream, f->slot[src].parsed, 0));
-  DFX_TRY(gather_rows_on<false>(&f->ctx->c, f->stream, S.off, S.idx, S.lab, rows_dev, begin, n,
-                                D.off, D.idx, D.lab, r0));
-  if (src >= 0) DFX_HIP(hipEventRecord(f->slot[src].gathered, f->stream));
-  return DFX_OK;
-}
-
-extern "C" int dfx_textfeed_batch_end(dfx_textfeed* f, int64_t rows, int64_t nnz, dfx_batch* out) {
-  DFX_CHECK_ARG(f && out && f->cur >= 0 && rows >= 0 && nnz >= 0, "textfeed_batch_end: bad argument");
-  const DevCsr& D = f->ring[f->cur].csr;
-  *out = dfx_batch{};
-  out->size = rows;
-  out->nnz = nnz;
-  out->offset = D.off;
-  out->index = D.idx;
-  out->label = D.lab;
-  return DFX_OK;
-}
-
-extern "C" int dfx_textfeed_consumed(dfx_textfeed* f) {
-  DFX_CHECK_ARG(f && f->cur >= 0, "textfeed_consumed: no batch begun");
-  DFX_HIP(hipEventRecord(f->ring[f->cur].consumed, f->ctx->c.stream));
-  return DFX_OK;
-}
-
-extern "C" int dfx_textfeed_slot_batch(dfx_textfeed* f, int slot, dfx_batch* out) {
-  DFX_FEED_SLOT(f, slot, "textfeed_slot_batch");
-  DFX_CHECK_ARG(out, "textfeed_slot_batch: null argument");
-  const auto& s = f->slot[slot];
-  // the step waits for the input stream, the input stream for the chunk's parse
-  DFX_HIP(hipStreamWaitEvent(f->stream, s.parsed, 0));
-  *out = dfx_batch{};
-  out->size = s.rows;
-  out->nnz = s.nnz;
-  out->offset = s.csr.off;
-  out->index = s.csr.idx;
-  out->label = s.csr.lab;
-  return DFX_OK;
-}
-
-extern "C" int dfx_textfeed_slot_consumed(dfx_textfeed* f, int slot) {
-  DFX_FEED_SLOT(f, slot, "textfeed_slot_consumed");
-  DFX_HIP(hipEventRecord(f->slot[slot].consumed, f->ctx->c.stream));
-  return DFX_OK;
-}
-
-// ---- the libsvm mode ------------------------------------------------------------------------------
-// The same slots, shuffle buffer and ring with values and row flags beside the ids.  A row has
-// any number of features, so every CSR has an nnz capacity of its own: a slot's is the caller's
-// bound for its chunk, the shuffle buffer's and a ring entry's grow on demand (x1.25) and keep
-// their contents.
-static int feed_slot_valued(dfx_textfeed::Slot& s, int64_t rows, int64_t nnz) {
-  DFX_TRY(s.csr.ensure_valued(rows, nnz));
-  if (s.csr.cap > s.mirror_cap || !s.h_off || !s.h_flag) {
-    for (void* p : {(void*)s.h_off, (void*)s.h_lab, (void*)s.h_flag})
-      if (p) DFX_HIP(hipHostFree(p));
-    s.h_off = nullptr;
-    s.h_lab = nullptr;
-    s.h_flag = nullptr;
-    s.mirror_cap = 0;
-    DFX_HIP(hipHostMalloc(&s.h_off, (size_t)(s.csr.cap + 1) * 8, hipHostMallocDefault));
-    DFX_HIP(hipHostMalloc(&s.h_lab, (size_t)s.csr.cap * 4, hipHostMallocDefault));
-    DFX_HIP(hipHostMalloc(&s.h_flag, (size_t)s.csr.cap, hipHostMallocDefault));
-    s.mirror_cap = s.csr.cap;
-  }
-  return DFX_OK;
-}
-
-extern "C" int dfx_textfeed_submit_libsvm(dfx_textfeed* f, int slot, int64_t nbytes,
-                                          int64_t max_rows, int64_t max_nnz) {
-  DFX_FEED_SLOT(f, slot, "textfeed_submit_libsvm");
-  DFX_FEED_FMT(f, DFX_TEXT_LIBSVM, "textfeed_submit_libsvm");
-  auto& s = f->slot[slot];
-  DFX_CHECK_ARG(nbytes >= 0 && nbytes <= s.text_cap && max_rows >= 0 && max_nnz >= 0,
-                "textfeed_submit_libsvm: more bytes than dfx_textfeed_text reserved");
-  DFX_HIP(hipSetDevice(f->ctx->c.device));
-  DFX_TRY(feed_slot_valued(s, max_rows, max_nnz));
-  hipStream_t up = f->up_stream;
-  DFX_HIP(hipStreamWaitEvent(up, s.gathered, 0));
-  DFX_HIP(hipStreamWaitEvent(up, s.consumed, 0));
-  if (nbytes)
-    DFX_HIP(hipMemcpyAsync(s.d_text, s.h_text, (size_t)nbytes, hipMemcpyHostToDevice, up));
-  DFX_TRY(parse_libsvm_on(&f->tp[0], &f->tp[5], up, s.d_text, nbytes, max_rows, max_nnz,
-                          s.csr.off, s.csr.idx, s.csr.val, s.csr.lab, s.csr.flag, s.d_stat));
-  // offsets, labels and row flags (13 bytes a row) for the batch planner, the counts
-  DFX_HIP(hipMemcpyAsync(s.h_off, s.csr.off, (size_t)(max_rows + 1) * 8, hipMemcpyDeviceToHost,
-                         up));
-  if (max_rows) {
-    DFX_HIP(hipMemcpyAsync(s.h_lab, s.csr.lab, (size_t)max_rows * 4, hipMemcpyDeviceToHost, up));
-    DFX_HIP(hipMemcpyAsync(s.h_flag, s.csr.flag, (size_t)max_rows, hipMemcpyDeviceToHost, up));
-  }
-  DFX_HIP(hipMemcpyAsync(s.h_stat, s.d_stat, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, up));
-  DFX_HIP(hipEventRecord(s.parsed, up));
-  return DFX_OK;
-}
-
-extern "C" int dfx_textfeed_wait_valued(dfx_textfeed* f, int slot, int64_t* stat,
-                                        const uint64_t** offset_host, const float** label_host,
-                                        const uint8_t** rowflag_host) {
-  DFX_FEED_SLOT(f, slot, "textfeed_wait_valued");
-  if (rowflag_host) *rowflag_host = f->slot[slot].h_flag;
-  return dfx_textfeed_wait(f, slot, stat, offset_host, label_host);
-}
-
-extern "C" int dfx_textfeed_upload_valued(dfx_textfeed* f, int slot, int64_t rows, int64_t nnz,
-                                          const uint64_t* offset, const uint64_t* index,
-                                          const float* value, const float* label) {
-  DFX_FEED_SLOT(f, slot, "textfeed_upload_valued");
-  DFX_FEED_FMT(f, DFX_TEXT_LIBSVM, "textfeed_upload_valued");
-  DFX_CHECK_ARG(rows >= 0 && nnz >= 0 && offset && ((index && value) || !nnz) &&
-                    (label || !rows) && offset[0] == 0 && (int64_t)offset[rows] == nnz,
-                "textfeed_upload_valued: bad argument");
-  auto& s = f->slot[slot];
-  DFX_HIP(hipSetDevice(f->ctx->c.device));
-  hipStream_t up = f->up_stream;
-  if (rows > s.csr.cap || nnz > s.csr.nnz_cap || !s.h_flag) {
-    DFX_HIP(hipStreamSynchronize(up));
-    DFX_TRY(feed_slot_valued(s, rows, nnz));
-  }
-  // after the slot's own parse (dfx_textfeed_wait joined it); the gathers wait for `parsed`
-  std::copy(offset, offset + rows + 1, s.h_off);
-  if (rows) std::copy(label, label + rows, s.h_lab);
-  for (int64_t r = 0; r < rows; ++r) {  // the row flags: a value that is not 1.0f
-    uint8_t fl = 0;
-    for (uint64_t k = offset[r]; k < offset[r + 1] && !fl; ++k) fl = value[k] != 1.f;
-    s.h_flag[r] = fl;
-  }
-  DFX_HIP(hipMemcpyAsync(s.csr.off, s.h_off, (size_t)(rows + 1) * 8, hipMemcpyHostToDevice, up));
-  if (nnz) DFX_HIP(hipMemcpyAsync(s.csr.idx, index, (size_t)nnz * 8, hipMemcpyHostToDevice, up));
-  if (nnz)
-    DFX_HIP(hipMemcpyAsync(s.csr.val, value, (size_t)nnz * 4, hipMemcpyHostToDevice, up));
-  if (rows) {
-    DFX_HIP(hipMemcpyAsync(s.csr.lab, s.h_lab, (size_t)rows * 4, hipMemcpyHostToDevice, up));
-    DFX_HIP(hipMemcpyAsync(s.csr.flag, s.h_flag, (size_t)rows, hipMemcpyHostToDevice, up));
-  }
-  DFX_HIP(hipEventRecord(s.parsed, up));
-  s.rows = rows;
-  s.nnz = nnz;
-  return DFX_OK;
-}
-
-extern "C" int dfx_textfeed_gather_valued(dfx_textfeed* f, int src, int to_batch,
-                                          const uint32_t* rows, int64_t begin, int64_t n,
-                                          int64_t r0, int64_t nnz) {
-  DFX_CHECK_ARG(f && src >= -1 && src < (int)f->slot.size() && n >= 0 && r0 >= 0 && begin >= 0 &&
-                    nnz >= 0,
-                "textfeed_gather_valued: bad argument");
-  DFX_FEED_FMT(f, DFX_TEXT_LIBSVM, "textfeed_gather_valued");
-  DFX_CHECK_ARG(!to_batch || f->cur >= 0, "textfeed_gather_valued: no batch begun");
-  DFX_CHECK_ARG(src >= 0 || to_batch, "textfeed_gather_valued: the shuffle buffer onto itself");
-  if (n == 0) return DFX_OK;
-  DFX_HIP(hipSetDevice(f->ctx->c.device));
-  const DevCsr& S = src >= 0 ? f->slot[src].csr : f->shuf;
-  DevCsr& D = to_batch ? f->ring[f->cur].csr : f->shuf;
-  int64_t& used = to_batch ? f->ring[f->cur].nnz : f->shuf_nnz;
-  DFX_CHECK_ARG(r0 + n <= D.cap, "textfeed_gather_valued: more rows than the destination holds");
-  if (r0 == 0) used = 0;
-  // the copies of a growth run on the gathers' stream: behind the gathers that filled the old
-  // arrays and, for the shuffle buffer, behind the gathers that read them
-  DFX_TRY(D.ensure_valued(D.cap, used + nnz, f->stream, r0, used));
-  used += nnz;
-  const uint32_t* rows_dev = nullptr;
-  if (rows) {
-    DFX_CHECK_ARG(to_batch, "textfeed_gather_valued: row lists go to the batch");
-    auto& r = f->ring[f->cur];
-    DFX_CHECK_ARG(r.used + n <= f->batch_rows,
-                  "textfeed_gather_valued: row lists past the batch size");
-    std::copy(rows, rows + n, r.h_rows + r.used);
-    DFX_HIP(hipMemcpyAsync(r.d_rows + r.used, r.h_rows + r.used, (size_t)n * 4,
-                           hipMemcpyHostToDevice, f->stream));
-    rows_dev = r.d_rows + r.used;
-    r.used += n;
-  }
-  if (src >= 0) DFX_HIP(hipStreamWaitEvent(f->stream, f->slot[src].parsed, 0));
-  DFX_TRY(gather_rows_on<true>(&f->ctx->c, f->stream, S.off, S.idx, S.lab, rows_dev, begin, n,
-                               D.off, D.idx, D.lab, r0, S.val, D.val, S.flag, D.flag));
-  if (src >= 0) DFX_HIP(hipEventRecord(f->slot[src].gathered, f->stream));
-  return DFX_OK;
-}
-
-extern "C" int dfx_textfeed_batch_end_valued(dfx_textfeed* f, int64_t rows, int64_t nnz,
-                                             int valued, dfx_batch* out) {
-  DFX_TRY(dfx_textfeed_batch_end(f, rows, nnz, out));
-  DFX_FEED_FMT(f, DFX_TEXT_LIBSVM, "textfeed_batch_end_valued");
-  out->value = valued ? f->ring[f->cur].csr.val : nullptr;
-  return DFX_OK;
-}
-
-extern "C" int dfx_textfeed_slot_batch_valued(dfx_textfeed* f, int slot, int valued,
-                                              dfx_batch* out) {
-  DFX_TRY(dfx_textfeed_slot_batch(f, slot, out));
-  DFX_FEED_FMT(f, DFX_TEXT_LIBSVM, "textfeed_slot_batch_valued");
-  out->value = valued ? f->slot[slot].csr.val : nullptr;
-  return DFX_OK;
 }

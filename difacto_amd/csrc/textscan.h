@@ -1,17 +1,40 @@
 // The scan helpers of the device text parsers (textparse.hip: Criteo, the row gather;
 // libsvmparse.hip: libsvm): a block scan, the plain multi-launch scan (tile totals, a scan of
-// the totals, apply - no look-back, nothing spins) and the launch helpers.  Everything sits in
-// an unnamed namespace: each .hip file that includes this gets kernels of its own.
+// the totals, apply - no look-back, nothing spins) and the launch helpers.  These sit in an
+// unnamed namespace: each .hip file that uses them gets kernels of its own.  In front of them:
+// what the text feed (textfeed.hip) calls of the two parsers and the gather.
 #pragma once
 #include "internal.h"
 
 namespace dfx {
-// dfx_parse_libsvm on a stream and scratch of the caller's choice (libsvmparse.hip); the text
-// feeder's parses run on a stream of their own
-int parse_libsvm_on(DevBuf* tiles_buf, DevBuf* stat_buf, hipStream_t st, const char* text,
-                    int64_t nbytes, int64_t max_rows, int64_t max_nnz, uint64_t* offset,
-                    uint64_t* index, float* value, float* label, uint8_t* rowflag,
-                    int64_t* stat_dev);
+constexpr int kCols = 39;  // criteo feature columns (13 integer + 26 categorical)
+
+// a parser's scratch: the context's own set (dfx_parse_criteo / dfx_parse_libsvm, on the input
+// stream) or a text feed's (textfeed.hip; its parses run on a stream of their own).  The libsvm
+// parser uses tiles and stat only.
+struct TpScratch {
+  DevBuf *tiles, *cells, *lines, *pair, *tot, *stat;
+};
+// the parsers and the row gather on a stream of the caller's choice (textparse.hip,
+// libsvmparse.hip); capacity_status: DFX_ERR_CAPACITY when the stat a parser left says overflow
+int parse_criteo_on(const TpScratch& ws, hipStream_t st, const char* text, int64_t nbytes,
+                    int is_train, int64_t max_rows, int64_t max_nnz, uint64_t* offset,
+                    uint64_t* index, float* label, int64_t* stat_dev);
+int parse_libsvm_on(const TpScratch& ws, hipStream_t st, const char* text, int64_t nbytes,
+                    int64_t max_rows, int64_t max_nnz, uint64_t* offset, uint64_t* index,
+                    float* value, float* label, uint8_t* rowflag, int64_t* stat_dev);
+int capacity_status(const int64_t* stat);
+template <bool kValued>
+int gather_rows_on(Context* c, hipStream_t st, const uint64_t* src_offset,
+                   const uint64_t* src_index, const float* src_label, const uint32_t* rows_dev,
+                   int64_t begin, int64_t n, uint64_t* dst_offset, uint64_t* dst_index,
+                   float* dst_label, int64_t r0, const float* src_value = nullptr,
+                   float* dst_value = nullptr, const uint8_t* src_flag = nullptr,
+                   uint8_t* dst_flag = nullptr);
+inline TpScratch context_scratch(Context* c) {
+  return TpScratch{&c->tp_tiles, &c->tp_cells, &c->tp_lines,
+                   &c->tp_pair,  &c->tp_tot,   &c->tp_stat};
+}
 }  // namespace dfx
 
 namespace {

@@ -16,10 +16,12 @@ static double Seconds() {
 
 DeviceTextFeed::DeviceTextFeed(dfx_ctx* ctx, size_t batch_size, size_t shuf_buf,
                                const std::string& format)
-    : batch_size_(batch_size ? batch_size : 1), shuf_buf_(shuf_buf), libsvm_(format == "libsvm") {
-  DfxCheck(dfx_textfeed_create_fmt(ctx, kSlots, kRing, (int64_t)batch_size_, (int64_t)shuf_buf_,
-                                   libsvm_ ? DFX_TEXT_LIBSVM : DFX_TEXT_CRITEO, &h_),
-           "dfx_textfeed_create_fmt");
+    : batch_size_(batch_size ? batch_size : 1),
+      shuf_buf_(shuf_buf),
+      format_(format == "libsvm" ? DFX_TEXT_LIBSVM : DFX_TEXT_CRITEO) {
+  DfxCheck(dfx_textfeed_create(ctx, kSlots, kRing, (int64_t)batch_size_, (int64_t)shuf_buf_,
+                               format_, &h_),
+           "dfx_textfeed_create");
 }
 
 DeviceTextFeed::~DeviceTextFeed() {
@@ -82,12 +84,12 @@ DeviceBatchReader::DeviceBatchReader(DeviceTextFeed* feed, const std::string& pa
     : f_(feed->h()),
       reader_(path, format, part, nparts, chunk_bytes, nthreads, 0),
       train_(format != "criteo_test"),
-      libsvm_(format == "libsvm"),
+      valued_(feed->valued()),
       batch_size_(batch_size),
       nthreads_(nthreads < 1 ? 1 : nthreads) {
   DFX_HOST_CHECK(format == "criteo" || format == "criteo_test" || format == "libsvm",
                  "the device reader parses criteo, criteo_test and libsvm, not " + format);
-  DFX_HOST_CHECK(libsvm_ == feed->libsvm(), "the text feed was created for another format");
+  DFX_HOST_CHECK((format == "libsvm") == valued_, "the text feed was created for another format");
   DFX_HOST_CHECK(batch_size <= feed->batch_size() && shuf_buf <= feed->shuf_buf(),
                  "batch or shuffle buffer larger than the text feed's");
   if (batch_size_) {
@@ -96,14 +98,7 @@ DeviceBatchReader::DeviceBatchReader(DeviceTextFeed* feed, const std::string& pa
         [this](size_t* rows, const uint64_t** off, const float** lab) {
           return FetchChunk(rows, off, lab);
         },
-        [this](const GatherOp& op) {
-          if (libsvm_) return Gather(op);
-          const int src = op.src == GatherOp::kShuffle ? -1 : seq_slot_[op.src];
-          DfxCheck(dfx_textfeed_gather(f_, src, op.to_batch ? 1 : 0,
-                                       op.rows.empty() ? nullptr : op.rows.data(),
-                                       (int64_t)op.begin, (int64_t)op.n, (int64_t)op.r0),
-                   "dfx_textfeed_gather");
-        }));
+        [this](const GatherOp& op) { Gather(op); }));
   }
   for (int s = 0; s < DeviceTextFeed::kSlots; ++s) free_.push_back(s);
   loader_ = std::thread([this]() { Load(); });
@@ -119,7 +114,7 @@ DeviceBatchReader::~DeviceBatchReader() {
   // parses still in flight read the slots' pinned text
   for (const Filled& c : submitted_) {
     int64_t stat[4];
-    (void)dfx_textfeed_wait(f_, c.slot, stat, nullptr, nullptr);
+    (void)dfx_textfeed_wait(f_, c.slot, stat, nullptr, nullptr, nullptr);
   }
 }
 
@@ -147,7 +142,7 @@ void DeviceBatchReader::Load() {
     DfxCheck(dfx_textfeed_text(f_, slot, (int64_t)size, &dst), "dfx_textfeed_text");
     const double t0 = Seconds();
     size_t blanks = 0;
-    const size_t nl = CopyCountLines(dst, data, size, nthreads_, libsvm_ ? &blanks : nullptr);
+    const size_t nl = CopyCountLines(dst, data, size, nthreads_, valued_ ? &blanks : nullptr);
     {
       std::lock_guard<std::mutex> lk(mu_);
       times_.copy += Seconds() - t0;
@@ -170,15 +165,10 @@ void DeviceBatchReader::SubmitFilled(bool wait) {
   }
   for (const Filled& c : take) {
     // rows <= lines <= newlines: whole lines, the last one terminated (TextReader::NextRaw);
-    // libsvm: a feature follows a blank
-    if (libsvm_)
-      DfxCheck(dfx_textfeed_submit_libsvm(f_, c.slot, (int64_t)c.bytes, (int64_t)c.newlines,
-                                          (int64_t)c.blanks),
-               "dfx_textfeed_submit_libsvm");
-    else
-      DfxCheck(dfx_textfeed_submit(f_, c.slot, (int64_t)c.bytes, train_ ? 1 : 0,
-                                   (int64_t)c.newlines),
-               "dfx_textfeed_submit");
+    // libsvm: a feature follows a blank (the loader counts blanks for a valued feed only)
+    DfxCheck(dfx_textfeed_submit(f_, c.slot, (int64_t)c.bytes, train_ ? 1 : 0,
+                                 (int64_t)c.newlines, (int64_t)c.blanks),
+             "dfx_textfeed_submit");
     submitted_.push_back(c);
   }
 }
@@ -204,12 +194,7 @@ bool DeviceBatchReader::FetchChunk(size_t* rows, const uint64_t** off, const flo
   submitted_.pop_front();
   int64_t stat[4];
   const double t0 = Seconds();
-  chunk_flag_ = nullptr;
-  if (libsvm_)
-    DfxCheck(dfx_textfeed_wait_valued(f_, c.slot, stat, off, lab, &chunk_flag_),
-             "dfx_textfeed_wait_valued");
-  else
-    DfxCheck(dfx_textfeed_wait(f_, c.slot, stat, off, lab), "dfx_textfeed_wait");
+  DfxCheck(dfx_textfeed_wait(f_, c.slot, stat, off, lab, &chunk_flag_), "dfx_textfeed_wait");
   times_.wait_parse += Seconds() - t0;
   SubmitFilled(false);  // slots filled meanwhile: their parses run beside this chunk's batches
   *rows = (size_t)stat[0];
@@ -219,24 +204,13 @@ bool DeviceBatchReader::FetchChunk(size_t* rows, const uint64_t** off, const flo
     DfxCheck(dfx_textfeed_text(f_, c.slot, (int64_t)c.bytes, &text), "dfx_textfeed_text");
     reader_.ParseChunk(text, c.bytes, &host_blk_);
     static_assert(sizeof(size_t) == sizeof(uint64_t), "size_t offsets");
-    if (libsvm_) {
-      DfxCheck(dfx_textfeed_upload_valued(
-                   f_, c.slot, (int64_t)host_blk_.Size(), (int64_t)host_blk_.index.size(),
-                   reinterpret_cast<const uint64_t*>(host_blk_.offset.data()),
-                   host_blk_.index.data(), host_blk_.value.data(), host_blk_.label.data()),
-               "dfx_textfeed_upload_valued");
-      host_flag_.assign(host_blk_.Size(), 0);
-      for (size_t r = 0; r < host_blk_.Size(); ++r)
-        for (size_t k = host_blk_.offset[r]; k < host_blk_.offset[r + 1] && !host_flag_[r]; ++k)
-          host_flag_[r] = host_blk_.value[k] != 1.f;
-      chunk_flag_ = host_flag_.data();
-    } else {
-      DfxCheck(dfx_textfeed_upload(f_, c.slot, (int64_t)host_blk_.Size(),
-                                   (int64_t)host_blk_.index.size(),
-                                   reinterpret_cast<const uint64_t*>(host_blk_.offset.data()),
-                                   host_blk_.index.data(), host_blk_.label.data()),
-               "dfx_textfeed_upload");
-    }
+    DfxCheck(dfx_textfeed_upload(f_, c.slot, (int64_t)host_blk_.Size(),
+                                 (int64_t)host_blk_.index.size(),
+                                 reinterpret_cast<const uint64_t*>(host_blk_.offset.data()),
+                                 host_blk_.index.data(),
+                                 valued_ ? host_blk_.value.data() : nullptr,
+                                 host_blk_.label.data(), &chunk_flag_),
+             "dfx_textfeed_upload");
     *rows = host_blk_.Size();
     *off = reinterpret_cast<const uint64_t*>(host_blk_.offset.data());
     *lab = host_blk_.label.data();
@@ -249,9 +223,18 @@ bool DeviceBatchReader::FetchChunk(size_t* rows, const uint64_t** off, const flo
   return true;
 }
 
-// libsvm: the copy's nnz from the mirrored row lengths, the flags carried along
+// one copy of the plan; a valued feed: its nnz from the mirrored row lengths, the flags carried
+// along
 void DeviceBatchReader::Gather(const GatherOp& op) {
   const bool from_shuf = op.src == GatherOp::kShuffle;
+  const size_t nnz = valued_ ? MirrorRows(op, from_shuf) : 0;
+  DfxCheck(dfx_textfeed_gather(f_, from_shuf ? -1 : seq_slot_[op.src], op.to_batch ? 1 : 0,
+                               op.rows.empty() ? nullptr : op.rows.data(), (int64_t)op.begin,
+                               (int64_t)op.n, (int64_t)op.r0, (int64_t)nnz),
+           "dfx_textfeed_gather");
+}
+
+size_t DeviceBatchReader::MirrorRows(const GatherOp& op, bool from_shuf) {
   auto len = [&](size_t j) {
     return from_shuf ? (size_t)shuf_len_[j] : (size_t)(chunk_off_[j + 1] - chunk_off_[j]);
   };
@@ -275,11 +258,7 @@ void DeviceBatchReader::Gather(const GatherOp& op) {
       shuf_flag_.push_back(flag(j));
     }
   }
-  DfxCheck(dfx_textfeed_gather_valued(f_, from_shuf ? -1 : seq_slot_[op.src], op.to_batch ? 1 : 0,
-                                      op.rows.empty() ? nullptr : op.rows.data(),
-                                      (int64_t)op.begin, (int64_t)op.n, (int64_t)op.r0,
-                                      (int64_t)nnz),
-           "dfx_textfeed_gather_valued");
+  return nnz;
 }
 
 bool DeviceBatchReader::Next() {
@@ -290,14 +269,10 @@ bool DeviceBatchReader::Next() {
     do {
       if (!FetchChunk(&rows, &off, &lab)) return false;
     } while (rows == 0);
-    if (libsvm_) {
-      bool valued = false;
-      for (size_t r = 0; r < chunk_rows_ && !valued; ++r) valued = chunk_flag_[r];
-      DfxCheck(dfx_textfeed_slot_batch_valued(f_, cur_slot_, valued ? 1 : 0, &batch_),
-               "dfx_textfeed_slot_batch_valued");
-    } else {
-      DfxCheck(dfx_textfeed_slot_batch(f_, cur_slot_, &batch_), "dfx_textfeed_slot_batch");
-    }
+    bool valued = false;  // no flags (a Criteo feed), no loop
+    for (size_t r = 0; chunk_flag_ && r < chunk_rows_ && !valued; ++r) valued = chunk_flag_[r];
+    DfxCheck(dfx_textfeed_slot_batch(f_, cur_slot_, valued ? 1 : 0, &batch_),
+             "dfx_textfeed_slot_batch");
     slot_batch_ = true;
     return true;
   }
@@ -307,13 +282,9 @@ bool DeviceBatchReader::Next() {
   size_t rows, nnz;
   batch_valued_ = false;
   if (!planner_->Next(&rows, &nnz)) return false;
-  if (libsvm_)
-    DfxCheck(dfx_textfeed_batch_end_valued(f_, (int64_t)rows, (int64_t)nnz, batch_valued_ ? 1 : 0,
-                                           &batch_),
-             "dfx_textfeed_batch_end_valued");
-  else
-    DfxCheck(dfx_textfeed_batch_end(f_, (int64_t)rows, (int64_t)nnz, &batch_),
-             "dfx_textfeed_batch_end");
+  DfxCheck(
+      dfx_textfeed_batch_end(f_, (int64_t)rows, (int64_t)nnz, batch_valued_ ? 1 : 0, &batch_),
+      "dfx_textfeed_batch_end");
   slot_batch_ = false;
   return true;
 }

@@ -2,10 +2,11 @@
 //
 // The host reader (reader.h) tokenises, hashes and copies every row on CPU threads.  Here the
 // host's per-byte work is one copy of the raw chunk into pinned memory; the device parses it
-// (dfx_parse_criteo), the batch planner (reader.h BatchPlanner) runs on the host from the
-// parsed chunk's offsets and labels (12 bytes a row), and the row copies of the plan run on
-// the device (dfx_gather_rows) into a ring of device batches — the batches BatchReader forms
-// (src/reader/batch_reader.cc:29-78) for the chunks TextReader cuts (src/reader/reader.h:18-55).
+// (dfx_parse_criteo / dfx_parse_libsvm), the batch planner (reader.h BatchPlanner) runs on the
+// host from the parsed chunk's offsets and labels (12 bytes a row), and the row copies of the
+// plan run on the device (dfx_gather_rows) into a ring of device batches — the batches
+// BatchReader forms (src/reader/batch_reader.cc:29-78) for the chunks TextReader cuts
+// (src/reader/reader.h:18-55).
 //
 //   loader thread   TextReader::NextRaw -> parallel copy into a pinned text slot, counting
 //                   newlines (max_rows; 39 ids a row at most size the rest)
@@ -14,16 +15,16 @@
 //                   chunk's batches train; the planner and its gathers per Next()
 //
 // A chunk the device flags (needs_host: the forms listed in include/difacto_amd.h) is parsed
-// by ParseCriteo on the host and uploaded into the same device arrays; FallbackChunks counts
-// them.
+// by TextReader::ParseChunk on the host and uploaded into the same device arrays, values
+// included; FallbackChunks counts them.
 //
-// libsvm (dfx_parse_libsvm, the feed's libsvm mode): rows have any number of features and carry
-// values.  The loader also counts the chunk's blanks, which bound its features; the reader
-// mirrors row lengths and the parser's row flags (a row holding a value that is not 1.0f)
-// through the GatherOps it carries out, chunk -> shuffle buffer -> batch, so it knows every
-// copy's nnz (the feed sizes its arrays by it) and hands a batch out with values iff one of its
-// rows is flagged: BatchReader::Next's all-ones test (batch_reader.cc:71-73) with no device
-// read-back.  A flagged chunk goes through ParseLibSVM and is uploaded values included.
+// The feed's format decides what its calls do; the reader only carries more data when the feed
+// is valued (libsvm: rows have any number of features and carry values).  The loader then also
+// counts the chunk's blanks, which bound its features; the reader mirrors row lengths and the
+// row flags the feed hands out (a row holding a value that is not 1.0f) through the GatherOps it
+// carries out, chunk -> shuffle buffer -> batch, so it knows every copy's nnz (the feed sizes
+// its arrays by it) and hands a batch out with values iff one of its rows is flagged:
+// BatchReader::Next's all-ones test (batch_reader.cc:71-73) with no device read-back.
 // criteo, criteo_test and libsvm only.
 #ifndef DIFACTO_AMD_HOST_DEVICE_READER_H_
 #define DIFACTO_AMD_HOST_DEVICE_READER_H_
@@ -47,7 +48,7 @@ namespace difacto {
 class DeviceTextFeed {
  public:
   static constexpr int kSlots = 3, kRing = 3;
-  /** format: "libsvm" takes the feed's libsvm mode, anything else the Criteo mode */
+  /** format: "libsvm" makes a DFX_TEXT_LIBSVM feed, anything else a DFX_TEXT_CRITEO one */
   DeviceTextFeed(dfx_ctx* ctx, size_t batch_size, size_t shuf_buf,
                  const std::string& format = "criteo");
   ~DeviceTextFeed();
@@ -56,12 +57,13 @@ class DeviceTextFeed {
   dfx_textfeed* h() const { return h_; }
   size_t batch_size() const { return batch_size_; }
   size_t shuf_buf() const { return shuf_buf_; }
-  bool libsvm() const { return libsvm_; }
+  int format() const { return format_; }
+  bool valued() const { return format_ == DFX_TEXT_LIBSVM; }
 
  private:
   dfx_textfeed* h_ = nullptr;
   size_t batch_size_, shuf_buf_;
-  bool libsvm_;
+  int format_;
 };
 
 class DeviceBatchReader {
@@ -97,14 +99,15 @@ class DeviceBatchReader {
     int slot;
     size_t bytes, newlines, blanks;
   };
-  void Gather(const GatherOp& op);  // libsvm: one copy of the plan, lengths and flags mirrored
+  void Gather(const GatherOp& op);  // one copy of the plan
+  size_t MirrorRows(const GatherOp& op, bool from_shuf);  // valued: its lengths and flags; nnz
   void Load();                  // the loader thread
   void SubmitFilled(bool wait); // queue the parses of the filled slots
   bool FetchChunk(size_t* rows, const uint64_t** off, const float** lab);
   void ReleaseChunk();
   dfx_textfeed* f_;
   TextReader reader_;
-  bool train_, libsvm_;
+  bool train_, valued_;
   size_t batch_size_;
   int nthreads_;
   std::unique_ptr<BatchPlanner> planner_;
@@ -119,12 +122,13 @@ class DeviceBatchReader {
   std::vector<int> seq_slot_;       // chunk sequence number -> slot
   RowBlockContainer<feaid_t> host_blk_;  // a flagged chunk, parsed on the host
   const float* chunk_lab_ = nullptr;
-  // libsvm: the current chunk's offsets and row flags, the shuffle buffer's row lengths and
-  // flags, whether a flagged row went into the batch being formed
+  // the current chunk's offsets and row flags (the feed's pinned mirror; none on a Criteo
+  // feed); valued: the shuffle buffer's row lengths and flags, whether a flagged row went into
+  // the batch being formed
   const uint64_t* chunk_off_ = nullptr;
   const uint8_t* chunk_flag_ = nullptr;
   size_t chunk_rows_ = 0;
-  std::vector<uint8_t> host_flag_, shuf_flag_;
+  std::vector<uint8_t> shuf_flag_;
   std::vector<uint32_t> shuf_len_;
   bool batch_valued_ = false;
   size_t fallback_ = 0;

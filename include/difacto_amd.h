@@ -215,13 +215,15 @@ int dfx_gather_rows_valued(dfx_ctx* ctx, const uint64_t* src_offset, const uint6
                            int64_t n, uint64_t* dst_offset, uint64_t* dst_index, float* dst_value,
                            float* dst_label, uint8_t* dst_rowflag, int64_t r0);
 
-/* The text feeder: raw text to device batches (src/reader/reader.h:18-55 + batch_reader.cc
- * with the parsing and the row copies on the device).  nslots pinned text slots, a loader
- * stream that becomes the context's input stream, one parsed chunk (device CSR + pinned
- * copies of its offsets and labels) per slot, a shuffle buffer of shuf_rows rows and a ring
- * of nring device batches of batch_rows rows (39 ids a row at most: rows size everything).
+/* The text feed (difacto_amd/csrc/textfeed.hip): raw text to device batches
+ * (src/reader/reader.h:18-55 + batch_reader.cc with the parsing and the row copies on the
+ * device).  nslots pinned text slots, a loader stream that becomes the context's input stream,
+ * one parsed chunk (device CSR + pinned copies of its offsets and labels) per slot, a shuffle
+ * buffer of shuf_rows rows and a ring of nring device batches of batch_rows rows.  The format
+ * (DFX_TEXT_CRITEO, DFX_TEXT_LIBSVM) is fixed at creation and every call below takes its
+ * behaviour from the feed.  A Criteo feed holds 39 ids a row at most: rows size everything.
  *   dfx_textfeed_text      the slot's pinned text buffer, at least `bytes` long; fill it
- *   dfx_textfeed_submit    upload + dfx_parse_criteo + the copies back, asynchronous
+ *   dfx_textfeed_submit    upload + the format's parser + the copies back, asynchronous
  *   dfx_textfeed_wait      join: stat[4] as dfx_parse_criteo_wait, the pinned offsets / labels
  *   dfx_textfeed_upload    a chunk the host parsed (needs_host) into the slot's arrays
  *   dfx_textfeed_batch_begin / _gather / _batch_end   form the next ring batch: gathers from
@@ -230,53 +232,38 @@ int dfx_gather_rows_valued(dfx_ctx* ctx, const uint64_t* src_offset, const uint6
  *                          NULL for the range [begin, begin + n), appended at row r0
  *   dfx_textfeed_consumed  after dfx_train_step(*out): the ring entry is in use until then
  *   dfx_textfeed_slot_batch / _slot_consumed   a slot's whole chunk as one batch (validation
- *                          reads 256 MB chunks as batches, sgd_learner.cc:281-286) */
+ *                          reads 256 MB chunks as batches, sgd_learner.cc:281-286)
+ * A libsvm feed is valued: every CSR also holds values and row flags (dfx_parse_libsvm) and has
+ * an nnz capacity of its own.  A slot's is the submit's max_nnz (the chunk's blanks bound its
+ * features; a Criteo feed ignores it, and a libsvm feed is_train); the shuffle buffer's and a
+ * ring entry's grow on demand (x 1.25) keeping their contents, by the nnz a gather says it
+ * appends (the caller knows the row lengths).  _wait and _upload also hand out the slot's pinned
+ * row flags (NULL on a Criteo feed); _upload computes them from the values, and may move all
+ * three pinned arrays.  _batch_end / _slot_batch with valued == 0 hand out value == NULL: the
+ * caller found no flagged row in the batch (batch_reader.cc:71-73).  On a Criteo feed a value
+ * array, a gather's nnz != 0 and valued != 0 are DFX_ERR_ARG, as is an _upload with features
+ * and no value array on a libsvm feed; a rejected call queues nothing. */
 typedef struct dfx_textfeed dfx_textfeed;
+enum { DFX_TEXT_CRITEO = 0, DFX_TEXT_LIBSVM = 1 };
 int dfx_textfeed_create(dfx_ctx* ctx, int nslots, int nring, int64_t batch_rows,
-                        int64_t shuf_rows, dfx_textfeed** out);
+                        int64_t shuf_rows, int format, dfx_textfeed** out);
 int dfx_textfeed_destroy(dfx_textfeed* f);
 int dfx_textfeed_text(dfx_textfeed* f, int slot, int64_t bytes, char** pinned);
 int dfx_textfeed_submit(dfx_textfeed* f, int slot, int64_t nbytes, int is_train,
-                        int64_t max_rows);
+                        int64_t max_rows, int64_t max_nnz);
 int dfx_textfeed_wait(dfx_textfeed* f, int slot, int64_t* stat, const uint64_t** offset_host,
-                      const float** label_host);
+                      const float** label_host, const uint8_t** rowflag_host);
 int dfx_textfeed_upload(dfx_textfeed* f, int slot, int64_t rows, int64_t nnz,
-                        const uint64_t* offset, const uint64_t* index, const float* label);
+                        const uint64_t* offset, const uint64_t* index, const float* value,
+                        const float* label, const uint8_t** rowflag_host);
 int dfx_textfeed_batch_begin(dfx_textfeed* f);
 int dfx_textfeed_gather(dfx_textfeed* f, int src, int to_batch, const uint32_t* rows,
-                        int64_t begin, int64_t n, int64_t r0);
-int dfx_textfeed_batch_end(dfx_textfeed* f, int64_t rows, int64_t nnz, dfx_batch* out);
+                        int64_t begin, int64_t n, int64_t r0, int64_t nnz);
+int dfx_textfeed_batch_end(dfx_textfeed* f, int64_t rows, int64_t nnz, int valued,
+                           dfx_batch* out);
 int dfx_textfeed_consumed(dfx_textfeed* f);
-int dfx_textfeed_slot_batch(dfx_textfeed* f, int slot, dfx_batch* out);
+int dfx_textfeed_slot_batch(dfx_textfeed* f, int slot, int valued, dfx_batch* out);
 int dfx_textfeed_slot_consumed(dfx_textfeed* f, int slot);
-/* The libsvm mode (dfx_textfeed_create_fmt with DFX_TEXT_LIBSVM; dfx_textfeed_create is the
- * DFX_TEXT_CRITEO mode, whose entry points above reject a libsvm feed and the other way round).
- * Every CSR also holds values and row flags (dfx_parse_libsvm) and has an nnz capacity of its
- * own: a slot's is the submit's max_nnz (the chunk's blanks bound its features), the shuffle
- * buffer's and a ring entry's grow on demand (x 1.25) keeping their contents.
- *   dfx_textfeed_submit_libsvm  upload + dfx_parse_libsvm + the copies back, asynchronous
- *   dfx_textfeed_wait_valued    dfx_textfeed_wait, and the pinned row flags
- *   dfx_textfeed_upload_valued  a chunk the host parsed, values included; flags from the values
- *   dfx_textfeed_gather_valued  dfx_textfeed_gather with values and flags; nnz: the features
- *                          the copy appends (the caller knows the row lengths)
- *   dfx_textfeed_batch_end_valued / _slot_batch_valued   valued == 0 hands out value == NULL:
- *                          the caller found no flagged row in the batch (batch_reader.cc:71-73) */
-enum { DFX_TEXT_CRITEO = 0, DFX_TEXT_LIBSVM = 1 };
-int dfx_textfeed_create_fmt(dfx_ctx* ctx, int nslots, int nring, int64_t batch_rows,
-                            int64_t shuf_rows, int format, dfx_textfeed** out);
-int dfx_textfeed_submit_libsvm(dfx_textfeed* f, int slot, int64_t nbytes, int64_t max_rows,
-                               int64_t max_nnz);
-int dfx_textfeed_wait_valued(dfx_textfeed* f, int slot, int64_t* stat,
-                             const uint64_t** offset_host, const float** label_host,
-                             const uint8_t** rowflag_host);
-int dfx_textfeed_upload_valued(dfx_textfeed* f, int slot, int64_t rows, int64_t nnz,
-                               const uint64_t* offset, const uint64_t* index, const float* value,
-                               const float* label);
-int dfx_textfeed_gather_valued(dfx_textfeed* f, int src, int to_batch, const uint32_t* rows,
-                               int64_t begin, int64_t n, int64_t r0, int64_t nnz);
-int dfx_textfeed_batch_end_valued(dfx_textfeed* f, int64_t rows, int64_t nnz, int valued,
-                                  dfx_batch* out);
-int dfx_textfeed_slot_batch_valued(dfx_textfeed* f, int slot, int valued, dfx_batch* out);
 
 /* ---- device batch cache (difacto_amd/csrc/batchcache.hip) --------------------------------
  * Formed batches kept in device memory, so that every epoch after the first replays them with

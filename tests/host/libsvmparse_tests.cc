@@ -24,6 +24,12 @@
 //                       included (batch 257, 64 KB chunks, shuffle 0 / 3, neg_sampling 1 / 0.7,
 //                       parts 0/1 and 1/2), whole chunks as batches, a file whose long rows make
 //                       the ring entry and the shuffle buffer grow mid-run, a flagged file
+//     feedargs          the text feed's argument checks, on a Criteo and a libsvm feed (batch 4,
+//                       shuffle buffer 8): values asked of or given to a Criteo feed, features
+//                       without values on a libsvm feed, the shuffle buffer gathered onto
+//                       itself and a gather with no batch begun are DFX_ERR_ARG with a message;
+//                       a three-row chunk then goes text -> submit -> wait -> batch_begin ->
+//                       gather -> batch_end and equals the host parser's block
 //   CPU mode (no HIP call)
 //     plan FILE         BatchPlanner's plan carried out with GatherRows and the row-flag
 //                       mirroring == BatchReader, including which batches drop their values
@@ -627,6 +633,76 @@ bool SameHostBlock(const Block& a, const Block& b) {
          (a.value.empty() || std::memcmp(a.value.data(), b.value.data(), a.value.size() * 4) == 0);
 }
 
+// ---- the feed's argument checks ------------------------------------------------------------
+void ExpectArg(int rc, const char* what, const char* needle) {
+  const std::string msg = rc == DFX_OK ? "" : dfx_last_error();
+  EXPECT(rc == DFX_ERR_ARG && msg.find(needle) != std::string::npos,
+         "feedargs %s: status %d, message \"%s\" (want DFX_ERR_ARG naming \"%s\")", what, rc,
+         msg.c_str(), needle);
+}
+
+int ModeFeedArgs(dfx_ctx* c) {
+  Dev dstat(c, 32);
+  const int64_t zero[4] = {0, 0, 0, 0};
+  dstat.Up(zero, 32);
+  const uint64_t off[2] = {0, 3}, idx[3] = {1, 2, 3};
+  const float val[3] = {1.f, 2.f, 3.f}, lab[1] = {1.f};
+  for (const bool libsvm : {false, true}) {
+    const char* name = libsvm ? "libsvm" : "criteo";
+    DeviceTextFeed feed(c, 4, 8, name);
+    dfx_textfeed* f = feed.h();
+    dfx_batch b;
+    if (libsvm) {
+      ExpectArg(dfx_textfeed_upload(f, 0, 1, 3, off, idx, nullptr, lab, nullptr),
+                "libsvm upload without values", "textfeed_upload");
+    } else {
+      ExpectArg(dfx_textfeed_batch_end(f, 1, 3, 1, &b), "criteo batch_end valued", "Criteo feed");
+      ExpectArg(dfx_textfeed_slot_batch(f, 0, 1, &b), "criteo slot_batch valued", "Criteo feed");
+      ExpectArg(dfx_textfeed_upload(f, 0, 1, 3, off, idx, val, lab, nullptr),
+                "criteo upload with values", "Criteo feed");
+    }
+    ExpectArg(dfx_textfeed_gather(f, -1, 0, nullptr, 0, 1, 0, 0), "shuffle buffer onto itself",
+              "onto itself");
+    ExpectArg(dfx_textfeed_gather(f, 0, 1, nullptr, 0, 1, 0, 0), "gather before batch_begin",
+              "no batch begun");
+    // the feed is still usable: three rows through it
+    const std::string text = libsvm ? "1 3:0.5 7\n0 2:1\n1 5:2.5 6:1 9\n"
+                                    : "1\t5\t\tab\n0\t\t7\n1\tx\ty\tz\n";
+    Block want;
+    if (libsvm)
+      want = HostParse(text);
+    else
+      ParseCriteo(text.data(), text.data() + text.size(), true, &want);
+    char* pinned = nullptr;
+    DfxCheck(dfx_textfeed_text(f, 0, (int64_t)text.size(), &pinned), "dfx_textfeed_text");
+    std::memcpy(pinned, text.data(), text.size());
+    const int64_t blanks = std::count(text.begin(), text.end(), ' ');
+    DfxCheck(dfx_textfeed_submit(f, 0, (int64_t)text.size(), 1, 3, blanks), "dfx_textfeed_submit");
+    int64_t stat[4];
+    const uint64_t* h_off = nullptr;
+    const float* h_lab = nullptr;
+    const uint8_t* h_flag = nullptr;
+    DfxCheck(dfx_textfeed_wait(f, 0, stat, &h_off, &h_lab, &h_flag), "dfx_textfeed_wait");
+    EXPECT(stat[0] == 3 && stat[1] == (int64_t)want.index.size() && !stat[2] && !stat[3],
+           "feedargs %s: stat %lld %lld %lld %lld", name, (long long)stat[0], (long long)stat[1],
+           (long long)stat[2], (long long)stat[3]);
+    EXPECT((h_flag != nullptr) == libsvm, "feedargs %s: row flags handed out: %d", name,
+           (int)(h_flag != nullptr));
+    if (stat[0] != 3 || stat[2]) continue;
+    bool valued = false;
+    for (int r = 0; h_flag && r < 3; ++r) valued = valued || h_flag[r];
+    EXPECT(valued == libsvm, "feedargs %s: flagged rows: %d", name, (int)valued);
+    DfxCheck(dfx_textfeed_batch_begin(f), "dfx_textfeed_batch_begin");
+    DfxCheck(dfx_textfeed_gather(f, 0, 1, nullptr, 0, 3, 0, libsvm ? (int64_t)h_off[3] : 0),
+             "dfx_textfeed_gather");
+    DfxCheck(dfx_textfeed_batch_end(f, 3, stat[1], valued ? 1 : 0, &b), "dfx_textfeed_batch_end");
+    EXPECT(SameDeviceBatch(c, &dstat, want, b), "feedargs %s: the batch != the host parser's block",
+           name);
+    std::printf("feedargs %s: rejections and a %lld-feature chunk ok\n", name, (long long)stat[1]);
+  }
+  return 0;
+}
+
 int ModePlan(const std::string& path) {
   const size_t bs = 257, chunk = 64 << 10;
   size_t valued = 0, binary = 0;
@@ -721,17 +797,18 @@ int main(int argc, char** argv) {
   if (mode == "plan" && argc > 2) {
     ModePlan(a2);
   } else if ((mode == "parse" && argc > 2) || mode == "fallback" || mode == "gather" ||
-             (mode == "batches" && argc > 3)) {
+             mode == "feedargs" || (mode == "batches" && argc > 3)) {
     dfx_ctx* c = nullptr;
     DfxCheck(dfx_ctx_create(0, "V_dim=0,max_keys=1024", &c), "dfx_ctx_create");
     if (mode == "parse") ModeParse(c, a2);
     if (mode == "fallback") ModeFallback(c);
     if (mode == "gather") ModeGather(c);
     if (mode == "batches") ModeBatches(c, a2, a3);
+    if (mode == "feedargs") ModeFeedArgs(c);
     dfx_ctx_destroy(c);
   } else {
     std::fprintf(stderr,
-                 "usage: %s parse FILE | fallback | gather | batches FILE DIR | plan FILE\n",
+                 "usage: %s parse FILE | fallback | gather | batches FILE DIR | feedargs | plan FILE\n",
                  argv[0]);
     return 2;
   }

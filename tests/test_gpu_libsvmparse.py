@@ -1,5 +1,5 @@
-"""libsvm text parsed and batched on the device (difacto_amd/csrc/libsvmparse.hip, the feed's
-libsvm mode in textparse.hip, difacto_amd/host/device_reader.cc) against the host reader, which
+"""libsvm text parsed and batched on the device (difacto_amd/csrc/libsvmparse.hip, the text
+feed in textfeed.hip, difacto_amd/host/device_reader.cc) against the host reader, which
 is the yardstick everywhere: ParseLibSVM, GatherRows, BatchReader and TextReader of
 difacto_amd/host/reader.cc, and libc's strtof / strtoull through ctypes.  Every comparison is
 exact.  The C++ driver is tests/host/libsvmparse_tests.cc (build/libsvmparse_tests)."""
@@ -69,6 +69,17 @@ def test_device_batch_reader_libsvm_equals_batch_reader(tmp_path):
     out = _run("batches", _gen(tmp_path / "mixed.libsvm", 5000, 7, 5, 15, 24, 3), tmp_path)
     assert out.count("batches (") == 8 and "chunks parsed by the host ok" in out
     assert out.count("grow file") == 2
+
+
+@pytest.mark.gpu
+def test_textfeed_rejects_bad_arguments_and_stays_usable():
+    """on a Criteo and a libsvm feed (batch 4, shuffle buffer 8): valued batches and a value
+    array on the Criteo feed, features without values on the libsvm feed, the shuffle buffer onto
+    itself and a gather before batch_begin are DFX_ERR_ARG with a message, all rejected by the
+    host-side argument checks; a three-row chunk then goes through each feed and equals the host
+    parser's block"""
+    out = _run("feedargs")
+    assert "feedargs criteo:" in out and "feedargs libsvm:" in out
 
 
 # ---- the driver ----------------------------------------------------------------------------
