@@ -6,8 +6,11 @@ A hot key (C5, Zipf(1.1): tens of thousands of occurrences per batch) cannot be 
 on a GPU in bounded time, so the device sums its chunks in double and rounds once.  Both the
 device and the reference are then compared with these float64 sums, with the error measured
 against the condition scale of each sum (sum of |terms|): the reference's own float rounding
-is the only difference that remains between the two."""
+is the only difference that remains between the two.  The float32 terms themselves are
+tests/backward_ref.py's (which restates the device's order of the sums, bit for bit)."""
 import numpy as np
+
+from tests.backward_ref import v_terms, w_terms, xv_rows
 
 
 def exact_calcgrad(blk, col, W, wp, vp, d, pred, U):
@@ -21,8 +24,7 @@ def exact_calcgrad(blk, col, W, wp, vp, d, pred, U):
     # p = -y / (1 + exp(y pred)), the exponential rounded once (as the device computes it)
     p = (-y / (1.0 + np.exp(y * pred.astype(np.float64)))).astype(np.float32)
     row = np.repeat(np.arange(B), np.diff(offs))
-    px = (p[row] * x).astype(np.float32)
-    pxx = (p[row] * (x * x).astype(np.float32)).astype(np.float32)
+    px, pxx = w_terms(p, row, x)
     nz = p[row] != 0
     gw = np.zeros(U)
     np.add.at(gw, col[nz], px[nz].astype(np.float64))
@@ -37,19 +39,10 @@ def exact_calcgrad(blk, col, W, wp, vp, d, pred, U):
     out[wp[has_w]] = gw[has_w]
     scale[wp[has_w]] = absw[has_w]
     if d > 0:
-        # X*V per row in float32, in the reference's (row, nnz) order (fm_loss.h:95-106)
-        XV = np.zeros((B, d), np.float32)
-        maxlen = int(np.max(np.diff(offs))) if B else 0
-        for j in range(maxlen):
-            rows = np.nonzero(offs[:-1] + j < offs[1:])[0]
-            q = offs[rows] + j
-            v = vp[col[q]]
-            ok = v >= 0
-            r2, q2, v2 = rows[ok], q[ok], v[ok]
-            Vv = W[v2[:, None] + np.arange(d)]
-            XV[r2] = (XV[r2] + (Vv * x[q2][:, None]).astype(np.float32)).astype(np.float32)
-        XVp = (XV * p[:, None]).astype(np.float32)
-        T = (XVp[row] * x[:, None]).astype(np.float32)
+        vp = np.asarray(vp)
+        XVp = (xv_rows(offs, col, x, np.asarray(W, np.float32), vp, d) * p[:, None]).astype(
+            np.float32)
+        T = v_terms(XVp, row, x)
         S = np.zeros((U, d))
         np.add.at(S, col, T.astype(np.float64))
         SA = np.zeros((U, d))

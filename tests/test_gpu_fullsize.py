@@ -156,7 +156,7 @@ def test_fused_full_c2(H):
 def test_fused_full_c5(H):
     """C5: Zipf(1.1) keys over 2^24, V_dim = 128, reference defaults (V_threshold = 10,
     l1 = 1, l1_shrk): V is created lazily for the hot keys.  Hot keys' Xᵀ sums run in
-    256-occurrence chunks combined in chunk order (reordered sums), so predictions after the
+    128-occurrence chunks combined in chunk order (reordered sums), so predictions after the
     first update and the model are compared within tolerance (Determinism).  The
     model is held to the drift bound every step (the device within 1e-5 of the reference as a
     vector, and no farther from the exact f64-sum trajectory than the reference is), not to an
@@ -175,8 +175,9 @@ def test_calcgrad_c5_chunked(H):
     fused step's chunk plan): B = 10^4 rows of 39 Zipf(1.1) keys over [1, 2^24], V_dim = 128,
     a third of the keys without V.  The hottest key has ~45k occurrences in the batch.
 
-    Keys of <= 256 occurrences are summed in the reference's order (bit-exact up to expf);
-    longer ones in 256-occurrence chunks combined in double.  Against float64 sums of the
+    Keys of <= 128 occurrences (kChunkOcc) are summed in the reference's order (bit-exact, expf
+    included); longer ones in 128-occurrence chunks combined in double (bit for bit against the
+    restated order: tests/test_gpu_backward_paths.py).  Against float64 sums of the
     reference's own terms (tests/exact_sums.py) the device is within 1e-6 of each element's
     condition scale (sum of |terms|); the reference itself (the oracle) is up to ~3e-5 of that
     scale away — its own sequential float rounding over ~45k terms — so the device and the

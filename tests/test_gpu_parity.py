@@ -191,7 +191,8 @@ def test_fmloss_random(H, d, binary):
     assert np.array_equal(pred, opred), np.max(np.abs(pred - opred))
     og = O.fm_calcgrad(blk.offs, ocol, blk.vals, blk.labels, rw, W, wp, vp, U, d, opred)
     assert close(grad, og)
-    # no key reaches a chunked sum (<= 256 occurrences) and p's expf is glibc's (csrc/expf.h):
+    # no key reaches a chunked sum (<= 128 occurrences, kChunkOcc) and p's expf is glibc's
+    # (csrc/expf.h):
     # the gradients are the reference's bit for bit
     assert np.array_equal(grad, og), int((grad != og).sum())
     assert abs(objv - O.evaluate(blk.labels, opred)) <= 1e-4 * abs(objv)
@@ -377,12 +378,17 @@ def test_fused_matches_oracle_rcv1(H, rcv1, cfg):
     db = H.DeviceRowBlock(c, rcv1)
     halves = [rcv1.slice(0, 50), rcv1.slice(50, 100)]
     dhalves = [H.DeviceRowBlock(c, h) for h in halves]
+    for hb in halves:  # no key reaches a chunked sum: the steps are the oracle's bit for bit
+        assert np.bincount(O.localize(hb.offs, hb.ids)[2]).max() <= 128
     for ep in range(6):
         for hb, dh in zip(halves, dhalves):
             loss, auc, opred = up.train_step(hb.offs, hb.ids, hb.vals, hb.labels,
                                              push_cnt=(ep == 0), want_pred=True)
-            H.train_step(c, dh, H.kTraining, push_cnt=(ep == 0))
+            pred = torch.zeros(hb.size, dtype=torch.float32, device=c.device)
+            H.train_step(c, dh, H.kTraining, push_cnt=(ep == 0), pred=pred)
             p = H.progress(c)
+            assert np.array_equal(pred.cpu().numpy().view(np.uint32),
+                                  np.asarray(opred, np.float32).view(np.uint32)), ep
             assert abs(p["loss"] - loss) <= 1e-4 * max(1, abs(loss)), (ep, p["loss"], loss)
             want = _auc_expect(hb.labels, opred, auc)
             assert abs(p["auc"] - want) <= 1e-4 * hb.size, (ep, p["auc"], want)
@@ -392,6 +398,7 @@ def test_fused_matches_oracle_rcv1(H, rcv1, cfg):
     ov, ol = up.get(uniq)
     assert np.array_equal(l.cpu().numpy(), ol)
     assert close(v.cpu().numpy(), ov, rtol=1e-4)
+    assert np.array_equal(v.cpu().numpy().view(np.uint32), ov.view(np.uint32))
     assert st.stats()["seed"] == up.seed
 
 
@@ -405,6 +412,8 @@ def test_fused_criteo_like_vs_oracle(H, key_space, pack):
     up = O.Updater(**cfg)
     for step in range(4):
         blk = D.synthetic(3000, 39, key_space, seed=50 + step)
+        # no key reaches a chunked sum: the steps are the oracle's bit for bit
+        assert np.bincount(O.localize(blk.offs, blk.ids)[2]).max() <= 128
         loss, auc, opred = up.train_step(blk.offs, blk.ids, blk.vals, blk.labels,
                                          push_cnt=(step < 2), want_pred=True)
         db = H.DeviceRowBlock(c, blk)
@@ -412,11 +421,18 @@ def test_fused_criteo_like_vs_oracle(H, key_space, pack):
         H.train_step(c, db, H.kTraining, push_cnt=(step < 2), pred=pred)
         p = H.progress(c)
         assert close(pred.cpu().numpy(), opred, rtol=1e-4)
+        assert np.array_equal(pred.cpu().numpy().view(np.uint32),
+                              np.asarray(opred, np.float32).view(np.uint32)), step
         assert abs(p["loss"] - loss) <= 1e-4 * abs(loss)
         want = _auc_expect(blk.labels, opred, auc)
         assert abs(p["auc"] - want) <= 1e-4 * blk.size
     s = H.Store(c).stats()
     assert s["seed"] == up.seed and s["n_keys"] == up.size()
+    uniq, _, _ = O.localize(blk.offs, blk.ids)
+    v, l = H.Store(c).pull(c.tensor(uniq, torch.int64))
+    ov, ol = up.get(uniq)
+    assert np.array_equal(l.cpu().numpy(), ol)
+    assert np.array_equal(v.cpu().numpy().view(np.uint32), ov.view(np.uint32))
 
 
 @pytest.mark.parametrize("max_index", [1000, 65537, (1 << 64) - 1])
