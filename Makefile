@@ -30,11 +30,12 @@ CONVBIN = build/dfx_convert
 RBENCH = build/reader_bench
 TPBIN = build/textparse_tests
 LSBIN = build/libsvmparse_tests
+SEBIN = build/shard_eval_tests
 
 DISTLIB = difacto_amd/libdfx_dist.so
 
 all: $(LIB) $(DISTLIB) oracle $(HOSTBIN) $(TRAINBIN) $(READERBIN) $(GENBIN) $(CONVBIN) $(RBENCH) \
-  $(TPBIN) $(LSBIN) build/expf_check build/strtof_check build/gen_libsvm build/locbench
+  $(TPBIN) $(LSBIN) $(SEBIN) build/expf_check build/strtof_check build/gen_libsvm build/locbench
 
 $(RBENCH): difacto_amd/host/reader.cc tools/reader_bench.cc difacto_amd/host/reader.h $(CITYHDR)
 	@mkdir -p build
@@ -87,6 +88,16 @@ $(HOSTBIN): $(HOSTSRC) $(HOSTHDR) build/obj/dist_host.o $(LIB) $(DISTLIB)
 	@mkdir -p build
 	g++ $(HOSTFLAGS) -o $@ $(HOSTSRC) build/obj/dist_host.o -Ldifacto_amd -ldifacto_amd -ldfx_dist \
 	  -L/opt/rocm/lib -lrccl -lamdhip64 \
+	  -Wl,-rpath,'$$ORIGIN/../difacto_amd' -Wl,-rpath,/opt/rocm/lib
+
+# the sharded stores' evaluation paths from C++ (GpuShardedStore's non-training branch,
+# GpuSplitLearner's prediction output) against the single context's validation step
+$(SEBIN): $(HOSTLIB) difacto_amd/host/split_learner.cc tests/host/shard_eval_tests.cc $(HOSTHDR) \
+  build/obj/dist_host.o $(LIB) $(DISTLIB)
+	@mkdir -p build
+	g++ $(HOSTFLAGS) -o $@ $(HOSTLIB) difacto_amd/host/split_learner.cc \
+	  tests/host/shard_eval_tests.cc build/obj/dist_host.o \
+	  -Ldifacto_amd -ldifacto_amd -ldfx_dist -L/opt/rocm/lib -lrccl -lamdhip64 \
 	  -Wl,-rpath,'$$ORIGIN/../difacto_amd' -Wl,-rpath,/opt/rocm/lib
 
 # the sharded store's C++ driver (host code: HIP runtime API + RCCL, built by hipcc)

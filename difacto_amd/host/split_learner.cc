@@ -37,12 +37,15 @@ struct GpuSplitLearner::Impl {
   std::condition_variable cv;
   std::vector<const dmlc::RowBlock<feaid_t>*> pend;
   std::vector<int> pend_job, pend_cnt;
+  std::vector<std::vector<real_t>*> pend_pred;  // where a worker wants its predictions
+  std::vector<std::unique_ptr<DevArray<float>>> dpred;  // their device buffers
   int arrived = 0;
   int64_t gen = 0;
   std::string failure;
 
   ~Impl() {
     if (store) (void)dfx_split_store_destroy(store);  // flushes and syncs the contexts
+    dpred.clear();
     for (dfx_feeder* f : feeders)
       if (f) (void)dfx_feeder_destroy(f);
     for (dfx_ctx* c : ctxs) (void)dfx_ctx_destroy(c);
@@ -95,7 +98,20 @@ struct GpuSplitLearner::Impl {
                                  x.weight != nullptr && B > 0, &b[l]),
                "dfx_feeder_submit");
     }
-    DistCheck(dfx_split_store_submit(store, b.data(), job, push_cnt ? 1 : 0, nullptr),
+    bool want_pred = false;
+    for (const auto* p : pend_pred) want_pred = want_pred || p != nullptr;
+    std::vector<float*> dp(L, nullptr);
+    if (want_pred) {
+      if (dpred.empty())
+        for (int l = 0; l < L; ++l) dpred.emplace_back(new DevArray<float>(ctxs[l]));
+      for (int l = 0; l < L; ++l) {
+        if (!pend_pred[l]) continue;
+        dpred[l]->ensure((size_t)b[l].size);
+        dp[l] = dpred[l]->get();
+      }
+    }
+    DistCheck(dfx_split_store_submit(store, b.data(), job, push_cnt ? 1 : 0,
+                                     want_pred ? dp.data() : nullptr),
               "dfx_split_store_submit");
     // a pipelined submit queued the previous step, the last reader of the previous batch
     for (int l = 0; l < L; ++l)
@@ -104,6 +120,19 @@ struct GpuSplitLearner::Impl {
                "dfx_feeder_consumed");
     queued = pipelined;
     ++submits;
+    if (!want_pred) return;
+    // the step runs now (pipelined: it was only queued), then its predictions come down on the
+    // context streams, behind the combine that wrote them
+    if (queued) {
+      DistCheck(dfx_split_store_flush(store), "dfx_split_store_flush");
+      for (dfx_feeder* f : feeders) DfxCheck(dfx_feeder_consumed(f), "dfx_feeder_consumed");
+      queued = false;
+    }
+    for (int l = 0; l < L; ++l) {
+      if (!pend_pred[l]) continue;
+      pend_pred[l]->resize((size_t)b[l].size);
+      dpred[l]->download(pend_pred[l]->data(), (size_t)b[l].size);
+    }
   }
 };
 
@@ -198,6 +227,7 @@ GpuSplitLearner::GpuSplitLearner(std::unique_ptr<Impl> impl) : impl_(std::move(i
   impl_->pend.assign(impl_->L, nullptr);
   impl_->pend_job.assign(impl_->L, 0);
   impl_->pend_cnt.assign(impl_->L, 0);
+  impl_->pend_pred.assign(impl_->L, nullptr);
 }
 
 GpuSplitLearner::~GpuSplitLearner() {}
@@ -208,11 +238,13 @@ int GpuSplitLearner::rank(int local) const { return impl_->rank0 + local; }
 dfx_ctx* GpuSplitLearner::shard(int local) const { return impl_->ctxs.at(local); }
 
 void GpuSplitLearner::ProcessBatch(int local, const dmlc::RowBlock<feaid_t>& batch, int job_type,
-                                   bool push_cnt) {
+                                   bool push_cnt, std::vector<real_t>* pred) {
   Impl& m = *impl_;
   DFX_HOST_CHECK(local >= 0 && local < m.L, "GpuSplitLearner: bad local worker");
   DFX_HOST_CHECK(job_type == kTraining || job_type == kValidation || job_type == kPrediction,
                  "GpuSplitLearner: bad job type");
+  DFX_HOST_CHECK(!pred || job_type != kTraining,
+                 "GpuSplitLearner: predictions are for validation and prediction jobs");
   push_cnt = push_cnt && job_type == kTraining;
   std::unique_lock<std::mutex> lk(m.mu);
   DFX_HOST_CHECK(m.failure.empty(), "GpuSplitLearner: " + m.failure);
@@ -220,6 +252,7 @@ void GpuSplitLearner::ProcessBatch(int local, const dmlc::RowBlock<feaid_t>& bat
   m.pend[local] = &batch;
   m.pend_job[local] = job_type;
   m.pend_cnt[local] = push_cnt ? 1 : 0;
+  m.pend_pred[local] = pred;
   const int64_t my_gen = m.gen;
   if (++m.arrived < m.L) {
     // the other local workers' batches complete the step; the last one submits it
@@ -233,22 +266,31 @@ void GpuSplitLearner::ProcessBatch(int local, const dmlc::RowBlock<feaid_t>& bat
   if (m.failure.empty()) m.Submit(job_type, push_cnt);
   m.arrived = 0;
   for (auto& p : m.pend) p = nullptr;
+  for (auto& p : m.pend_pred) p = nullptr;
   ++m.gen;
   m.cv.notify_all();
   DFX_HOST_CHECK(m.failure.empty(), "GpuSplitLearner: " + m.failure);
 }
 
 void GpuSplitLearner::ProcessBatches(const std::vector<const dmlc::RowBlock<feaid_t>*>& batches,
-                                     int job_type, bool push_cnt) {
+                                     int job_type, bool push_cnt,
+                                     std::vector<std::vector<real_t>>* preds) {
   Impl& m = *impl_;
   DFX_HOST_CHECK((int)batches.size() == m.L, "GpuSplitLearner: one batch per local worker");
   DFX_HOST_CHECK(job_type == kTraining || job_type == kValidation || job_type == kPrediction,
                  "GpuSplitLearner: bad job type");
+  DFX_HOST_CHECK(!preds || job_type != kTraining,
+                 "GpuSplitLearner: predictions are for validation and prediction jobs");
   std::lock_guard<std::mutex> lk(m.mu);
   DFX_HOST_CHECK(m.arrived == 0, "GpuSplitLearner: ProcessBatches beside ProcessBatch calls");
-  for (int l = 0; l < m.L; ++l) m.pend[l] = batches[l];
+  if (preds) preds->resize(m.L);
+  for (int l = 0; l < m.L; ++l) {
+    m.pend[l] = batches[l];
+    m.pend_pred[l] = preds ? &(*preds)[l] : nullptr;
+  }
   m.Submit(job_type, push_cnt && job_type == kTraining);
   for (auto& p : m.pend) p = nullptr;
+  for (auto& p : m.pend_pred) p = nullptr;
 }
 
 void GpuSplitLearner::Flush() {

@@ -46,12 +46,18 @@ class GpuSplitLearner {
   /** the server context of local shard l (model save / load / stats) */
   dfx_ctx* shard(int local) const;
   /** worker `local`'s minibatch of this step (thread-safe across the local workers: the step
-   * is submitted when the last of them gave its batch; the others wait for that) */
+   * is submitted when the last of them gave its batch; the others wait for that).
+   * pred (optional; validation and prediction jobs only): the batch's predictions, one per
+   * row, as SGDLearner's executor hands them to SavePred (sgd_learner.cc:231-237).  A step any
+   * of whose workers asks for them runs before the calls return (submit, then flush: an
+   * evaluation step pushes nothing, so no schedule depends on when it runs), and every
+   * worker's vector is filled on return. */
   void ProcessBatch(int local, const dmlc::RowBlock<feaid_t>& batch, int job_type,
-                    bool push_cnt);
-  /** one step from a single caller thread: batches[l] is local worker l's minibatch */
+                    bool push_cnt, std::vector<real_t>* pred = nullptr);
+  /** one step from a single caller thread: batches[l] is local worker l's minibatch;
+   * preds (optional, as above): resized to one vector per local worker */
   void ProcessBatches(const std::vector<const dmlc::RowBlock<feaid_t>*>& batches, int job_type,
-                      bool push_cnt);
+                      bool push_cnt, std::vector<std::vector<real_t>>* preds = nullptr);
   /** run the queued step (one thread, every local worker idle) */
   void Flush();
   /** sgd::Progress of worker `local` since the last call (Flush first) */

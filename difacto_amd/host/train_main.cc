@@ -3,7 +3,8 @@
 //
 //   build/dfx_train data_in=FILE [data_val=FILE] [data_format=libsvm|criteo|criteo_test]
 //                   [batch_size=100] [shuffle=10] [neg_sampling=1] [max_num_epochs=20]
-//                   [num_jobs_per_epoch=10] [stop_rel_objv=1e-5] [model_in=F] [model_out=F]
+//                   [num_jobs_per_epoch=10] [stop_rel_objv=1e-5] [stop_val_auc=1e-5]
+//                   [model_in=F] [model_out=F]
 //                   [load_epoch=-1] [has_aux=0] [task=0|2] [pred_out=F] [pred_prob=1]
 //                   [fused=1] [nthreads=8] [parse=host|device|auto] [cache=none|device]
 //                   [cache_mb=16384] [cache_loc=0] [V_dim=..] [lr=..] [l1=..] ...
@@ -55,6 +56,18 @@
 // <model_out>_part-<rank>; `model_in_parts=K` loads a model K servers saved into this run's
 // shards (each keeps the keys it owns).  `exchange=split` runs the sharded epochs through the
 // owner-computes split (GpuSplitLearner, split_learner.h) instead of KVStoreDist's exchanges.
+// Both exchanges run the same epoch loop (ShardedPass over a ShardRunner).  With data_val every
+// epoch ends in a validation pass: the store is flushed first (the stale schedule's last push is
+// applied), the shard of rank g reads part j * shards + g of data_val as whole 256 MB chunks,
+// one batch per chunk, the shards stepping together as in training; rank 0 prints the
+// "Epoch[k] Validation:" line from the all-reduced sums, and the stop rules (training loss, then
+// validation AUC against stop_val_auc, sgd_learner.cc:92-106) are decided on those sums, the
+// same on every rank.  task=2 (needs model_in and data_val, else exit 2) is one such pass with
+// job type prediction: every rank writes <pred_out>_part-<its global rank>, one
+// "label\tprediction" line per row in the order it read them (the file exists even when it read
+// none), and rank 0 prints the "Prediction:" line.  A prediction step runs synchronously
+// (submit, flush, copy the predictions down); validation steps are queued like training steps.
+// cache=device exchange=a2a keeps and replays the validation batches too (lists of their own).
 //
 // Model files are named like SGDLearner::ModelName (sgd_learner.h:65-69):
 // <prefix>[_iter-<epoch>]_part-0, in SGDUpdater::Save's format; task=2 predicts data_val with
@@ -95,6 +108,7 @@ struct Param {
   std::string exchange = "a2a";  // a2a: GpuShardedStore (KVStoreDist); split: GpuSplitLearner
   bool has_aux = false, pred_prob = true;
   double stop_rel_objv = 1e-5;
+  double stop_val_auc = 1e-5;  // sgd_param.h:73
   std::string parse = "host";  // device: DeviceBatchReader (text parsed on the GPU); auto
   std::string cache = "none";  // device: formed batches kept in HBM, replayed after the first epoch
   int64_t cache_mb = 16384;    // its budget (per shard)
@@ -272,248 +286,383 @@ std::string KwString(const KWArgs& kw) {
   return s;
 }
 
-// exchange=split: the owner-computes split behind GpuSplitLearner (split_learner.h): the same
-// readers, parts and stop rule, one synchronous reference step per batch index on the
-// concatenation of the shards' batches (push_agg=sum); pipelined=1 only overlaps model-free
-// work, so the results equal the synchronous schedule
-int RunShardedSplit(const Param& P, const KWArgs& rest) {
-  const char* ws = std::getenv("WORLD_SIZE");
-  const int world = ws ? std::atoi(ws) : 1;
-  const bool rccl = world > 1 || P.shards < 0;
-  KWArgs kw = rest;
-  kw.push_back({"pipelined", P.pipelined ? "1" : "0"});
-  std::shared_ptr<GpuSplitLearner> sl =
-      rccl ? GpuSplitLearner::CreateRccl(kw) : GpuSplitLearner::CreateLoopback(P.shards, kw);
-  const int nlocal = sl->nlocal(), nshards = sl->nranks(), rank = sl->rank(0);
-  if (!P.model_in.empty()) {
-    const int it = P.load_epoch > 0 ? P.load_epoch : -1;
-    for (int l = 0; l < nlocal; ++l) {
-      if (P.model_in_parts <= 0 || P.model_in_parts == nshards) {
-        DfxCheck(dfx_store_load(sl->shard(l), ModelNamePart(P.model_in, it, sl->rank(l)).c_str()),
-                 "dfx_store_load");
-      } else {
-        for (int r = 0; r < P.model_in_parts; ++r)
-          DfxCheck(dfx_store_load_part(sl->shard(l), ModelNamePart(P.model_in, it, r).c_str(),
-                                       sl->rank(l), nshards),
-                   "dfx_store_load_part");
-      }
-    }
-  }
-  static const size_t kZeroOff = 0;
-  dmlc::RowBlock<feaid_t> empty;
-  empty.size = 0;
-  empty.offset = &kZeroOff;
-  const double t0 = Now();
-  double pre_loss = 0;
-  for (int k = std::max(0, P.load_epoch > 0 ? P.load_epoch + 1 : 0); k < P.max_num_epochs; ++k) {
-    const double te = Now();
-    for (int job = 0; job < P.num_jobs_per_epoch; ++job) {
-      const int nparts = P.num_jobs_per_epoch * nshards;
-      std::vector<std::unique_ptr<ThreadedBatchReader>> rd(nlocal);
-      for (int l = 0; l < nlocal; ++l)
-        rd[l].reset(new ThreadedBatchReader(P.data_in, P.data_format,
-                                            job * nshards + sl->rank(l), nparts, P.batch_size,
-                                            P.batch_size * P.shuffle, P.neg_sampling,
-                                            P.nthreads));
-      std::vector<bool> more(nlocal, true);
-      std::vector<dmlc::RowBlock<feaid_t>> blk(nlocal);
-      for (;;) {
-        std::vector<double> any(1, 0.0);
-        for (int l = 0; l < nlocal; ++l) {
-          if (more[l]) more[l] = rd[l]->Next();
-          if (more[l]) any[0] += 1;
-        }
-        sl->AllReduceSum(&any);
-        if (any[0] == 0) break;
-        std::vector<const dmlc::RowBlock<feaid_t>*> ptrs(nlocal);
-        for (int l = 0; l < nlocal; ++l) {
-          blk[l] = more[l] ? rd[l]->Value().GetBlock() : empty;
-          ptrs[l] = &blk[l];
-        }
-        sl->ProcessBatches(ptrs, GpuSplitLearner::kTraining, k == 0);
-      }
-    }
-    std::vector<double> pr(3, 0.0);
-    for (int l = 0; l < nlocal; ++l) {
-      const Progress p = sl->TakeProgress(l);
-      pr[0] += p.nrows;
-      pr[1] += p.loss;
-      pr[2] += p.auc;
-    }
-    sl->AllReduceSum(&pr);
-    Progress tr;
-    tr.nrows = pr[0];
-    tr.loss = pr[1];
-    tr.auc = pr[2];
-    const double dt = Now() - te;
-    if (rank == 0)
-      std::printf("Epoch[%d] Training: %s  (%.0f ex/s incl. parse+PCIe, %d shards, split, %.2f s)\n",
-                  k, Text(tr).c_str(), tr.nrows / dt, nshards, Now() - t0);
-    std::fflush(stdout);
-    const double eps = std::fabs(tr.loss - pre_loss) / pre_loss;
-    if (eps < P.stop_rel_objv) break;
-    pre_loss = tr.loss;
-  }
-  sl->Flush();
-  if (!P.model_out.empty())
+// What the sharded epoch needs of a store.  exchange=a2a: GpuShardedStore (KVStoreDist's
+// exchanges, dist_host.h) over device batches, with the batch cache; exchange=split: the
+// owner-computes split behind GpuSplitLearner (split_learner.h), which takes host row blocks —
+// one synchronous reference step per batch index on the concatenation of the shards' batches
+// (push_agg=sum; pipelined=1 only overlaps model-free work, so the results equal the
+// synchronous schedule).
+class ShardRunner {
+ public:
+  /** local shard l's batch of a step: a host block (null: none, the shard gives an empty
+   * batch), or batch `replay` of the cached list the step names */
+  struct Item {
+    const RowBlockContainer<feaid_t>* host = nullptr;
+    int64_t replay = -1;
+  };
+  virtual ~ShardRunner() {}
+  virtual int nlocal() const = 0;
+  virtual int nranks() const = 0;
+  virtual int rank(int local) const = 0;
+  virtual dfx_ctx* ctx(int local) const = 0;
+  virtual const char* tag() const = 0;  // in the Training line, after the shard count
+  virtual void AllReduceSum(std::vector<double>* v) = 0;
+  /** one step of every local shard.  record: the host blocks are also appended to `list` of
+   * the shards' caches.  preds (evaluation jobs): the step runs before the call returns and
+   * preds[l] holds local shard l's predictions; without it the step may only be queued */
+  virtual void Step(const std::vector<Item>& items, int64_t list, bool record, int job_type,
+                    bool push_cnt, std::vector<std::vector<real_t>>* preds) = 0;
+  /** run what is queued and apply the last push */
+  virtual void Flush() = 0;
+  // the batch cache (cache=device; exchange=a2a only): a sealed list's batches of local shard
+  // l, -1 when the part has to be read; the recording pass's list brackets; the shards' sums
+  virtual bool has_cache() const { return false; }
+  virtual int64_t Cached(int, int64_t) { return -1; }
+  virtual void BeginList(int64_t) {}
+  virtual void SealList() {}
+  virtual void CacheSums(std::vector<double>* cs) { cs->assign(4, 0.0); }
+};
+
+class A2aRunner : public ShardRunner {
+ public:
+  A2aRunner(const Param& P, const KWArgs& rest) {
+    const char* ws = std::getenv("WORLD_SIZE");
+    const int world = ws ? std::atoi(ws) : 1;
+    const bool rccl = world > 1 || P.shards < 0;
+    const int rank = rccl && std::getenv("RANK") ? std::atoi(std::getenv("RANK")) : 0;
+    const int local = std::getenv("LOCAL_RANK") ? std::atoi(std::getenv("LOCAL_RANK")) : 0;
+    const int nlocal = rccl ? 1 : P.shards;
+    ctxs_.assign(nlocal, nullptr);
+    const std::string kw = KwString(rest);
     for (int l = 0; l < nlocal; ++l)
-      DfxCheck(dfx_store_save(sl->shard(l), ModelNamePart(P.model_out, -1, sl->rank(l)).c_str(),
-                              P.has_aux ? 1 : 0),
-               "dfx_store_save");
-  return 0;
+      DfxCheck(dfx_ctx_create(rccl ? local : 0, kw.c_str(), &ctxs_[l]), "dfx_ctx_create");
+    if (rccl) {
+      std::string id_file;
+      if (const char* f = std::getenv("DFX_COMM_ID_FILE")) {
+        id_file = f;
+      } else {
+        const char* port = std::getenv("MASTER_PORT");
+        id_file = std::string("/tmp/dfx_comm_") + (port ? port : "0");
+      }
+      ex_ = MakeRcclExchange(ctxs_[0], rank, world, id_file);
+    } else {
+      ex_ = MakeLoopbackExchange(ctxs_);
+    }
+    store_.reset(new GpuShardedStore(ex_.get(), P.pipelined));
+    dev_.resize(nlocal);
+    for (auto& v : dev_) v.resize(3);
+    // cache=device: each local shard's batch cache on its own context, recorded in the first
+    // epoch this run executes (task=2 is one pass: nothing to replay)
+    if (P.cache == "device" && P.task != 2)
+      for (int l = 0; l < nlocal; ++l)
+        caches_.emplace_back(new DeviceBatchCache(ctxs_[l], P.cache_mb << 20));
+  }
+  ~A2aRunner() override {
+    store_.reset();  // flushes and joins the contexts
+    dpred_.clear();
+    caches_.clear();
+    dev_.clear();
+    ex_.reset();
+    for (auto c : ctxs_) dfx_ctx_destroy(c);
+  }
+  int nlocal() const override { return ex_->nlocal(); }
+  int nranks() const override { return ex_->nranks(); }
+  int rank(int local) const override { return ex_->rank(local); }
+  dfx_ctx* ctx(int local) const override { return ctxs_[local]; }
+  const char* tag() const override { return ""; }
+  void AllReduceSum(std::vector<double>* v) override { ex_->AllReduceSum(v); }
+  void Step(const std::vector<Item>& items, int64_t list, bool record, int job_type,
+            bool push_cnt, std::vector<std::vector<real_t>>* preds) override {
+    const int L = nlocal();
+    std::vector<dfx_batch> bs(L);
+    for (int l = 0; l < L; ++l) {
+      if (items[l].replay >= 0) {
+        bs[l] = caches_[l]->Get(list, items[l].replay);
+        continue;
+      }
+      DevBatch& db = dev_[l][ring_];  // three per shard: a queued step still reads the last
+      db.Upload(ctxs_[l], items[l].host);
+      bs[l] = db.b;
+      if (record && items[l].host) caches_[l]->Append(db.b);
+    }
+    ring_ = (ring_ + 1) % 3;
+    if (!preds) {
+      store_->Submit(bs, job_type, push_cnt);
+      return;
+    }
+    // a submitted step runs at the next Submit or at Flush: flush, then its predictions come
+    // down behind it on the contexts' streams
+    if (dpred_.empty())
+      for (int l = 0; l < L; ++l) dpred_.emplace_back(new DevArray<float>(ctxs_[l]));
+    std::vector<float*> dp(L);
+    for (int l = 0; l < L; ++l) {
+      dpred_[l]->ensure((size_t)bs[l].size);
+      dp[l] = dpred_[l]->get();
+    }
+    store_->Submit(bs, job_type, push_cnt, dp);
+    store_->Flush();
+    preds->resize(L);
+    for (int l = 0; l < L; ++l) {
+      (*preds)[l].resize((size_t)bs[l].size);
+      dpred_[l]->download((*preds)[l].data(), (size_t)bs[l].size);
+    }
+  }
+  void Flush() override { store_->Flush(); }
+  bool has_cache() const override { return !caches_.empty(); }
+  int64_t Cached(int l, int64_t list) override { return caches_[l]->Count(list); }
+  void BeginList(int64_t list) override {
+    for (auto& c : caches_) c->Begin(list);
+  }
+  void SealList() override {
+    for (auto& c : caches_) c->Seal();
+  }
+  void CacheSums(std::vector<double>* cs) override {
+    cs->assign(4, 0.0);
+    for (auto& c : caches_) {
+      const DeviceBatchCache::Stats s = c->GetStats();
+      (*cs)[0] += (double)s.batches;
+      (*cs)[1] += (double)s.bytes;
+      (*cs)[2] += (double)s.dropped;
+      (*cs)[3] += (double)(s.sealed + s.dropped);
+    }
+  }
+
+ private:
+  std::vector<dfx_ctx*> ctxs_;
+  std::unique_ptr<ShardExchange> ex_;
+  std::unique_ptr<GpuShardedStore> store_;
+  std::vector<std::vector<DevBatch>> dev_;
+  std::vector<std::unique_ptr<DeviceBatchCache>> caches_;
+  std::vector<std::unique_ptr<DevArray<float>>> dpred_;
+  int ring_ = 0;
+};
+
+class SplitRunner : public ShardRunner {
+ public:
+  SplitRunner(const Param& P, const KWArgs& rest) {
+    const char* ws = std::getenv("WORLD_SIZE");
+    const int world = ws ? std::atoi(ws) : 1;
+    const bool rccl = world > 1 || P.shards < 0;
+    KWArgs kw = rest;
+    kw.push_back({"pipelined", P.pipelined ? "1" : "0"});
+    sl_ = rccl ? GpuSplitLearner::CreateRccl(kw) : GpuSplitLearner::CreateLoopback(P.shards, kw);
+    empty_.size = 0;
+    empty_.offset = &zero_off_;
+  }
+  int nlocal() const override { return sl_->nlocal(); }
+  int nranks() const override { return sl_->nranks(); }
+  int rank(int local) const override { return sl_->rank(local); }
+  dfx_ctx* ctx(int local) const override { return sl_->shard(local); }
+  const char* tag() const override { return ", split"; }
+  void AllReduceSum(std::vector<double>* v) override { sl_->AllReduceSum(v); }
+  void Step(const std::vector<Item>& items, int64_t, bool, int job_type, bool push_cnt,
+            std::vector<std::vector<real_t>>* preds) override {
+    const int L = nlocal();
+    std::vector<dmlc::RowBlock<feaid_t>> blk(L);
+    std::vector<const dmlc::RowBlock<feaid_t>*> ptrs(L);
+    for (int l = 0; l < L; ++l) {
+      blk[l] = items[l].host ? items[l].host->GetBlock() : empty_;
+      ptrs[l] = &blk[l];
+    }
+    sl_->ProcessBatches(ptrs, job_type, push_cnt, preds);
+  }
+  void Flush() override { sl_->Flush(); }
+
+ private:
+  std::shared_ptr<GpuSplitLearner> sl_;
+  size_t zero_off_ = 0;
+  dmlc::RowBlock<feaid_t> empty_;
+};
+
+// a part's batches: training reads minibatches (sgd_learner.cc:273-280), validation and
+// prediction whole 256 MB chunks, one batch per chunk, never shuffled or down-sampled
+// (sgd_learner.cc:281-286)
+class PartReader {
+ public:
+  PartReader(const Param& P, bool train, int part, int nparts) {
+    if (train)
+      batches_.reset(new ThreadedBatchReader(P.data_in, P.data_format, part, nparts, P.batch_size,
+                                             P.batch_size * P.shuffle, P.neg_sampling,
+                                             P.nthreads));
+    else
+      chunks_.reset(new TextReader(P.data_val, P.data_format, part, nparts, 256 << 20,
+                                   P.nthreads));
+  }
+  bool Next() {
+    if (batches_) return batches_->Next();
+    while (chunks_->Next())
+      if (chunks_->Value().Size() != 0) return true;
+    return false;
+  }
+  const RowBlockContainer<feaid_t>& Value() const {
+    return batches_ ? batches_->Value() : chunks_->Value();
+  }
+
+ private:
+  std::unique_ptr<ThreadedBatchReader> batches_;
+  std::unique_ptr<TextReader> chunks_;
+};
+
+// One pass of one job kind over the shards' parts, the one epoch loop of both exchanges: for
+// job j the shard of global rank g reads part j * nshards + g of num_jobs_per_epoch * nshards
+// (or replays the batches it cached for it), the shards step together (an exhausted shard
+// gives empty batches until the all-reduced "any shard still has a batch" is 0), then the
+// store is flushed and the progress summed over every shard of every rank.
+// pred_files (prediction): local shard l's rows go to pred_files[l] in the order read.
+Progress ShardedPass(ShardRunner* run, const Param& P, int epoch, int job_type, bool record,
+                     const std::vector<FILE*>* pred_files = nullptr) {
+  const int nlocal = run->nlocal(), nshards = run->nranks();
+  const bool train = job_type == GpuSGDLearner::kTraining;
+  const int nparts = P.num_jobs_per_epoch * nshards;
+  std::vector<std::vector<real_t>> preds;
+  for (int job = 0; job < P.num_jobs_per_epoch; ++job) {
+    const int64_t list = CacheList(P, train, job);
+    const bool rec = record && run->has_cache();
+    std::vector<std::unique_ptr<PartReader>> rd(nlocal);
+    std::vector<int64_t> n_cached(nlocal, -1), pos(nlocal, 0);
+    for (int l = 0; l < nlocal; ++l) {
+      if (run->has_cache() && !record) n_cached[l] = run->Cached(l, list);
+      if (n_cached[l] < 0)
+        rd[l].reset(new PartReader(P, train, job * nshards + run->rank(l), nparts));
+    }
+    if (rec) run->BeginList(list);
+    std::vector<bool> more(nlocal, true);
+    for (;;) {
+      std::vector<double> any(1, 0.0);
+      for (int l = 0; l < nlocal; ++l) {
+        if (more[l]) more[l] = rd[l] ? rd[l]->Next() : pos[l] < n_cached[l];
+        if (more[l]) any[0] += 1;
+      }
+      run->AllReduceSum(&any);
+      if (any[0] == 0) break;
+      std::vector<ShardRunner::Item> items(nlocal);
+      for (int l = 0; l < nlocal; ++l) {
+        if (!more[l]) continue;
+        if (rd[l])
+          items[l].host = &rd[l]->Value();
+        else
+          items[l].replay = pos[l]++;
+      }
+      run->Step(items, list, rec, job_type, train && epoch == 0, pred_files ? &preds : nullptr);
+      for (int l = 0; pred_files && l < nlocal; ++l) {  // SavePred
+        if (!items[l].host) continue;
+        const auto& label = items[l].host->label;
+        for (size_t i = 0; i < preds[l].size(); ++i)
+          std::fprintf((*pred_files)[l], "%g\t%g\n", label[i],
+                       P.pred_prob ? 1.0 / (1.0 + std::exp(-preds[l][i])) : (double)preds[l][i]);
+      }
+    }
+    if (rec) run->SealList();
+  }
+  run->Flush();
+  std::vector<double> pr(3, 0.0);
+  for (int l = 0; l < nlocal; ++l) {
+    dfx_progress p;
+    DfxCheck(dfx_progress_read(run->ctx(l), &p, 1), "dfx_progress_read");
+    pr[0] += p.nrows;
+    pr[1] += p.loss;
+    pr[2] += p.auc;
+  }
+  run->AllReduceSum(&pr);
+  Progress out;
+  out.nrows = pr[0];
+  out.loss = pr[1];
+  out.auc = pr[2];
+  return out;
 }
 
+// the sharded runs: training (with data_val: a validation pass after every epoch) and task=2
 int RunSharded(const Param& P, const KWArgs& rest) {
-  if (P.exchange == "split") return RunShardedSplit(P, rest);
-  if (P.exchange != "a2a") {
+  if (P.exchange != "a2a" && P.exchange != "split") {
     std::fprintf(stderr, "exchange must be a2a or split\n");
     return 2;
   }
-  const char* ws = std::getenv("WORLD_SIZE");
-  const int world = ws ? std::atoi(ws) : 1;
-  const bool rccl = world > 1 || P.shards < 0;
-  const int rank = rccl && std::getenv("RANK") ? std::atoi(std::getenv("RANK")) : 0;
-  const int local = std::getenv("LOCAL_RANK") ? std::atoi(std::getenv("LOCAL_RANK")) : 0;
-  const int nlocal = rccl ? 1 : P.shards;
-  const int nshards = rccl ? world : P.shards;
-  if (P.task == 2 || !P.data_val.empty()) {
-    std::fprintf(stderr, "sharded store: training only (task=0, no data_val)\n");
-    return 2;
-  }
-  std::vector<dfx_ctx*> ctxs(nlocal, nullptr);
-  const std::string kw = KwString(rest);
-  for (int l = 0; l < nlocal; ++l)
-    DfxCheck(dfx_ctx_create(rccl ? local : 0, kw.c_str(), &ctxs[l]), "dfx_ctx_create");
-  std::unique_ptr<ShardExchange> ex;
-  if (rccl) {
-    std::string id_file;
-    if (const char* f = std::getenv("DFX_COMM_ID_FILE")) {
-      id_file = f;
-    } else {
-      const char* port = std::getenv("MASTER_PORT");
-      id_file = std::string("/tmp/dfx_comm_") + (port ? port : "0");
-    }
-    ex = MakeRcclExchange(ctxs[0], rank, world, id_file);
-  } else {
-    ex = MakeLoopbackExchange(ctxs);
-  }
+  std::unique_ptr<ShardRunner> run;
+  if (P.exchange == "split")
+    run.reset(new SplitRunner(P, rest));
+  else
+    run.reset(new A2aRunner(P, rest));
+  const int nlocal = run->nlocal(), nshards = run->nranks(), rank = run->rank(0);
   if (!P.model_in.empty()) {
     const int it = P.load_epoch > 0 ? P.load_epoch : -1;
     for (int l = 0; l < nlocal; ++l) {
       if (P.model_in_parts <= 0 || P.model_in_parts == nshards) {
-        DfxCheck(dfx_store_load(ctxs[l], ModelNamePart(P.model_in, it, ex->rank(l)).c_str()),
+        DfxCheck(dfx_store_load(run->ctx(l), ModelNamePart(P.model_in, it, run->rank(l)).c_str()),
                  "dfx_store_load");
       } else {  // saved by a different number of servers: keep the keys this shard owns
         for (int r = 0; r < P.model_in_parts; ++r)
-          DfxCheck(dfx_store_load_part(ctxs[l], ModelNamePart(P.model_in, it, r).c_str(),
-                                       ex->rank(l), nshards),
+          DfxCheck(dfx_store_load_part(run->ctx(l), ModelNamePart(P.model_in, it, r).c_str(),
+                                       run->rank(l), nshards),
                    "dfx_store_load_part");
       }
     }
   }
-  {
-    GpuShardedStore store(ex.get(), P.pipelined);
-    std::vector<std::vector<DevBatch>> dev(nlocal);
-    for (auto& v : dev) v.resize(3);
-    // cache=device: each local shard's batch cache on its own context (list = job), recorded in
-    // the first epoch this run executes; destroyed, joining its context, before the contexts
-    std::vector<std::unique_ptr<DeviceBatchCache>> caches(nlocal);
-    if (P.cache == "device")
-      for (int l = 0; l < nlocal; ++l)
-        caches[l].reset(new DeviceBatchCache(ctxs[l], P.cache_mb << 20));
-    int ring = 0;
-    const double t0 = Now();
-    double pre_loss = 0;
-    const int kfirst = std::max(0, P.load_epoch > 0 ? P.load_epoch + 1 : 0);
-    for (int k = kfirst; k < P.max_num_epochs; ++k) {
-      const double te = Now();
-      const bool record = P.cache == "device" && k == kfirst;
-      for (int job = 0; job < P.num_jobs_per_epoch; ++job) {
-        // shard r reads part job * nshards + r of num_jobs_per_epoch * nshards, or replays the
-        // batches it uploaded for it in the recording epoch
-        const int nparts = P.num_jobs_per_epoch * nshards;
-        std::vector<std::unique_ptr<ThreadedBatchReader>> rd(nlocal);
-        std::vector<int64_t> n_cached(nlocal, -1), pos(nlocal, 0);
-        for (int l = 0; l < nlocal; ++l) {
-          if (caches[l] && !record) n_cached[l] = caches[l]->Count(job);
-          if (n_cached[l] < 0)
-            rd[l].reset(new ThreadedBatchReader(P.data_in, P.data_format,
-                                                job * nshards + ex->rank(l), nparts, P.batch_size,
-                                                P.batch_size * P.shuffle, P.neg_sampling,
-                                                P.nthreads));
-          if (record) caches[l]->Begin(job);
-        }
-        std::vector<bool> more(nlocal, true);
-        for (;;) {
-          std::vector<dfx_batch> bs(nlocal);
-          std::vector<double> any(1, 0.0);
-          for (int l = 0; l < nlocal; ++l) {
-            if (more[l]) more[l] = rd[l] ? rd[l]->Next() : pos[l] < n_cached[l];
-            if (more[l]) any[0] += 1;
-          }
-          ex->AllReduceSum(&any);
-          bool local_any = false;
-          for (int l = 0; l < nlocal; ++l) local_any = local_any || more[l];
-          if (any[0] == 0 && !local_any) break;
-          for (int l = 0; l < nlocal; ++l) {
-            if (more[l] && !rd[l]) {
-              bs[l] = caches[l]->Get(job, pos[l]++);
-              continue;
-            }
-            DevBatch& db = dev[l][ring];
-            db.Upload(ctxs[l], more[l] ? &rd[l]->Value() : nullptr);
-            bs[l] = db.b;
-            if (record && more[l]) caches[l]->Append(db.b);
-          }
-          ring = (ring + 1) % 3;
-          store.Submit(bs, GpuSGDLearner::kTraining, k == 0);
-        }
-        if (record)
-          for (int l = 0; l < nlocal; ++l) caches[l]->Seal();
-      }
-      store.Flush();
-      std::vector<double> pr(3, 0.0);
+  const int kfirst = std::max(0, P.load_epoch > 0 ? P.load_epoch + 1 : 0);
+  if (P.task == 2) {  // one pass over data_val; every worker saves its own rows (SavePred)
+    std::vector<FILE*> files;
+    if (!P.pred_out.empty()) {
       for (int l = 0; l < nlocal; ++l) {
-        dfx_progress p;
-        DfxCheck(dfx_progress_read(ctxs[l], &p, 1), "dfx_progress_read");
-        pr[0] += p.nrows;
-        pr[1] += p.loss;
-        pr[2] += p.auc;
-      }
-      ex->AllReduceSum(&pr);
-      Progress tr;
-      tr.nrows = pr[0];
-      tr.loss = pr[1];
-      tr.auc = pr[2];
-      const double dt = Now() - te;
-      if (rank == 0)
-        std::printf("Epoch[%d] Training: %s  (%.0f ex/s incl. parse+PCIe, %d shards, %.2f s)\n", k,
-                    Text(tr).c_str(), tr.nrows / dt, nshards, Now() - t0);
-      if (record) {  // rank 0 prints the shards' sums
-        std::vector<double> cs(4, 0.0);
-        for (int l = 0; l < nlocal; ++l) {
-          const DeviceBatchCache::Stats s = caches[l]->GetStats();
-          cs[0] += (double)s.batches;
-          cs[1] += (double)s.bytes;
-          cs[2] += (double)s.dropped;
-          cs[3] += (double)(s.sealed + s.dropped);
+        const std::string name = P.pred_out + "_part-" + std::to_string(run->rank(l));
+        files.push_back(std::fopen(name.c_str(), "w"));
+        if (!files.back()) {
+          std::fprintf(stderr, "cannot open %s\n", name.c_str());
+          for (FILE* f : files)
+            if (f) std::fclose(f);
+          return 1;
         }
-        ex->AllReduceSum(&cs);
-        if (rank == 0) PrintCacheLine(cs[0], cs[1], cs[2], cs[3]);
       }
-      std::fflush(stdout);
-      const double eps = std::fabs(tr.loss - pre_loss) / pre_loss;
-      if (eps < P.stop_rel_objv) break;
-      pre_loss = tr.loss;
     }
+    const Progress pr = ShardedPass(run.get(), P, kfirst, GpuSGDLearner::kPrediction, false,
+                                    files.empty() ? nullptr : &files);
+    for (FILE* f : files) std::fclose(f);
+    if (rank == 0) std::printf("Prediction: %s\n", Text(pr).c_str());
+    return 0;
   }
+  const double t0 = Now();
+  double pre_loss = 0, pre_val_auc = 0;
+  for (int k = kfirst; k < P.max_num_epochs; ++k) {
+    const double te = Now();
+    const bool record = k == kfirst;  // the first epoch this run executes records
+    const Progress tr = ShardedPass(run.get(), P, k, GpuSGDLearner::kTraining, record);
+    const double dt = Now() - te;
+    if (rank == 0)
+      std::printf("Epoch[%d] Training: %s  (%.0f ex/s incl. parse+PCIe, %d shards%s, %.2f s)\n", k,
+                  Text(tr).c_str(), tr.nrows / dt, nshards, run->tag(), Now() - t0);
+    Progress va;
+    if (!P.data_val.empty()) {
+      // (the pass above flushed: the 1-step-stale schedule's last push is applied)
+      const double tv = Now();
+      va = ShardedPass(run.get(), P, k, GpuSGDLearner::kValidation, record);
+      if (rank == 0)
+        std::printf("Epoch[%d] Validation: %s  (%.0f ex/s)\n", k, Text(va).c_str(),
+                    va.nrows / (Now() - tv));
+    }
+    if (record && run->has_cache()) {  // rank 0 prints the shards' sums
+      std::vector<double> cs;
+      run->CacheSums(&cs);
+      run->AllReduceSum(&cs);
+      if (rank == 0) PrintCacheLine(cs[0], cs[1], cs[2], cs[3]);
+    }
+    std::fflush(stdout);
+    // stop criteria (sgd_learner.cc:92-106) on the all-reduced sums: the same on every rank,
+    // so all of them leave the loop in the same epoch
+    double eps = std::fabs(tr.loss - pre_loss) / pre_loss;
+    if (eps < P.stop_rel_objv) break;
+    if (va.auc > 0) {
+      eps = (va.auc - pre_val_auc) / va.nrows;
+      if (eps < P.stop_val_auc) break;
+    }
+    pre_loss = tr.loss;
+    pre_val_auc = va.auc;
+  }
+  run->Flush();
   if (!P.model_out.empty())
-    for (int l = 0; l < nlocal; ++l)
-      DfxCheck(dfx_store_save(ctxs[l], ModelNamePart(P.model_out, -1, ex->rank(l)).c_str(),
+    for (int l = 0; l < nlocal; ++l) {
+      DfxCheck(dfx_sync(run->ctx(l)), "dfx_sync");
+      DfxCheck(dfx_store_save(run->ctx(l), ModelNamePart(P.model_out, -1, run->rank(l)).c_str(),
                               P.has_aux ? 1 : 0),
                "dfx_store_save");
-  ex.reset();
-  for (auto c : ctxs) dfx_ctx_destroy(c);
+    }
   return 0;
 }
 }  // namespace
@@ -540,6 +689,7 @@ int main(int argc, char** argv) {
     else if (k == "max_num_epochs") P.max_num_epochs = std::stoi(v);
     else if (k == "num_jobs_per_epoch") P.num_jobs_per_epoch = std::stoi(v);
     else if (k == "stop_rel_objv") P.stop_rel_objv = std::stod(v);
+    else if (k == "stop_val_auc") P.stop_val_auc = std::stod(v);
     else if (k == "nthreads") P.nthreads = std::stoi(v);
     else if (k == "load_epoch") P.load_epoch = std::stoi(v);
     else if (k == "task") P.task = std::stoi(v);
@@ -641,6 +791,10 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
+  if (sharded && P.task == 2 && (P.model_in.empty() || P.data_val.empty())) {
+    std::fprintf(stderr, "prediction needs model_in and data_val\n");  // before any context
+    return 2;
+  }
   if (sharded) return RunSharded(P, rest);
   if (!fused_given) rest.push_back({"fused", "1"});
   GpuSGDLearner learner(rest);
@@ -721,7 +875,7 @@ int main(int argc, char** argv) {
     }
     if (va.auc > 0) {
       eps = (va.auc - pre_val_auc) / va.nrows;
-      if (eps < 1e-5) break;
+      if (eps < P.stop_val_auc) break;
     }
     pre_loss = tr.loss;
     pre_val_auc = va.auc;
