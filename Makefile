@@ -21,7 +21,8 @@ HOSTSRC = $(HOSTLIB) difacto_amd/host/dist_store.cc difacto_amd/host/split_learn
   tests/host/host_tests.cc
 HOSTHDR = difacto_amd/host/iface.h difacto_amd/host/gpu_adapters.h difacto_amd/host/reader.h \
   difacto_amd/host/dist_host.h difacto_amd/host/dist_store.h difacto_amd/host/split_learner.h \
-  difacto_amd/host/device_reader.h include/difacto_amd.h include/difacto_amd_dist.h $(CITYHDR)
+  difacto_amd/host/device_reader.h include/difacto_amd.h include/difacto_amd_dist.h $(CITYHDR) \
+  $(CSRC)/reshuffle.h
 HOSTFLAGS = -std=c++14 -O2 -Wall -pthread
 
 READERBIN = build/reader_tests
@@ -35,7 +36,8 @@ SEBIN = build/shard_eval_tests
 DISTLIB = difacto_amd/libdfx_dist.so
 
 all: $(LIB) $(DISTLIB) oracle $(HOSTBIN) $(TRAINBIN) $(READERBIN) $(GENBIN) $(CONVBIN) $(RBENCH) \
-  $(TPBIN) $(LSBIN) $(SEBIN) build/expf_check build/strtof_check build/gen_libsvm build/locbench
+  $(TPBIN) $(LSBIN) $(SEBIN) build/expf_check build/strtof_check build/gen_libsvm build/locbench \
+  build/reshuffle_check
 
 $(RBENCH): difacto_amd/host/reader.cc tools/reader_bench.cc difacto_amd/host/reader.h $(CITYHDR)
 	@mkdir -p build
@@ -75,6 +77,11 @@ $(LSBIN): $(HOSTLIB) tests/host/libsvmparse_tests.cc $(HOSTHDR) $(CSRC)/strtof.h
 
 # test infrastructure: csrc/strtof.h (the device parser's numbers) against the host's strtof
 build/strtof_check: tools/strtof_check.cc $(CSRC)/strtof.h
+	@mkdir -p build
+	g++ -std=c++14 -O2 -Wall -o $@ $<
+
+# test infrastructure: csrc/reshuffle.h (the reshuffler's permutation) printed from the host
+build/reshuffle_check: tools/reshuffle_check.cc $(CSRC)/reshuffle.h
 	@mkdir -p build
 	g++ -std=c++14 -O2 -Wall -o $@ $<
 

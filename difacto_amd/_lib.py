@@ -142,6 +142,14 @@ _SIGS = {
     "dfx_batchcache_stats_loc": (ctypes.c_int, [vp, i64p]),
     "dfx_train_step_loc": (ctypes.c_int, [vp, ctypes.POINTER(Batch), ctypes.POINTER(Loc),
                                           ctypes.c_int, ctypes.c_int, c_u64, vp]),
+    "dfx_reshuffle_create": (ctypes.c_int, [vp, c_i64, c_i64, ctypes.c_int, ctypes.POINTER(vp),
+                                            ctypes.POINTER(ctypes.c_int)]),
+    "dfx_reshuffle_destroy": (ctypes.c_int, [vp]),
+    "dfx_reshuffle_begin_epoch": (ctypes.c_int, [vp, c_u64, i64p]),
+    "dfx_reshuffle_next": (ctypes.c_int, [vp, ctypes.POINTER(Batch),
+                                          ctypes.POINTER(ctypes.c_int)]),
+    "dfx_reshuffle_consumed": (ctypes.c_int, [vp]),
+    "dfx_reshuffle_stats": (ctypes.c_int, [vp, i64p]),
     "dfx_dist_record_floats": (ctypes.c_int, [vp]),
     "dfx_dist_localize": (ctypes.c_int, [vp, ctypes.POINTER(Batch), c_u64, ctypes.c_int,
                                          ctypes.c_int, vp, vp]),

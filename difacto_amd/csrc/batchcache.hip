@@ -60,6 +60,7 @@ struct dfx_batchcache {
   std::map<int64_t, List> lists;
   int64_t open = -1;
   int64_t n_sealed = 0, n_dropped = 0, n_batches = 0;
+  int held = 0;  // live reshufflers over lists of this cache (reshuffle.hip)
   // kept Localizer outputs (sealed lists): batches, bytes; steps dfx_train_step_loc served
   int64_t n_loc = 0, loc_bytes = 0, served = 0;
   uint64_t loc_seq = 0;               // the context step whose outputs append_loc took last
@@ -78,21 +79,9 @@ inline hipStream_t copy_stream(dfx_batchcache* bc) {
 // one device allocation within the budget -> 1; over the budget or out of device memory -> 0
 // (the HIP error cleared); another HIP failure -> -1 with the error set
 int alloc_within_budget(dfx_batchcache* bc, List* l, int64_t bytes, void** out) {
-  if (bytes > bc->budget - bc->allocated) return 0;
-  void* p = nullptr;
-  const hipError_t e = hipMalloc(&p, (size_t)bytes);
-  if (e == hipErrorOutOfMemory) {
-    (void)hipGetLastError();
-    return 0;
-  }
-  if (e != hipSuccess) {
-    set_error(std::string("batchcache: hipMalloc: ") + hipGetErrorString(e));
-    return -1;
-  }
-  l->allocs.push_back(Alloc{p, bytes});
-  bc->allocated += bytes;
-  *out = p;
-  return 1;
+  const int rc = batchcache_take(bc, bytes, out);
+  if (rc == 1) l->allocs.push_back(Alloc{*out, bytes});
+  return rc;
 }
 
 // room for an array of `bytes` (> 0) on a 256-byte boundary: the tail of the list's block, a new
@@ -145,6 +134,52 @@ void release(dfx_batchcache* bc, List* l) {
   l->copied = false;
 }
 }  // namespace
+
+// ---- the cache's side of a reshuffler (internal.h) --------------------------------------------
+namespace dfx {
+dfx_ctx* batchcache_ctx(dfx_batchcache* bc) { return bc->ctx; }
+
+int batchcache_take(dfx_batchcache* bc, int64_t bytes, void** out) {
+  if (bytes > bc->budget - bc->allocated) return 0;
+  void* p = nullptr;
+  const hipError_t e = hipMalloc(&p, (size_t)bytes);
+  if (e == hipErrorOutOfMemory) {
+    (void)hipGetLastError();
+    return 0;
+  }
+  if (e != hipSuccess) {
+    set_error(std::string("batchcache: hipMalloc: ") + hipGetErrorString(e));
+    return -1;
+  }
+  bc->allocated += bytes;
+  *out = p;
+  return 1;
+}
+
+void batchcache_give(dfx_batchcache* bc, void* p, int64_t bytes) {
+  (void)hipFree(p);
+  bc->allocated -= bytes;
+}
+
+void batchcache_hold(dfx_batchcache* bc, int delta) { bc->held += delta; }
+
+int batchcache_sealed(dfx_batchcache* bc, int64_t list, const dfx_batch** batches, int64_t* n) {
+  const auto it = bc->lists.find(list);
+  DFX_CHECK_ARG(it != bc->lists.end(), "reshuffle_create: no such list");
+  List& l = it->second;
+  DFX_CHECK_ARG(l.state != kOpen, "reshuffle_create: the list is still open (seal it)");
+  DFX_CHECK_ARG(l.state == kSealed, "reshuffle_create: the list was dropped (over budget)");
+  // the reshuffler reads the list on the input stream of now: copies queued elsewhere are joined
+  if (l.copied && (l.streams_differ || l.copy_stream != copy_stream(bc))) {
+    DFX_HIP(hipDeviceSynchronize());
+    l.streams_differ = false;
+    l.copy_stream = copy_stream(bc);
+  }
+  *batches = l.batches.data();
+  *n = (int64_t)l.batches.size();
+  return DFX_OK;
+}
+}  // namespace dfx
 
 // ---- the Localizer's outputs kept with a batch (dfx_batchcache_append_loc) -------------------
 namespace dfx {
@@ -202,6 +237,8 @@ extern "C" int dfx_batchcache_create(dfx_ctx* ctx, int64_t budget_bytes, int64_t
 
 extern "C" int dfx_batchcache_destroy(dfx_batchcache* bc) {
   if (!bc) return DFX_OK;
+  DFX_CHECK_ARG(bc->held == 0,
+                "batchcache_destroy: a reshuffler of this cache is alive (destroy it first)");
   // batches handed out by get may still be read by queued steps, and copies may be queued
   const int rc = dfx_sync(bc->ctx);
   (void)hipSetDevice(bc->ctx->c.device);

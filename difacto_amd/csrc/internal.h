@@ -605,3 +605,18 @@ int evaluate_run(Context* c, int64_t B, const float* label, const float* pred, d
 struct dfx_ctx {
   dfx::Context c;
 };
+
+namespace dfx {
+// The batch cache's side of a reshuffler (batchcache.hip; reshuffle.hip is the caller).
+// batchcache_sealed: the batches of a sealed list, valid until the cache is destroyed, their
+// copies joined if they ran on another stream than the context's input stream of now;
+// DFX_ERR_ARG for an open, dropped or unknown list.  batchcache_take: a device allocation
+// inside the cache's budget -> 1; over the budget or out of device memory -> 0; another HIP
+// failure -> -1 with the error set.  batchcache_give returns one.  batchcache_hold counts the
+// live reshufflers (dfx_batchcache_destroy refuses while there is one).
+dfx_ctx* batchcache_ctx(dfx_batchcache* bc);
+int batchcache_sealed(dfx_batchcache* bc, int64_t list, const dfx_batch** batches, int64_t* n);
+int batchcache_take(dfx_batchcache* bc, int64_t bytes, void** out);
+void batchcache_give(dfx_batchcache* bc, void* p, int64_t bytes);
+void batchcache_hold(dfx_batchcache* bc, int delta);
+}  // namespace dfx

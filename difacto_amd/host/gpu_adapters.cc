@@ -616,6 +616,46 @@ DeviceBatchCache::Stats DeviceBatchCache::GetStats() const {
   return out;
 }
 
+// ---- device reshuffler ---------------------------------------------------------------------
+DeviceReshuffler::DeviceReshuffler(DeviceBatchCache* cache, int64_t list, int64_t batch_rows,
+                                   int nring) {
+  int kept = 0;
+  DfxCheck(dfx_reshuffle_create(cache->h(), list, batch_rows, nring, &h_, &kept),
+           "dfx_reshuffle_create");
+  if (!kept) h_ = nullptr;
+}
+
+DeviceReshuffler::~DeviceReshuffler() {
+  if (h_) dfx_reshuffle_destroy(h_);
+}
+
+int64_t DeviceReshuffler::BeginEpoch(uint64_t key) {
+  int64_t n = 0;
+  DfxCheck(dfx_reshuffle_begin_epoch(h_, key, &n), "dfx_reshuffle_begin_epoch");
+  return n;
+}
+
+bool DeviceReshuffler::Next(dfx_batch* b) {
+  int has = 0;
+  DfxCheck(dfx_reshuffle_next(h_, b, &has), "dfx_reshuffle_next");
+  return has != 0;
+}
+
+void DeviceReshuffler::Consumed() {
+  DfxCheck(dfx_reshuffle_consumed(h_), "dfx_reshuffle_consumed");
+}
+
+DeviceReshuffler::Stats DeviceReshuffler::GetStats() const {
+  int64_t s[4] = {0, 0, 0, 0};
+  DfxCheck(dfx_reshuffle_stats(h_, s), "dfx_reshuffle_stats");
+  Stats out;
+  out.rows = s[0];
+  out.batches = s[1];
+  out.ring_bytes = s[2];
+  out.scratch_bytes = s[3];
+  return out;
+}
+
 // ---- reader ------------------------------------------------------------------------------
 bool ReadLibSVM(const std::string& path, RowBlockContainer<feaid_t>* out) {
   std::ifstream in(path, std::ios::binary);

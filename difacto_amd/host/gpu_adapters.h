@@ -242,8 +242,35 @@ class DeviceBatchCache {
   };
   LocStats GetLocStats() const;
 
+  dfx_batchcache* h() const { return h_; }
+
  private:
   dfx_batchcache* h_ = nullptr;
+};
+
+/** a fresh shuffle per epoch of one sealed list of a DeviceBatchCache (dfx_reshuffle_*,
+ * include/difacto_amd.h); destroyed before its cache */
+class DeviceReshuffler {
+ public:
+  /** kept() false: the ring and the scratch did not fit the cache's budget */
+  DeviceReshuffler(DeviceBatchCache* cache, int64_t list, int64_t batch_rows, int nring = 2);
+  ~DeviceReshuffler();
+  DeviceReshuffler(const DeviceReshuffler&) = delete;
+  DeviceReshuffler& operator=(const DeviceReshuffler&) = delete;
+  bool kept() const { return h_ != nullptr; }
+  /** the epoch keyed by `key` -> its batch count; -1: the ring no longer fits (replay the list) */
+  int64_t BeginEpoch(uint64_t key);
+  /** the next batch, ready by the context's input stream's order; false past the last */
+  bool Next(dfx_batch* b);
+  /** after the step that took the batch */
+  void Consumed();
+  struct Stats {
+    int64_t rows = 0, batches = 0, ring_bytes = 0, scratch_bytes = 0;
+  };
+  Stats GetStats() const;
+
+ private:
+  dfx_reshuffle* h_ = nullptr;
 };
 
 /** a libsvm reader ("label idx:val ..."): the thin CSR producer the path's caller uses */

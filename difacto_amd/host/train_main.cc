@@ -7,8 +7,8 @@
 //                   [model_in=F] [model_out=F]
 //                   [load_epoch=-1] [has_aux=0] [task=0|2] [pred_out=F] [pred_prob=1]
 //                   [fused=1] [nthreads=8] [parse=host|device|auto] [cache=none|device]
-//                   [cache_mb=16384] [cache_loc=0] [V_dim=..] [lr=..] [l1=..] ...
-//                   (SGDUpdaterParam)
+//                   [cache_mb=16384] [cache_loc=0] [epoch_shuffle=0] [shuffle_seed=0]
+//                   [V_dim=..] [lr=..] [l1=..] ... (SGDUpdaterParam)
 //
 // parse=device (data_format=criteo|criteo_test, the single-GPU fused path: training, data_val
 // validation and task=2 prediction): the raw text is copied to pinned memory and uploaded, the
@@ -45,6 +45,23 @@
 // left out and their batches replay with the Localizer.  One more line after the cache's
 // reports the batches that hold outputs and their MB.  Without cache=device, with fused=0,
 // task=2 or in a sharded run it is an error (exit 2).  Default 0: the run as without it.
+//
+// epoch_shuffle=1 (with cache=device, the single-GPU fused path, not task=2, not cache_loc=1):
+// a reader seeds its shuffle afresh, so a part yields the same rows in the same batches in every
+// epoch, cached or not; the reference's BatchReader draws from the process-wide rand() state,
+// which is never reseeded (src/reader/batch_reader.cc:38-45), so its epochs see other batch
+// compositions.  With this option the recording epoch is unchanged, and in every later epoch each
+// TRAINING part whose list is sealed is stepped through a device reshuffler (DeviceReshuffler,
+// gpu_adapters.h; dfx_reshuffle_*): all rows of the part in the order of a keyed permutation
+// (csrc/reshuffle.h, key = rs_epoch_key(shuffle_seed, epoch, list)), cut into batches of
+// batch_size rows, gathered on the device out of the cached batches, which stay as they are.
+// Parts run in order and validation lists replay as recorded; a part that is not cached, or whose
+// reshuffler did not fit cache_mb, goes the way it goes without the option.  The same
+// shuffle_seed gives the same run.  One line after the cache's says how many parts reshuffle and
+// the MB their rings and scratch take, and every reshuffled epoch prints the time the host
+// waited for the batches' sizes (once per part).  Without cache=device, with cache_loc=1 (new
+// batches have no kept Localizer outputs), fused=0, task=2 or in a sharded run it is an error
+// (exit 2).  Default 0: the run as without it.
 //
 // Sharded store (KVStoreDist over GPUs, dist_host.h): `shards=N` holds N shards on this GPU
 // (loopback exchange, for tests); `shards=-1` or a launch with WORLD_SIZE > 1 (RANK / LOCAL_RANK as
@@ -87,6 +104,7 @@
 #include <vector>
 #include <string>
 
+#include "../csrc/reshuffle.h"
 #include "device_reader.h"
 #include "dist_host.h"
 #include "gpu_adapters.h"
@@ -113,6 +131,8 @@ struct Param {
   std::string cache = "none";  // device: formed batches kept in HBM, replayed after the first epoch
   int64_t cache_mb = 16384;    // its budget (per shard)
   bool cache_loc = false;      // the Localizer's outputs kept with the cached batches too
+  bool epoch_shuffle = false;  // replayed training parts are reshuffled on the device per epoch
+  uint64_t shuffle_seed = 0;   // ... keyed by (shuffle_seed, epoch, list)
 };
 
 // sgd_learner.h:65-69
@@ -155,7 +175,9 @@ void PrintCacheLine(double batches, double bytes, double dropped, double parts) 
 Progress RunEpoch(GpuSGDLearner* learner, const Param& P, int epoch, int job_type,
                   FILE* pred_file = nullptr, DeviceTextFeed* feed = nullptr,
                   DeviceBatchReader::Times* times = nullptr, double* step_s = nullptr,
-                  DeviceBatchCache* cache = nullptr, bool record = false) {
+                  DeviceBatchCache* cache = nullptr, bool record = false,
+                  std::vector<std::unique_ptr<DeviceReshuffler>>* resh = nullptr,
+                  double* shuffle_wait = nullptr) {
   Progress prog;
   std::vector<real_t> pred;
   const bool train = job_type == GpuSGDLearner::kTraining;
@@ -167,7 +189,25 @@ Progress RunEpoch(GpuSGDLearner* learner, const Param& P, int epoch, int job_typ
     const bool rec_loc = rec && P.cache_loc;  // each step's Localizer outputs with its batch
     const int64_t n_cached = cache && !record ? cache->Count(list) : -1;
     if (rec) cache->Begin(list);
-    if (n_cached >= 0) {
+    // epoch_shuffle=1: the part's rows in this epoch's order; -1: its ring no longer fits
+    DeviceReshuffler* rs = train && n_cached >= 0 && resh && (*resh)[part] ? (*resh)[part].get()
+                                                                          : nullptr;
+    int64_t n_shuffled = -1;
+    if (rs) {
+      const double tb = Now();
+      n_shuffled = rs->BeginEpoch(rs_epoch_key(P.shuffle_seed, (uint64_t)epoch, (uint64_t)list));
+      if (shuffle_wait) shuffle_wait[0] += Now() - tb;
+    }
+    if (n_shuffled >= 0) {
+      dfx_batch b;
+      while (rs->Next(&b)) {
+        const double ts = Now();
+        learner->ProcessDeviceBatch(b, job_type, train && epoch == 0);
+        rs->Consumed();
+        if (step_s) step_s[0] += Now() - ts;
+      }
+      if (shuffle_wait) shuffle_wait[1] += 1;
+    } else if (n_cached >= 0) {
       for (int64_t i = 0; i < n_cached; ++i) {
         const dfx_batch b = cache->Get(list, i);
         dfx_loc loc;
@@ -704,6 +744,8 @@ int main(int argc, char** argv) {
     else if (k == "cache") P.cache = v;
     else if (k == "cache_mb") P.cache_mb = std::stoll(v);
     else if (k == "cache_loc") P.cache_loc = std::stoi(v) != 0;
+    else if (k == "epoch_shuffle") P.epoch_shuffle = std::stoi(v) != 0;
+    else if (k == "shuffle_seed") P.shuffle_seed = std::stoull(v);
     else {
       fused_given = fused_given || k == "fused";
       rest.push_back({k, v});
@@ -775,6 +817,26 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
+  if (P.epoch_shuffle) {  // no silent run in the recorded order
+    bool fused = true;
+    for (const auto& kv : rest)
+      if (kv.first == "fused") fused = std::stoi(kv.second) != 0;
+    const char* why = nullptr;
+    if (P.cache != "device")
+      why = "cache=device (the rows are reshuffled out of the cached batches)";
+    else if (P.cache_loc)
+      why = "cache_loc=0 (reshuffled batches have no kept Localizer outputs)";
+    else if (!fused)
+      why = "the fused path (fused=1)";
+    else if (P.task == 2)
+      why = "a training run (task=2 is one pass: nothing is replayed)";
+    else if (sharded)
+      why = "the single-GPU run (shards=0)";
+    if (why) {
+      std::fprintf(stderr, "epoch_shuffle=1 needs %s\n", why);
+      return 2;
+    }
+  }
   if (P.cache == "device") {  // no silent run without the cache
     bool fused = true;
     for (const auto& kv : rest)
@@ -806,6 +868,9 @@ int main(int argc, char** argv) {
   std::unique_ptr<DeviceBatchCache> cache;
   if (P.cache == "device" && P.task != 2)
     cache.reset(new DeviceBatchCache(learner.context(), P.cache_mb << 20));
+  // epoch_shuffle=1: one reshuffler per training part, made after the recording epoch (declared
+  // after the cache: destroyed before it)
+  std::vector<std::unique_ptr<DeviceReshuffler>> resh;
   int k0 = 0;
   if (!P.model_in.empty()) {  // sgd_learner.cc:58-67
     FileStream fi(ModelName(P.model_in, P.load_epoch > 0 ? P.load_epoch : -1).c_str(), "rb");
@@ -837,11 +902,17 @@ int main(int argc, char** argv) {
     DeviceBatchReader::Times rt;
     double step_s[2] = {0, 0};  // inside dfx_train_step calls; the epoch's final join
     const bool record = k == k0;  // the first epoch this run executes records
+    double shuffle_wait[2] = {0, 0};  // the host's wait for the batches' sizes; parts reshuffled
     const Progress tr = RunEpoch(&learner, P, k, GpuSGDLearner::kTraining, nullptr, feed.get(),
-                                 &rt, step_s, cache.get(), record);
+                                 &rt, step_s, cache.get(), record,
+                                 resh.empty() ? nullptr : &resh, shuffle_wait);
     const double dt = Now() - te;
     std::printf("Epoch[%d] Training: %s  (%.0f ex/s incl. parse+PCIe, %.2f s)\n", k,
                 Text(tr).c_str(), tr.nrows / dt, Now() - t0);
+    if (shuffle_wait[1] > 0)
+      std::printf("  epoch_shuffle: %.0f parts reshuffled, the host waited %.3f ms for their "
+                  "batches' sizes\n",
+                  shuffle_wait[1], shuffle_wait[0] * 1e3);
     if (feed)  // where the device reader's time went (device_reader.h Times)
       std::printf("  reader: epoch %.3f s, host copy %.3f s (loader thread); caller waited for "
                   "text %.3f s, for the parse %.3f s, for a ring batch %.3f s, in dfx_train_step "
@@ -864,6 +935,28 @@ int main(int argc, char** argv) {
                     "%.1f MB held\n",
                     (long long)ls.batches, (long long)cs.batches, (double)ls.bytes / (1 << 20),
                     (double)cs.bytes / (1 << 20));
+      }
+      if (P.epoch_shuffle) {
+        int made = 0;
+        int64_t ring = 0, scratch = 0;
+        resh.resize((size_t)P.num_jobs_per_epoch);
+        for (int part = 0; part < P.num_jobs_per_epoch; ++part) {
+          const int64_t list = CacheList(P, true, part);
+          if (cache->Count(list) < 0) continue;  // not cached: read as without the option
+          resh[part].reset(new DeviceReshuffler(cache.get(), list, (int64_t)P.batch_size, 4));
+          if (!resh[part]->kept()) {
+            resh[part].reset();
+            continue;
+          }
+          const DeviceReshuffler::Stats rs = resh[part]->GetStats();
+          ring += rs.ring_bytes;
+          scratch += rs.scratch_bytes;
+          ++made;
+        }
+        std::printf("epoch_shuffle=1: %d of %d training parts reshuffle, rings %.1f MB, scratch "
+                    "%.1f MB\n",
+                    made, P.num_jobs_per_epoch, (double)ring / (1 << 20),
+                    (double)scratch / (1 << 20));
       }
     }
     std::fflush(stdout);

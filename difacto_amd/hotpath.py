@@ -481,8 +481,64 @@ class BatchCache:
 
     def close(self):
         if getattr(self, "h", None):
+            for rs in list(getattr(self, "_reshufflers", ())):  # they read this cache
+                rs.close()
             h, self.h = self.h, None
             check(_lib.lib().dfx_batchcache_destroy(h))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Reshuffler:
+    """A fresh shuffle of a sealed list of a BatchCache per epoch (dfx_reshuffle_*,
+    include/difacto_amd.h): begin_epoch(key) -> the epoch's batch count, then next() /
+    train_step / consumed() per batch.  kept: False when the ring and the scratch did not fit
+    the cache's budget (every other call then raises: replay the list as recorded)."""
+
+    def __init__(self, bc, list_id, batch_rows, nring=2):
+        self.bc, self.ctx = bc, bc.ctx
+        h, kept = ctypes.c_void_p(), ctypes.c_int(0)
+        check(_lib.lib().dfx_reshuffle_create(bc.h, int(list_id), int(batch_rows), int(nring),
+                                              ctypes.byref(h), ctypes.byref(kept)))
+        self.h = h if kept.value else None
+        self.kept = bool(kept.value)
+        if self.kept:
+            if not hasattr(bc, "_reshufflers"):
+                bc._reshufflers = weakref.WeakSet()  # BatchCache.close closes them first
+            bc._reshufflers.add(self)
+
+    def begin_epoch(self, key):
+        """-> the number of batches of the epoch keyed by ``key`` (any 64 bits); -1: the ring
+        had to grow and no longer fits the budget"""
+        n = ctypes.c_int64(0)
+        check(_lib.lib().dfx_reshuffle_begin_epoch(self.h, ctypes.c_uint64(int(key)),
+                                                   ctypes.byref(n)))
+        return n.value
+
+    def next(self):
+        """-> the next batch (a CachedBatch whose pointers point into the ring), None past the
+        last one"""
+        b, has = _lib.Batch(), ctypes.c_int(0)
+        check(_lib.lib().dfx_reshuffle_next(self.h, ctypes.byref(b), ctypes.byref(has)))
+        return CachedBatch(self.ctx, b) if has.value else None
+
+    def consumed(self):
+        """after the train_step that took the batch next() handed out"""
+        check(_lib.lib().dfx_reshuffle_consumed(self.h))
+
+    def stats(self):
+        out = (ctypes.c_int64 * 4)()
+        check(_lib.lib().dfx_reshuffle_stats(self.h, out))
+        return dict(zip(("rows", "batches", "ring_bytes", "scratch_bytes"), list(out)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            h, self.h = self.h, None
+            check(_lib.lib().dfx_reshuffle_destroy(h))
 
     def __del__(self):
         try:

@@ -291,7 +291,8 @@ int dfx_textfeed_slot_consumed(dfx_textfeed* f, int slot);
  * append that does not fit drops the open list: *kept = 0 with DFX_OK (so do later appends),
  * its blocks are freed after joining the stream that copies into them, get on it is
  * DFX_ERR_ARG; sealed lists are untouched and a later list may use the freed budget.  Training
- * never fails because the cache could not grow.  destroy joins the context (dfx_sync) first.
+ * never fails because the cache could not grow.  destroy joins the context (dfx_sync) first; with
+ * a live reshuffler (dfx_reshuffle_create) it is DFX_ERR_ARG and the cache stays.
  * DFX_ERR_ARG: append / seal with no open list, begin while one is open or of an id already
  * sealed or dropped, get of an open list or with i out of range, negative sizes, a batch with
  * rows but no offset or label. */
@@ -377,6 +378,59 @@ int dfx_batchcache_get_loc(dfx_batchcache* bc, int64_t list, int64_t i, dfx_loc*
 int dfx_batchcache_stats_loc(dfx_batchcache* bc, int64_t* out); /* out[3] */
 int dfx_train_step_loc(dfx_ctx* ctx, const dfx_batch* batch, const dfx_loc* loc, int job_type,
                        int push_cnt, uint64_t max_index, float* pred_out);
+
+/* ---- a fresh shuffle of a cached list per epoch (difacto_amd/csrc/reshuffle.hip) -----------
+ * The cache replays a part's batches as recorded, the same rows in the same batches in every
+ * epoch.  The reference's BatchReader shuffles with the process-wide rand() state, which is never
+ * reseeded (src/reader/batch_reader.cc:38-45), so its epochs see other batch compositions.  A
+ * reshuffler hands out, per epoch, the N rows of a SEALED list (the concatenation of its batches
+ * in order) in the order of a keyed bijection of [0, N) (csrc/reshuffle.h: rs_perm, a Feistel
+ * network with cycle walking, computed per row on the device — no permutation array, no sort, no
+ * host list), cut every batch_rows rows; the last batch holds the remainder.  A destination
+ * batch has value iff some batch of the list has, and a binary source reads as ones
+ * (dfx_gather_rows_valued's rule); the same for weight: absent reads as 1.0f.  The sources are
+ * only read: after any number of epochs the cached batches are the bytes they were.
+ *   dfx_reshuffle_create      a device table of the batches' five pointers and their row prefix,
+ *                             12 bytes a row of per-epoch scratch and a ring of nring (2..8)
+ *                             destination batches, all out of the cache's budget, every array on
+ *                             a 256-byte boundary; *kept = 1.  What does not fit the budget (or
+ *                             hipMalloc out of memory): *kept = 0, *out = NULL with DFX_OK, the
+ *                             cache untouched — training never fails because this could not grow
+ *   dfx_reshuffle_begin_epoch on the context's input stream: one kernel computes for every output
+ *                             position its source row (rs_perm, a bisection of the row prefix)
+ *                             and that row's length, a scan per output batch gives every row's
+ *                             offset inside its batch and the batch's nnz, which go to a pinned
+ *                             host array; the host waits for them ONCE per epoch (dfx_batch.nnz
+ *                             is a host value), never per batch.  *n_batches = ceil(N /
+ *                             batch_rows).  A ring whose nnz capacity (it starts at 1.25 times
+ *                             the mean batch) is below this epoch's largest batch is regrown here,
+ *                             after the ring's `consumed` events, inside the budget; if it no
+ *                             longer fits, *n_batches = -1 (DFX_OK) and the caller replays the
+ *                             list as recorded (a later begin_epoch tries again)
+ *   dfx_reshuffle_next        the input stream waits for the ring entry's `consumed` event (a
+ *                             stream wait: the host never blocks), then ONE launch, a wave per
+ *                             row, recomputes each row's source and moves its ids, values, label
+ *                             and weight and writes the rebased offsets.  *has = 0 past the last
+ *                             batch.  The batch is ready by the input stream's order, as a text
+ *                             feed's, and stays valid until nring - 1 further batches were taken
+ *   dfx_reshuffle_consumed    after the dfx_train_step that took the batch: records the ring
+ *                             entry's event on the context stream (as dfx_textfeed_consumed)
+ *   dfx_reshuffle_stats       out[4] = {N, batches per epoch, the ring's bytes, the table's and
+ *                             the scratch's bytes}
+ *   dfx_reshuffle_destroy     joins the device; must come before the cache's own destroy
+ *                             (dfx_batchcache_destroy with a live reshuffler is DFX_ERR_ARG)
+ * key: any 64 bits; rs_epoch_key(shuffle_seed, epoch, list) is the driver's.  The same key gives
+ * the same batches.  DFX_ERR_ARG: an open, dropped or unknown list, N >= 2^31, batch_rows <= 0,
+ * nring outside 2..8, next before begin_epoch (or after one that returned -1), consumed with no
+ * batch handed out; a rejected call queues nothing. */
+typedef struct dfx_reshuffle dfx_reshuffle;
+int dfx_reshuffle_create(dfx_batchcache* bc, int64_t list, int64_t batch_rows, int nring,
+                         dfx_reshuffle** out, int* kept);
+int dfx_reshuffle_destroy(dfx_reshuffle* rs);
+int dfx_reshuffle_begin_epoch(dfx_reshuffle* rs, uint64_t key, int64_t* n_batches);
+int dfx_reshuffle_next(dfx_reshuffle* rs, dfx_batch* batch, int* has);
+int dfx_reshuffle_consumed(dfx_reshuffle* rs);
+int dfx_reshuffle_stats(dfx_reshuffle* rs, int64_t* out); /* out[4] */
 
 /* ---- Localizer::Compact (localizer.h:41-51) -------------------------------------------
  * keys = ReverseBytes(index % max_index); uniq[U] ascending, cnt[U] occurrence counts
