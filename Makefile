@@ -32,11 +32,12 @@ RBENCH = build/reader_bench
 TPBIN = build/textparse_tests
 LSBIN = build/libsvmparse_tests
 SEBIN = build/shard_eval_tests
+SDBIN = build/split_device_tests
 
 DISTLIB = difacto_amd/libdfx_dist.so
 
 all: $(LIB) $(DISTLIB) oracle $(HOSTBIN) $(TRAINBIN) $(READERBIN) $(GENBIN) $(CONVBIN) $(RBENCH) \
-  $(TPBIN) $(LSBIN) $(SEBIN) build/expf_check build/strtof_check build/gen_libsvm build/locbench \
+  $(TPBIN) $(LSBIN) $(SEBIN) $(SDBIN) build/expf_check build/strtof_check build/gen_libsvm build/locbench \
   build/reshuffle_check
 
 $(RBENCH): difacto_amd/host/reader.cc tools/reader_bench.cc difacto_amd/host/reader.h $(CITYHDR)
@@ -104,6 +105,16 @@ $(SEBIN): $(HOSTLIB) difacto_amd/host/split_learner.cc tests/host/shard_eval_tes
 	@mkdir -p build
 	g++ $(HOSTFLAGS) -o $@ $(HOSTLIB) difacto_amd/host/split_learner.cc \
 	  tests/host/shard_eval_tests.cc build/obj/dist_host.o \
+	  -Ldifacto_amd -ldifacto_amd -ldfx_dist -L/opt/rocm/lib -lrccl -lamdhip64 \
+	  -Wl,-rpath,'$$ORIGIN/../difacto_amd' -Wl,-rpath,/opt/rocm/lib
+
+# GpuSplitLearner's device entry (ProcessDeviceBatches: device, mixed and replayed steps) against
+# the same steps fed host row blocks, bit for bit
+$(SDBIN): $(HOSTLIB) difacto_amd/host/split_learner.cc tests/host/split_device_tests.cc $(HOSTHDR) \
+  build/obj/dist_host.o $(LIB) $(DISTLIB)
+	@mkdir -p build
+	g++ $(HOSTFLAGS) -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -o $@ $(HOSTLIB) \
+	  difacto_amd/host/split_learner.cc tests/host/split_device_tests.cc build/obj/dist_host.o \
 	  -Ldifacto_amd -ldifacto_amd -ldfx_dist -L/opt/rocm/lib -lrccl -lamdhip64 \
 	  -Wl,-rpath,'$$ORIGIN/../difacto_amd' -Wl,-rpath,/opt/rocm/lib
 

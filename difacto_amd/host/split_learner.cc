@@ -35,10 +35,15 @@ struct GpuSplitLearner::Impl {
   // the step being assembled from the local workers' calls
   std::mutex mu;
   std::condition_variable cv;
-  std::vector<const dmlc::RowBlock<feaid_t>*> pend;
+  std::vector<GpuSplitLearner::Item> pend;
+  std::vector<bool> pend_set;
   std::vector<int> pend_job, pend_cnt;
   std::vector<std::vector<real_t>*> pend_pred;  // where a worker wants its predictions
+  std::vector<dfx_batch>* pend_dev = nullptr;   // where the caller wants the device batches
   std::vector<std::unique_ptr<DevArray<float>>> dpred;  // their device buffers
+  // the queued (pipelined) step's batch of worker l sits in its feeder's newest slot: a device
+  // item or none holds no slot, and the learner owes it nothing
+  std::vector<bool> queued_host;
   int arrived = 0;
   int64_t gen = 0;
   std::string failure;
@@ -51,19 +56,24 @@ struct GpuSplitLearner::Impl {
     for (dfx_ctx* c : ctxs) (void)dfx_ctx_destroy(c);
   }
 
-  // feeders with room for every pending batch (3 staging slots: a pipelined step reads its
-  // batch until the submit after it)
+  // feeders with room for every pending host batch (3 staging slots: a pipelined step reads
+  // its batch until the submit after it)
   void Feeders() {
     int64_t rows = 0, nnz = 0;
-    for (const auto* b : pend) {
-      rows = std::max<int64_t>(rows, (int64_t)b->size);
-      nnz = std::max<int64_t>(nnz, b->size ? (int64_t)b->offset[b->size] : 0);
+    bool any = false;
+    for (const auto& it : pend) {
+      if (!it.host) continue;
+      any = true;
+      rows = std::max<int64_t>(rows, (int64_t)it.host->size);
+      nnz = std::max<int64_t>(nnz, it.host->size ? (int64_t)it.host->offset[it.host->size] : 0);
     }
+    if (!any) return;  // nothing to stage
     if (!feeders.empty() && rows <= cap_rows && nnz <= cap_nnz) return;
     // grow: every queued step must be done with the old staging buffers first (the store's
     // sync also frees the step buffers it outgrew)
     if (store) DistCheck(dfx_split_store_sync(store), "dfx_split_store_sync");
     queued = false;
+    queued_host.assign(L, false);
     for (dfx_ctx* c : ctxs) DfxCheck(dfx_sync(c), "dfx_sync");
     for (dfx_feeder* f : feeders) DfxCheck(dfx_feeder_destroy(f), "dfx_feeder_destroy");
     feeders.assign(L, nullptr);
@@ -74,12 +84,30 @@ struct GpuSplitLearner::Impl {
                "dfx_feeder_create_slots");
   }
 
-  // the last local worker's call: every pending batch uploaded, one step submitted
+  // the queued step ran (a flush): the staging slots of its host items are free behind it
+  void QueuedRan() {
+    for (int l = 0; l < L; ++l)
+      if (queued_host[l]) DfxCheck(dfx_feeder_consumed(feeders[l]), "dfx_feeder_consumed");
+    queued_host.assign(L, false);
+    queued = false;
+  }
+
+  // the last local worker's call: every pending host batch uploaded, one step submitted
   void Submit(int job, bool push_cnt) {
     Feeders();
     std::vector<dfx_batch> b(L);
     for (int l = 0; l < L; ++l) {
-      const dmlc::RowBlock<feaid_t>& x = *pend[l];
+      DFX_HOST_CHECK(!(pend[l].host && pend[l].dev),
+                     "split learner: an item is a host block or a device batch, not both");
+      if (pend[l].dev) {  // as it is: no staging, no copy
+        b[l] = *pend[l].dev;
+        continue;
+      }
+      if (!pend[l].host) {  // none: an empty batch (no kernel reads its arrays)
+        b[l] = dfx_batch{};
+        continue;
+      }
+      const dmlc::RowBlock<feaid_t>& x = *pend[l].host;
       const int64_t B = (int64_t)x.size, nnz = B ? (int64_t)x.offset[B] : 0;
       DFX_HOST_CHECK(B == 0 || x.offset[0] == 0, "split learner: offset[0] must be 0");
       dfx_host_batch hb;
@@ -98,6 +126,7 @@ struct GpuSplitLearner::Impl {
                                  x.weight != nullptr && B > 0, &b[l]),
                "dfx_feeder_submit");
     }
+    if (pend_dev) *pend_dev = b;
     bool want_pred = false;
     for (const auto* p : pend_pred) want_pred = want_pred || p != nullptr;
     std::vector<float*> dp(L, nullptr);
@@ -113,11 +142,19 @@ struct GpuSplitLearner::Impl {
     DistCheck(dfx_split_store_submit(store, b.data(), job, push_cnt ? 1 : 0,
                                      want_pred ? dp.data() : nullptr),
               "dfx_split_store_submit");
-    // a pipelined submit queued the previous step, the last reader of the previous batch
-    for (int l = 0; l < L; ++l)
-      DfxCheck(pipelined ? (queued ? dfx_feeder_consumed_back(feeders[l], 1) : DFX_OK)
-                         : dfx_feeder_consumed(feeders[l]),
-               "dfx_feeder_consumed");
+    // a pipelined submit queued the previous step, the last reader of the previous batch: of a
+    // worker whose previous item was a host block, that is the slot one back when this item
+    // took a slot too, else still the feeder's newest.  Device items are never counted.
+    for (int l = 0; l < L; ++l) {
+      const bool host = pend[l].host != nullptr;
+      if (pipelined) {
+        if (queued && queued_host[l])
+          DfxCheck(dfx_feeder_consumed_back(feeders[l], host ? 1 : 0), "dfx_feeder_consumed");
+      } else if (host) {
+        DfxCheck(dfx_feeder_consumed(feeders[l]), "dfx_feeder_consumed");
+      }
+      queued_host[l] = pipelined && host;
+    }
     queued = pipelined;
     ++submits;
     if (!want_pred) return;
@@ -125,8 +162,7 @@ struct GpuSplitLearner::Impl {
     // context streams, behind the combine that wrote them
     if (queued) {
       DistCheck(dfx_split_store_flush(store), "dfx_split_store_flush");
-      for (dfx_feeder* f : feeders) DfxCheck(dfx_feeder_consumed(f), "dfx_feeder_consumed");
-      queued = false;
+      QueuedRan();
     }
     for (int l = 0; l < L; ++l) {
       if (!pend_pred[l]) continue;
@@ -224,10 +260,12 @@ std::shared_ptr<GpuSplitLearner> GpuSplitLearner::CreateRccl(const KWArgs& kwarg
 }
 
 GpuSplitLearner::GpuSplitLearner(std::unique_ptr<Impl> impl) : impl_(std::move(impl)) {
-  impl_->pend.assign(impl_->L, nullptr);
+  impl_->pend.assign(impl_->L, Item());
+  impl_->pend_set.assign(impl_->L, false);
   impl_->pend_job.assign(impl_->L, 0);
   impl_->pend_cnt.assign(impl_->L, 0);
   impl_->pend_pred.assign(impl_->L, nullptr);
+  impl_->queued_host.assign(impl_->L, false);
 }
 
 GpuSplitLearner::~GpuSplitLearner() {}
@@ -248,8 +286,9 @@ void GpuSplitLearner::ProcessBatch(int local, const dmlc::RowBlock<feaid_t>& bat
   push_cnt = push_cnt && job_type == kTraining;
   std::unique_lock<std::mutex> lk(m.mu);
   DFX_HOST_CHECK(m.failure.empty(), "GpuSplitLearner: " + m.failure);
-  DFX_HOST_CHECK(m.pend[local] == nullptr, "GpuSplitLearner: two batches of one worker in a step");
-  m.pend[local] = &batch;
+  DFX_HOST_CHECK(!m.pend_set[local], "GpuSplitLearner: two batches of one worker in a step");
+  m.pend[local].host = &batch;
+  m.pend_set[local] = true;
   m.pend_job[local] = job_type;
   m.pend_cnt[local] = push_cnt ? 1 : 0;
   m.pend_pred[local] = pred;
@@ -265,7 +304,8 @@ void GpuSplitLearner::ProcessBatch(int local, const dmlc::RowBlock<feaid_t>& bat
       m.failure = "the local workers' calls of one step differ in job type or count push";
   if (m.failure.empty()) m.Submit(job_type, push_cnt);
   m.arrived = 0;
-  for (auto& p : m.pend) p = nullptr;
+  m.pend.assign(m.L, Item());
+  m.pend_set.assign(m.L, false);
   for (auto& p : m.pend_pred) p = nullptr;
   ++m.gen;
   m.cv.notify_all();
@@ -275,8 +315,20 @@ void GpuSplitLearner::ProcessBatch(int local, const dmlc::RowBlock<feaid_t>& bat
 void GpuSplitLearner::ProcessBatches(const std::vector<const dmlc::RowBlock<feaid_t>*>& batches,
                                      int job_type, bool push_cnt,
                                      std::vector<std::vector<real_t>>* preds) {
+  DFX_HOST_CHECK((int)batches.size() == impl_->L, "GpuSplitLearner: one batch per local worker");
+  std::vector<Item> items(batches.size());
+  for (size_t l = 0; l < batches.size(); ++l) {
+    DFX_HOST_CHECK(batches[l] != nullptr, "GpuSplitLearner: null batch");
+    items[l].host = batches[l];
+  }
+  ProcessDeviceBatches(items, job_type, push_cnt, preds, nullptr);
+}
+
+void GpuSplitLearner::ProcessDeviceBatches(const std::vector<Item>& items, int job_type,
+                                           bool push_cnt, std::vector<std::vector<real_t>>* preds,
+                                           std::vector<dfx_batch>* dev_out) {
   Impl& m = *impl_;
-  DFX_HOST_CHECK((int)batches.size() == m.L, "GpuSplitLearner: one batch per local worker");
+  DFX_HOST_CHECK((int)items.size() == m.L, "GpuSplitLearner: one batch per local worker");
   DFX_HOST_CHECK(job_type == kTraining || job_type == kValidation || job_type == kPrediction,
                  "GpuSplitLearner: bad job type");
   DFX_HOST_CHECK(!preds || job_type != kTraining,
@@ -285,12 +337,20 @@ void GpuSplitLearner::ProcessBatches(const std::vector<const dmlc::RowBlock<feai
   DFX_HOST_CHECK(m.arrived == 0, "GpuSplitLearner: ProcessBatches beside ProcessBatch calls");
   if (preds) preds->resize(m.L);
   for (int l = 0; l < m.L; ++l) {
-    m.pend[l] = batches[l];
+    m.pend[l] = items[l];
     m.pend_pred[l] = preds ? &(*preds)[l] : nullptr;
   }
+  m.pend_dev = dev_out;
+  // (a failed submit leaves no item behind)
+  struct Clear {
+    Impl& m;
+    ~Clear() {
+      m.pend.assign(m.L, Item());
+      for (auto& p : m.pend_pred) p = nullptr;
+      m.pend_dev = nullptr;
+    }
+  } clear{m};
   m.Submit(job_type, push_cnt && job_type == kTraining);
-  for (auto& p : m.pend) p = nullptr;
-  for (auto& p : m.pend_pred) p = nullptr;
 }
 
 void GpuSplitLearner::Flush() {
@@ -298,8 +358,18 @@ void GpuSplitLearner::Flush() {
   std::lock_guard<std::mutex> lk(m.mu);
   if (!m.queued) return;
   DistCheck(dfx_split_store_flush(m.store), "dfx_split_store_flush");
-  for (dfx_feeder* f : m.feeders) DfxCheck(dfx_feeder_consumed(f), "dfx_feeder_consumed");
-  m.queued = false;
+  m.QueuedRan();
+}
+
+void GpuSplitLearner::Sync() {
+  Flush();
+  DistCheck(dfx_split_store_sync(impl_->store), "dfx_split_store_sync");
+}
+
+double GpuSplitLearner::TakeThrottleSeconds() {
+  double s = 0;
+  DistCheck(dfx_split_store_throttle_seconds(impl_->store, &s), "dfx_split_store_throttle_seconds");
+  return s;
 }
 
 Progress GpuSplitLearner::TakeProgress(int local) {

@@ -58,8 +58,37 @@ class GpuSplitLearner {
    * preds (optional, as above): resized to one vector per local worker */
   void ProcessBatches(const std::vector<const dmlc::RowBlock<feaid_t>*>& batches, int job_type,
                       bool push_cnt, std::vector<std::vector<real_t>>* preds = nullptr);
+  /** a local worker's batch of one step: a host row block (staged and uploaded, as
+   * ProcessBatches'), or a batch in device memory (a DeviceBatchCache's: ready by the context's
+   * input stream's order and alive until the learner is gone), or neither: an empty batch */
+  struct Item {
+    const dmlc::RowBlock<feaid_t>* host = nullptr;
+    const dfx_batch* dev = nullptr;
+  };
+  /** one step from a single caller thread, like ProcessBatches (its all-host case); host and
+   * device items may be mixed in a step.  A device item goes to the split store as it is: no
+   * staging, no copy, and no staging slot is held for it.  preds: as above, the sizes are the
+   * batches' own.
+   * dev_out (optional): resized to one dfx_batch per local worker; dev_out[l] is the device
+   * batch worker l's host block was uploaded into (a device item: itself; none: size 0), valid
+   * until the worker's next host item is staged — what GpuSGDLearner::ProcessBatch's dev_out is.
+   * A caller that records appends it to the shard's DeviceBatchCache right after the call: the
+   * cache copies on the context's input stream, which is the feeder's loader stream (the feeder
+   * installs it, dfx_feeder_create_slots), so the copy runs behind the upload and before the
+   * next upload into the same slot with no event and no host wait.
+   * The contexts are the learner's own, and a cache must go before its context: a caller
+   * first joins the learner (Sync: no queued step reads a cached batch any more), then
+   * destroys its caches, then the learner. */
+  void ProcessDeviceBatches(const std::vector<Item>& items, int job_type, bool push_cnt,
+                            std::vector<std::vector<real_t>>* preds = nullptr,
+                            std::vector<dfx_batch>* dev_out = nullptr);
   /** run the queued step (one thread, every local worker idle) */
   void Flush();
+  /** Flush, then wait for every context and stream of the split driver: nothing reads a
+   * submitted batch any more */
+  void Sync();
+  /** host seconds the split store waited on its run-ahead bound (pipelined) since the last call */
+  double TakeThrottleSeconds();
   /** sgd::Progress of worker `local` since the last call (Flush first) */
   Progress TakeProgress(int local);
   /** v summed over the processes (the thread that submits steps; a collective of every rank,

@@ -6,7 +6,7 @@
 //                   [num_jobs_per_epoch=10] [stop_rel_objv=1e-5] [stop_val_auc=1e-5]
 //                   [model_in=F] [model_out=F]
 //                   [load_epoch=-1] [has_aux=0] [task=0|2] [pred_out=F] [pred_prob=1]
-//                   [fused=1] [nthreads=8] [parse=host|device|auto] [cache=none|device]
+//                   [fused=1] [nthreads=8] [parse=host|device|auto] [cache=none|device|auto]
 //                   [cache_mb=16384] [cache_loc=0] [epoch_shuffle=0] [shuffle_seed=0]
 //                   [V_dim=..] [lr=..] [l1=..] ... (SGDUpdaterParam)
 //
@@ -34,6 +34,18 @@
 // cache.  After the recording epoch one line reports the batches and MB held and the parts not
 // cached.  With exchange=split or fused=0 it is an error (exit 2); task=2 is one pass over the
 // data, so there it is accepted and has no effect.
+//
+// cache=auto takes the device cache on every path that can replay device batches: the
+// single-GPU fused path and exchange=a2a (there it runs as cache=device does) and exchange=split
+// (GpuSplitLearner::ProcessDeviceBatches: a replayed batch goes to the split store as it is, a
+// part that did not fit is read while the other shards replay); with fused=0 it runs without a
+// cache.  One line at the start says which, "cache: device (fused)", "cache: device
+// (exchange=a2a)", "cache: device (exchange=split)", "cache: none (fused=0)" or, in the one pass
+// of a prediction run, "cache: none (task=2)"; the report line after the recording epoch is
+// cache=device's.  An exchange=split run with the cache also prints per epoch where the
+// submitting thread's time went.  cache_mb < 0 is an error (exit 2); cache_loc=1 and
+// epoch_shuffle=1 ask for cache=device literally.  cache=device keeps its contract: a path
+// without the cache is an error.
 //
 // cache_loc=1 (with cache=device, the single-GPU fused path, not task=2): the recording epoch
 // also keeps, next to every cached batch, the outputs of that batch's Localizer
@@ -84,7 +96,8 @@
 // "label\tprediction" line per row in the order it read them (the file exists even when it read
 // none), and rank 0 prints the "Prediction:" line.  A prediction step runs synchronously
 // (submit, flush, copy the predictions down); validation steps are queued like training steps.
-// cache=device exchange=a2a keeps and replays the validation batches too (lists of their own).
+// cache=device exchange=a2a and cache=auto keep and replay the validation batches too (lists of
+// their own).
 //
 // Model files are named like SGDLearner::ModelName (sgd_learner.h:65-69):
 // <prefix>[_iter-<epoch>]_part-0, in SGDUpdater::Save's format; task=2 predicts data_val with
@@ -327,9 +340,9 @@ std::string KwString(const KWArgs& kw) {
 }
 
 // What the sharded epoch needs of a store.  exchange=a2a: GpuShardedStore (KVStoreDist's
-// exchanges, dist_host.h) over device batches, with the batch cache; exchange=split: the
-// owner-computes split behind GpuSplitLearner (split_learner.h), which takes host row blocks —
-// one synchronous reference step per batch index on the concatenation of the shards' batches
+// exchanges, dist_host.h) over device batches; exchange=split: the owner-computes split behind
+// GpuSplitLearner (split_learner.h), which takes host row blocks and device batches — one
+// synchronous reference step per batch index on the concatenation of the shards' batches
 // (push_agg=sum; pipelined=1 only overlaps model-free work, so the results equal the
 // synchronous schedule).
 class ShardRunner {
@@ -354,13 +367,15 @@ class ShardRunner {
                     bool push_cnt, std::vector<std::vector<real_t>>* preds) = 0;
   /** run what is queued and apply the last push */
   virtual void Flush() = 0;
-  // the batch cache (cache=device; exchange=a2a only): a sealed list's batches of local shard
+  // the batch cache (cache=device, cache=auto): a sealed list's batches of local shard
   // l, -1 when the part has to be read; the recording pass's list brackets; the shards' sums
   virtual bool has_cache() const { return false; }
   virtual int64_t Cached(int, int64_t) { return -1; }
   virtual void BeginList(int64_t) {}
   virtual void SealList() {}
   virtual void CacheSums(std::vector<double>* cs) { cs->assign(4, 0.0); }
+  /** host seconds the store made the submitting thread wait on its run-ahead bound */
+  virtual double TakeThrottleSeconds() { return 0; }
 };
 
 class A2aRunner : public ShardRunner {
@@ -486,8 +501,21 @@ class SplitRunner : public ShardRunner {
     KWArgs kw = rest;
     kw.push_back({"pipelined", P.pipelined ? "1" : "0"});
     sl_ = rccl ? GpuSplitLearner::CreateRccl(kw) : GpuSplitLearner::CreateLoopback(P.shards, kw);
-    empty_.size = 0;
-    empty_.offset = &zero_off_;
+    // the device cache (cache=auto): each local shard's batch cache on its own context, recorded
+    // in the first epoch this run executes (task=2 is one pass: nothing to replay)
+    if (P.cache == "device" && P.task != 2)
+      for (int l = 0; l < sl_->nlocal(); ++l)
+        caches_.emplace_back(new DeviceBatchCache(sl_->shard(l), P.cache_mb << 20));
+  }
+  ~SplitRunner() override {
+    // no queued step reads a cached batch any more; the caches go before the contexts, which
+    // are the learner's
+    try {
+      sl_->Sync();
+    } catch (...) {
+    }
+    caches_.clear();
+    sl_.reset();
   }
   int nlocal() const override { return sl_->nlocal(); }
   int nranks() const override { return sl_->nranks(); }
@@ -495,23 +523,53 @@ class SplitRunner : public ShardRunner {
   dfx_ctx* ctx(int local) const override { return sl_->shard(local); }
   const char* tag() const override { return ", split"; }
   void AllReduceSum(std::vector<double>* v) override { sl_->AllReduceSum(v); }
-  void Step(const std::vector<Item>& items, int64_t, bool, int job_type, bool push_cnt,
-            std::vector<std::vector<real_t>>* preds) override {
+  void Step(const std::vector<Item>& items, int64_t list, bool record, int job_type,
+            bool push_cnt, std::vector<std::vector<real_t>>* preds) override {
     const int L = nlocal();
     std::vector<dmlc::RowBlock<feaid_t>> blk(L);
-    std::vector<const dmlc::RowBlock<feaid_t>*> ptrs(L);
+    std::vector<dfx_batch> dev(L);
+    std::vector<GpuSplitLearner::Item> it(L);
     for (int l = 0; l < L; ++l) {
-      blk[l] = items[l].host ? items[l].host->GetBlock() : empty_;
-      ptrs[l] = &blk[l];
+      if (items[l].replay >= 0) {
+        dev[l] = caches_[l]->Get(list, items[l].replay);
+        it[l].dev = &dev[l];
+      } else if (items[l].host) {
+        blk[l] = items[l].host->GetBlock();
+        it[l].host = &blk[l];
+      }  // else none: the shard gives an empty batch
     }
-    sl_->ProcessBatches(ptrs, job_type, push_cnt, preds);
+    const bool rec = record && !caches_.empty();
+    std::vector<dfx_batch> up;
+    sl_->ProcessDeviceBatches(it, job_type, push_cnt, preds, rec ? &up : nullptr);
+    // the copies run on the contexts' input streams, behind the uploads and before the staging
+    // slots are reused (as the single-GPU path's, RunEpoch)
+    for (int l = 0; rec && l < L; ++l)
+      if (items[l].host) caches_[l]->Append(up[l]);
   }
   void Flush() override { sl_->Flush(); }
+  bool has_cache() const override { return !caches_.empty(); }
+  int64_t Cached(int l, int64_t list) override { return caches_[l]->Count(list); }
+  void BeginList(int64_t list) override {
+    for (auto& c : caches_) c->Begin(list);
+  }
+  void SealList() override {
+    for (auto& c : caches_) c->Seal();
+  }
+  void CacheSums(std::vector<double>* cs) override {
+    cs->assign(4, 0.0);
+    for (auto& c : caches_) {
+      const DeviceBatchCache::Stats s = c->GetStats();
+      (*cs)[0] += (double)s.batches;
+      (*cs)[1] += (double)s.bytes;
+      (*cs)[2] += (double)s.dropped;
+      (*cs)[3] += (double)(s.sealed + s.dropped);
+    }
+  }
+  double TakeThrottleSeconds() override { return sl_->TakeThrottleSeconds(); }
 
  private:
   std::shared_ptr<GpuSplitLearner> sl_;
-  size_t zero_off_ = 0;
-  dmlc::RowBlock<feaid_t> empty_;
+  std::vector<std::unique_ptr<DeviceBatchCache>> caches_;
 };
 
 // a part's batches: training reads minibatches (sgd_learner.cc:273-280), validation and
@@ -549,8 +607,9 @@ class PartReader {
 // gives empty batches until the all-reduced "any shard still has a batch" is 0), then the
 // store is flushed and the progress summed over every shard of every rank.
 // pred_files (prediction): local shard l's rows go to pred_files[l] in the order read.
+// host_s (optional): += the host seconds inside Step and inside the per-step all-reduce.
 Progress ShardedPass(ShardRunner* run, const Param& P, int epoch, int job_type, bool record,
-                     const std::vector<FILE*>* pred_files = nullptr) {
+                     const std::vector<FILE*>* pred_files = nullptr, double* host_s = nullptr) {
   const int nlocal = run->nlocal(), nshards = run->nranks();
   const bool train = job_type == GpuSGDLearner::kTraining;
   const int nparts = P.num_jobs_per_epoch * nshards;
@@ -573,7 +632,9 @@ Progress ShardedPass(ShardRunner* run, const Param& P, int epoch, int job_type, 
         if (more[l]) more[l] = rd[l] ? rd[l]->Next() : pos[l] < n_cached[l];
         if (more[l]) any[0] += 1;
       }
+      const double ta = host_s ? Now() : 0;
       run->AllReduceSum(&any);
+      if (host_s) host_s[1] += Now() - ta;
       if (any[0] == 0) break;
       std::vector<ShardRunner::Item> items(nlocal);
       for (int l = 0; l < nlocal; ++l) {
@@ -583,7 +644,9 @@ Progress ShardedPass(ShardRunner* run, const Param& P, int epoch, int job_type, 
         else
           items[l].replay = pos[l]++;
       }
+      const double ts = host_s ? Now() : 0;
       run->Step(items, list, rec, job_type, train && epoch == 0, pred_files ? &preds : nullptr);
+      if (host_s) host_s[0] += Now() - ts;
       for (int l = 0; pred_files && l < nlocal; ++l) {  // SavePred
         if (!items[l].host) continue;
         const auto& label = items[l].host->label;
@@ -663,11 +726,20 @@ int RunSharded(const Param& P, const KWArgs& rest) {
   for (int k = kfirst; k < P.max_num_epochs; ++k) {
     const double te = Now();
     const bool record = k == kfirst;  // the first epoch this run executes records
-    const Progress tr = ShardedPass(run.get(), P, k, GpuSGDLearner::kTraining, record);
+    // exchange=split with the cache: where the submitting thread's time went
+    const bool timed = run->has_cache() && P.exchange == "split";
+    double host_s[2] = {0, 0};
+    if (timed) (void)run->TakeThrottleSeconds();
+    const Progress tr = ShardedPass(run.get(), P, k, GpuSGDLearner::kTraining, record, nullptr,
+                                    timed ? host_s : nullptr);
     const double dt = Now() - te;
     if (rank == 0)
       std::printf("Epoch[%d] Training: %s  (%.0f ex/s incl. parse+PCIe, %d shards%s, %.2f s)\n", k,
                   Text(tr).c_str(), tr.nrows / dt, nshards, run->tag(), Now() - t0);
+    if (timed && rank == 0)
+      std::printf("  split: epoch %.3f s; the host spent %.3f s in Step (of it %.3f s waiting on "
+                  "the store's run-ahead bound) and %.3f s in the per-step all-reduce\n",
+                  dt, host_s[0], run->TakeThrottleSeconds(), host_s[1]);
     Progress va;
     if (!P.data_val.empty()) {
       // (the pass above flushed: the 1-step-stale schedule's last push is applied)
@@ -795,8 +867,8 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
-  if (P.cache != "none" && P.cache != "device") {
-    std::fprintf(stderr, "cache must be none or device\n");
+  if (P.cache != "none" && P.cache != "device" && P.cache != "auto") {
+    std::fprintf(stderr, "cache must be none, device or auto\n");
     return 2;
   }
   if (P.cache_loc) {  // no silent run without the kept outputs
@@ -845,13 +917,33 @@ int main(int argc, char** argv) {
     if (!fused)
       why = "the fused path (fused=1)";
     else if (sharded && P.exchange == "split")
-      why = "exchange=a2a in a sharded run (exchange=split takes host row blocks)";
+      why = "exchange=a2a in a sharded run (exchange=split replays under cache=auto)";
     else if (P.cache_mb < 0)
       why = "cache_mb >= 0";
     if (why) {
       std::fprintf(stderr, "cache=device needs %s\n", why);
       return 2;
     }
+  }
+  if (P.cache == "auto") {  // the device cache where batches replay, and a line saying which
+    if (P.cache_mb < 0) {
+      std::fprintf(stderr, "cache=auto needs cache_mb >= 0\n");
+      return 2;
+    }
+    bool fused = true;
+    for (const auto& kv : rest)
+      if (kv.first == "fused") fused = std::stoi(kv.second) != 0;
+    const bool dev = (sharded || fused) && P.task != 2;  // (task=2 is one pass: nothing to replay)
+    const std::string why = !sharded && !fused ? "fused=0"
+                            : P.task == 2      ? "task=2"
+                            : sharded          ? "exchange=" + P.exchange
+                                               : "fused";
+    const char* rk = std::getenv("RANK");
+    if (!sharded || !rk || std::atoi(rk) == 0) {
+      std::printf("cache: %s (%s)\n", dev ? "device" : "none", why.c_str());
+      std::fflush(stdout);
+    }
+    P.cache = dev ? "device" : "none";
   }
   if (sharded && P.task == 2 && (P.model_in.empty() || P.data_val.empty())) {
     std::fprintf(stderr, "prediction needs model_in and data_val\n");  // before any context
