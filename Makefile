@@ -38,7 +38,7 @@ DISTLIB = difacto_amd/libdfx_dist.so
 
 all: $(LIB) $(DISTLIB) oracle $(HOSTBIN) $(TRAINBIN) $(READERBIN) $(GENBIN) $(CONVBIN) $(RBENCH) \
   $(TPBIN) $(LSBIN) $(SEBIN) $(SDBIN) build/expf_check build/strtof_check build/gen_libsvm build/locbench \
-  build/reshuffle_check
+  build/reshuffle_check build/fmtg_check
 
 $(RBENCH): difacto_amd/host/reader.cc tools/reader_bench.cc difacto_amd/host/reader.h $(CITYHDR)
 	@mkdir -p build
@@ -85,6 +85,12 @@ build/strtof_check: tools/strtof_check.cc $(CSRC)/strtof.h
 build/reshuffle_check: tools/reshuffle_check.cc $(CSRC)/reshuffle.h
 	@mkdir -p build
 	g++ -std=c++14 -O2 -Wall -o $@ $<
+
+# test infrastructure: csrc/fmtg.h (the device prediction writer's rows) against the host's
+# snprintf("%g") and the driver's probability expression; also writes the GPU tests' expected text
+build/fmtg_check: tools/fmtg_check.cc $(CSRC)/fmtg.h $(CSRC)/expf.h
+	@mkdir -p build
+	g++ -std=c++17 -O2 -Wall -ffp-contract=off -o $@ $<
 
 build/gen_libsvm: tools/gen_libsvm.cc
 	@mkdir -p build

@@ -50,6 +50,12 @@ class HostBatch(ctypes.Structure):
                 ("max_rows", c_i64), ("max_nnz", c_i64)]
 
 
+class PredTextOut(ctypes.Structure):
+    """dfx_predtext_out: what dfx_predtext_take hands out of a slot (pinned host memory)"""
+    _fields_ = [("text", vp), ("bytes", c_i64), ("rows", c_i64), ("flagged", c_i64),
+                ("first_flagged", c_i64), ("label", vp), ("pred", vp)]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "dfx_last_error": (ctypes.c_char_p, []),
@@ -150,6 +156,11 @@ _SIGS = {
                                           ctypes.POINTER(ctypes.c_int)]),
     "dfx_reshuffle_consumed": (ctypes.c_int, [vp]),
     "dfx_reshuffle_stats": (ctypes.c_int, [vp, i64p]),
+    "dfx_format_pred": (ctypes.c_int, [vp, vp, vp, c_i64, ctypes.c_int, vp, c_i64, vp, vp]),
+    "dfx_predtext_create": (ctypes.c_int, [vp, c_i64, ctypes.POINTER(vp)]),
+    "dfx_predtext_submit": (ctypes.c_int, [vp, ctypes.c_int, vp, vp, c_i64, ctypes.c_int]),
+    "dfx_predtext_take": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(PredTextOut)]),
+    "dfx_predtext_destroy": (ctypes.c_int, [vp]),
     "dfx_dist_record_floats": (ctypes.c_int, [vp]),
     "dfx_dist_localize": (ctypes.c_int, [vp, ctypes.POINTER(Batch), c_u64, ctypes.c_int,
                                          ctypes.c_int, vp, vp]),

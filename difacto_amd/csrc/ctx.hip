@@ -378,7 +378,7 @@ int dfx_ctx_destroy(dfx_ctx* ctx) {
   release_ws(c->aws_alt);
   release_ws(c->uws);
   for (DevBuf* b : {&c->tp_tiles, &c->tp_cells, &c->tp_lines, &c->tp_pair, &c->tp_tot,
-                    &c->tp_stat, &c->tg_len, &c->tg_tot})
+                    &c->tp_stat, &c->tg_len, &c->tg_tot, &c->pt_rec, &c->pt_tot})
     b->release();
   for (auto h : c->dist_host)
     if (h) (void)hipHostFree(h);

@@ -6,8 +6,15 @@
 // the compiler contracts its multiply-adds, kd and r included).  tools/expf_check.hip compares
 // it with the host's expf on every float: identical on all 2^32 inputs.
 #pragma once
-#include <hip/hip_runtime.h>
 #include <stdint.h>
+
+// (plain g++ reads this too: tools/fmtg_check.cc through csrc/fmtg.h)
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define DFX_EXPF_HD __host__ __device__ inline
+#else
+#define DFX_EXPF_HD inline
+#endif
 
 namespace dfx {
 
@@ -24,7 +31,7 @@ namespace dfx {
 
 // tab(i): the table entry i (constant memory on the device, an array on the host)
 template <typename Tab>
-__host__ __device__ inline float expf_glibc(float x, const Tab& tab) {
+DFX_EXPF_HD float expf_glibc(float x, const Tab& tab) {
   constexpr double kInvLn2N = 0x1.71547652b82fep+0 * 32, kShift = 0x1.8p+52;
   constexpr double kC0 = 0x1.c6af84b912394p-5 / 32 / 32 / 32, kC1 = 0x1.ebfce50fac4f3p-3 / 32 / 32,
                    kC2 = 0x1.62e42ff0c52d6p-1 / 32;

@@ -223,6 +223,9 @@ struct Context {
   // scratch of the text parser and the row gather (textparse.hip), used in the input stream's
   // order: tile tuples, per-line cell table, per-line arrays, scan partials, counters
   DevBuf tp_tiles, tp_cells, tp_lines, tp_pair, tp_tot, tp_stat, tg_len, tg_tot;
+  // scratch of the prediction formatter (predtext.hip), used in the context stream's order: a
+  // 32-byte record per row, the tile totals
+  DevBuf pt_rec, pt_tot;
   Workspace bws[kSlots];  // [0], [1]: also the fused step's Localizer parities
   DevState* bds[kSlots] = {};
   Workspace aws;

@@ -1,6 +1,8 @@
 // gpu_adapters.cc — see gpu_adapters.h.
 #include "gpu_adapters.h"
 
+#include <chrono>
+#include <cmath>
 #include <cstdlib>
 
 #include <iterator>
@@ -426,7 +428,7 @@ GpuSGDLearner::~GpuSGDLearner() {
 
 void GpuSGDLearner::ProcessBatch(const dmlc::RowBlock<feaid_t>& batch, int job_type,
                                  bool push_cnt, std::vector<real_t>* pred_out,
-                                 dfx_batch* dev_batch) {
+                                 dfx_batch* dev_batch, const float** dev_pred) {
   push_cnt = push_cnt && job_type == kTraining && V_dim_ > 0;
   if (fused_) {
     const int64_t B = (int64_t)batch.size, nnz = B ? (int64_t)batch.offset[B] : 0;
@@ -454,7 +456,7 @@ void GpuSGDLearner::ProcessBatch(const dmlc::RowBlock<feaid_t>& batch, int job_t
              "dfx_feeder_submit");
     if (dev_batch) *dev_batch = b;
     float* dp = nullptr;
-    if (pred_out) {
+    if (pred_out || dev_pred) {
       if (!dpred_) dpred_.reset(new DevArray<float>(c));
       dpred_->ensure(B);
       dp = dpred_->get();
@@ -463,6 +465,7 @@ void GpuSGDLearner::ProcessBatch(const dmlc::RowBlock<feaid_t>& batch, int job_t
                             std::numeric_limits<uint64_t>::max(), dp),
              "dfx_train_step");
     DfxCheck(dfx_feeder_consumed(feeder_), "dfx_feeder_consumed");
+    if (dev_pred) *dev_pred = dp;
     if (pred_out) {
       pred_out->resize(B);
       dpred_->download(pred_out->data(), B);
@@ -509,12 +512,13 @@ void GpuSGDLearner::ProcessBatch(const dmlc::RowBlock<feaid_t>& batch, int job_t
 }
 
 void GpuSGDLearner::ProcessDeviceBatch(const dfx_batch& batch, int job_type, bool push_cnt,
-                                       std::vector<real_t>* pred_out, const dfx_loc* loc) {
+                                       std::vector<real_t>* pred_out, const dfx_loc* loc,
+                                       const float** dev_pred) {
   DFX_HOST_CHECK(fused_, "device batches run the fused path (fused=1)");
   push_cnt = push_cnt && job_type == kTraining && V_dim_ > 0;
   dfx_ctx* c = updater_->context()->h();
   float* dp = nullptr;
-  if (pred_out) {
+  if (pred_out || dev_pred) {
     if (!dpred_) dpred_.reset(new DevArray<float>(c));
     dpred_->ensure((size_t)batch.size);
     dp = dpred_->get();
@@ -527,6 +531,7 @@ void GpuSGDLearner::ProcessDeviceBatch(const dfx_batch& batch, int job_type, boo
     DfxCheck(dfx_train_step(c, &batch, job_type, push_cnt ? 1 : 0,
                             std::numeric_limits<uint64_t>::max(), dp),
              "dfx_train_step");
+  if (dev_pred) *dev_pred = dp;
   if (pred_out) {
     pred_out->resize((size_t)batch.size);
     dpred_->download(pred_out->data(), (size_t)batch.size);
@@ -544,6 +549,61 @@ Progress GpuSGDLearner::TakeProgress() {
     out.auc += p.auc;
   }
   return out;
+}
+
+// ---- prediction files ----------------------------------------------------------------------
+void WritePredRows(FILE* f, const real_t* label, const real_t* pred, size_t n, bool pred_prob) {
+  for (size_t i = 0; i < n; ++i)  // SavePred
+    std::fprintf(f, "%g\t%g\n", label[i],
+                 pred_prob ? 1.0 / (1.0 + std::exp(-pred[i])) : (double)pred[i]);
+}
+
+DevicePredWriter::DevicePredWriter(dfx_ctx* ctx, FILE* f, bool pred_prob)
+    : f_(f), pred_prob_(pred_prob) {
+  DfxCheck(dfx_predtext_create(ctx, 0, &h_), "dfx_predtext_create");
+}
+
+DevicePredWriter::~DevicePredWriter() {
+  if (!h_) return;
+  try {
+    Finish();
+  } catch (...) {
+  }
+  dfx_predtext_destroy(h_);
+}
+
+void DevicePredWriter::Submit(const float* label_dev, const float* pred_dev, int64_t n) {
+  const int slot = next_;
+  DfxCheck(dfx_predtext_submit(h_, slot, label_dev, pred_dev, n, pred_prob_ ? 1 : 0),
+           "dfx_predtext_submit");
+  pending_[slot] = true;
+  next_ ^= 1;
+  if (pending_[next_]) Drain(next_);  // the batch before this one, while this one is formatted
+}
+
+void DevicePredWriter::Finish() {
+  // in the order submitted: next_ is the older slot
+  for (int k = 0; k < 2; ++k) {
+    const int slot = next_ ^ k;
+    if (pending_[slot]) Drain(slot);
+  }
+}
+
+void DevicePredWriter::Drain(int slot) {
+  dfx_predtext_out o;
+  const auto t0 = std::chrono::steady_clock::now();
+  DfxCheck(dfx_predtext_take(h_, slot, &o), "dfx_predtext_take");
+  stats_.wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  pending_[slot] = false;
+  if (o.flagged == 0) {
+    if (o.bytes) DFX_HOST_CHECK(std::fwrite(o.text, 1, (size_t)o.bytes, f_) == (size_t)o.bytes,
+                                "DevicePredWriter: short write");
+  } else {
+    WritePredRows(f_, o.label, o.pred, (size_t)o.rows, pred_prob_);
+    ++stats_.host_batches;
+  }
+  stats_.rows += o.rows;
+  ++stats_.batches;
 }
 
 // ---- device batch cache --------------------------------------------------------------------

@@ -18,6 +18,7 @@
 #ifndef DIFACTO_AMD_HOST_GPU_ADAPTERS_H_
 #define DIFACTO_AMD_HOST_GPU_ADAPTERS_H_
 
+#include <cstdio>
 #include <limits>
 
 #include "../../include/difacto_amd.h"
@@ -182,15 +183,21 @@ class GpuSGDLearner {
    * dev_batch (optional, fused path): receives the device batch the feeder uploaded; its
    * buffers are the feeder's, reused by the upload after next, and anything queued on the
    * context's input stream before the next ProcessBatch (a DeviceBatchCache's copies) reads
-   * them complete. */
+   * them complete.
+   * dev_pred (optional, fused path): receives the device array the step writes the batch's
+   * predictions to, in the context stream's order and with no copy down (a DevicePredWriter
+   * formats them there); valid until the next Process call. */
   void ProcessBatch(const dmlc::RowBlock<feaid_t>& batch, int job_type, bool push_cnt,
-                    std::vector<real_t>* pred = nullptr, dfx_batch* dev_batch = nullptr);
+                    std::vector<real_t>* pred = nullptr, dfx_batch* dev_batch = nullptr,
+                    const float** dev_pred = nullptr);
   /** the fused path for a batch already on the device (DeviceBatchReader, device_reader.h):
    * dfx_train_step without the pinned copy; the batch's producer is the context's input
    * stream.  pred (optional) receives the predictions (joins the device).  loc (optional): the
-   * batch's Localizer outputs from a DeviceBatchCache (dfx_train_step_loc: no Localizer runs). */
+   * batch's Localizer outputs from a DeviceBatchCache (dfx_train_step_loc: no Localizer runs).
+   * dev_pred (optional): as ProcessBatch's. */
   void ProcessDeviceBatch(const dfx_batch& batch, int job_type, bool push_cnt,
-                          std::vector<real_t>* pred = nullptr, const dfx_loc* loc = nullptr);
+                          std::vector<real_t>* pred = nullptr, const dfx_loc* loc = nullptr,
+                          const float** dev_pred = nullptr);
   /** the learner's device context (the fused path's; null when a Store was given) */
   dfx_ctx* context() const { return updater_ ? updater_->context()->h() : nullptr; }
   /** sgd::Progress accumulated since the last call (joins the device) */
@@ -271,6 +278,43 @@ class DeviceReshuffler {
 
  private:
   dfx_reshuffle* h_ = nullptr;
+};
+
+/** SGDLearner::SavePred's rows (sgd_learner.h:72-83), "label\tvalue\n" with value the
+ * probability 1 / (1 + exp(-pred)) under pred_prob: the host writer of a prediction file */
+void WritePredRows(FILE* f, const real_t* label, const real_t* pred, size_t n, bool pred_prob);
+
+/** the device writer of a prediction file (pred_write=device): the same bytes as WritePredRows,
+ * formatted on the device (dfx_predtext_*, include/difacto_amd.h) and written to f as whole
+ * batches, batch t while the step of batch t + 1 runs.  A batch with a row the device does not
+ * format (csrc/fmtg.h: a field outside 1e-12 <= |x| < 1e12 that is not 0) is written whole by
+ * WritePredRows from the slot's copies of its labels and predictions, in its place. */
+class DevicePredWriter {
+ public:
+  DevicePredWriter(dfx_ctx* ctx, FILE* f, bool pred_prob);
+  ~DevicePredWriter();
+  DevicePredWriter(const DevicePredWriter&) = delete;
+  DevicePredWriter& operator=(const DevicePredWriter&) = delete;
+  /** batch t: n rows of device labels and predictions, read in the context stream's order,
+   * behind the step that wrote pred_dev; both arrays are free again when the call returns or,
+   * at the latest, when Submit(t + 1) or Finish returns.  Writes batch t - 1 to the file. */
+  void Submit(const float* label_dev, const float* pred_dev, int64_t n);
+  /** writes what is still in flight */
+  void Finish();
+  struct Stats {
+    int64_t rows = 0, batches = 0, host_batches = 0;  // host_batches: written by WritePredRows
+    double wait_s = 0;                                // the host waited for text
+  };
+  Stats GetStats() const { return stats_; }
+
+ private:
+  void Drain(int slot);
+  dfx_predtext* h_ = nullptr;
+  FILE* f_;
+  bool pred_prob_;
+  int next_ = 0;
+  bool pending_[2] = {false, false};
+  Stats stats_;
 };
 
 /** a libsvm reader ("label idx:val ..."): the thin CSR producer the path's caller uses */

@@ -40,6 +40,7 @@ struct GpuSplitLearner::Impl {
   std::vector<int> pend_job, pend_cnt;
   std::vector<std::vector<real_t>*> pend_pred;  // where a worker wants its predictions
   std::vector<dfx_batch>* pend_dev = nullptr;   // where the caller wants the device batches
+  std::vector<const float*>* pend_dpred = nullptr;  // ... and the predictions' device arrays
   std::vector<std::unique_ptr<DevArray<float>>> dpred;  // their device buffers
   // the queued (pipelined) step's batch of worker l sits in its feeder's newest slot: a device
   // item or none holds no slot, and the learner owes it nothing
@@ -129,12 +130,13 @@ struct GpuSplitLearner::Impl {
     if (pend_dev) *pend_dev = b;
     bool want_pred = false;
     for (const auto* p : pend_pred) want_pred = want_pred || p != nullptr;
+    want_pred = want_pred || pend_dpred != nullptr;
     std::vector<float*> dp(L, nullptr);
     if (want_pred) {
       if (dpred.empty())
         for (int l = 0; l < L; ++l) dpred.emplace_back(new DevArray<float>(ctxs[l]));
       for (int l = 0; l < L; ++l) {
-        if (!pend_pred[l]) continue;
+        if (!pend_pred[l] && !pend_dpred) continue;
         dpred[l]->ensure((size_t)b[l].size);
         dp[l] = dpred[l]->get();
       }
@@ -164,6 +166,7 @@ struct GpuSplitLearner::Impl {
       DistCheck(dfx_split_store_flush(store), "dfx_split_store_flush");
       QueuedRan();
     }
+    if (pend_dpred) pend_dpred->assign(dp.begin(), dp.end());
     for (int l = 0; l < L; ++l) {
       if (!pend_pred[l]) continue;
       pend_pred[l]->resize((size_t)b[l].size);
@@ -326,12 +329,13 @@ void GpuSplitLearner::ProcessBatches(const std::vector<const dmlc::RowBlock<feai
 
 void GpuSplitLearner::ProcessDeviceBatches(const std::vector<Item>& items, int job_type,
                                            bool push_cnt, std::vector<std::vector<real_t>>* preds,
-                                           std::vector<dfx_batch>* dev_out) {
+                                           std::vector<dfx_batch>* dev_out,
+                                           std::vector<const float*>* dev_preds) {
   Impl& m = *impl_;
   DFX_HOST_CHECK((int)items.size() == m.L, "GpuSplitLearner: one batch per local worker");
   DFX_HOST_CHECK(job_type == kTraining || job_type == kValidation || job_type == kPrediction,
                  "GpuSplitLearner: bad job type");
-  DFX_HOST_CHECK(!preds || job_type != kTraining,
+  DFX_HOST_CHECK((!preds && !dev_preds) || job_type != kTraining,
                  "GpuSplitLearner: predictions are for validation and prediction jobs");
   std::lock_guard<std::mutex> lk(m.mu);
   DFX_HOST_CHECK(m.arrived == 0, "GpuSplitLearner: ProcessBatches beside ProcessBatch calls");
@@ -341,6 +345,7 @@ void GpuSplitLearner::ProcessDeviceBatches(const std::vector<Item>& items, int j
     m.pend_pred[l] = preds ? &(*preds)[l] : nullptr;
   }
   m.pend_dev = dev_out;
+  m.pend_dpred = dev_preds;
   // (a failed submit leaves no item behind)
   struct Clear {
     Impl& m;
@@ -348,6 +353,7 @@ void GpuSplitLearner::ProcessDeviceBatches(const std::vector<Item>& items, int j
       m.pend.assign(m.L, Item());
       for (auto& p : m.pend_pred) p = nullptr;
       m.pend_dev = nullptr;
+      m.pend_dpred = nullptr;
     }
   } clear{m};
   m.Submit(job_type, push_cnt && job_type == kTraining);

@@ -78,10 +78,15 @@ class GpuSplitLearner {
    * next upload into the same slot with no event and no host wait.
    * The contexts are the learner's own, and a cache must go before its context: a caller
    * first joins the learner (Sync: no queued step reads a cached batch any more), then
-   * destroys its caches, then the learner. */
+   * destroys its caches, then the learner.
+   * dev_preds (optional, evaluation jobs): resized to one pointer per local worker; the step
+   * runs before the call returns as with preds, and dev_preds[l] is the device array holding
+   * worker l's predictions (dev_out[l].size of them) in its context stream's order, with no copy
+   * down; valid until the next step.  A DevicePredWriter formats them there. */
   void ProcessDeviceBatches(const std::vector<Item>& items, int job_type, bool push_cnt,
                             std::vector<std::vector<real_t>>* preds = nullptr,
-                            std::vector<dfx_batch>* dev_out = nullptr);
+                            std::vector<dfx_batch>* dev_out = nullptr,
+                            std::vector<const float*>* dev_preds = nullptr);
   /** run the queued step (one thread, every local worker idle) */
   void Flush();
   /** Flush, then wait for every context and stream of the split driver: nothing reads a

@@ -8,6 +8,7 @@
 //                   [load_epoch=-1] [has_aux=0] [task=0|2] [pred_out=F] [pred_prob=1]
 //                   [fused=1] [nthreads=8] [parse=host|device|auto] [cache=none|device|auto]
 //                   [cache_mb=16384] [cache_loc=0] [epoch_shuffle=0] [shuffle_seed=0]
+//                   [pred_write=host|device]
 //                   [V_dim=..] [lr=..] [l1=..] ... (SGDUpdaterParam)
 //
 // parse=device (data_format=criteo|criteo_test, the single-GPU fused path: training, data_val
@@ -74,6 +75,20 @@
 // waited for the batches' sizes (once per part).  Without cache=device, with cache_loc=1 (new
 // batches have no kept Localizer outputs), fused=0, task=2 or in a sharded run it is an error
 // (exit 2).  Default 0: the run as without it.
+//
+// pred_write=device (task=2 with pred_out; the single-GPU fused path with either parse, and the
+// sharded runs with both exchanges): every <pred_out>_part-<rank> is written from text the
+// device formatted (DevicePredWriter, gpu_adapters.h; dfx_predtext_*; csrc/fmtg.h restates
+// glibc's "%g" and the probability expression, bit for bit) instead of the host's per-row
+// fprintf: the predictions stay on the device, a batch's text comes down in one copy and is
+// written with one fwrite while the next step runs.  The files are the host writer's byte for
+// byte: a batch holding a row the device does not format (a field that is not 0 and outside
+// 1e-12 <= |x| < 1e12: a non-finite prediction, a probability below 1e-14) is written whole by
+// the host loop (WritePredRows) in its place, and the number of such batches is printed when
+// it is not zero.  One line after "Prediction:" gives the rows, the pass's seconds and the
+// seconds the host waited for text.  With fused=0, or a value other than host or device, it is
+// an error (exit 2, before any context exists); without task=2 it is accepted and does
+// nothing.  Default host: the run as without it.
 //
 // Sharded store (KVStoreDist over GPUs, dist_host.h): `shards=N` holds N shards on this GPU
 // (loopback exchange, for tests); `shards=-1` or a launch with WORLD_SIZE > 1 (RANK / LOCAL_RANK as
@@ -146,6 +161,7 @@ struct Param {
   bool cache_loc = false;      // the Localizer's outputs kept with the cached batches too
   bool epoch_shuffle = false;  // replayed training parts are reshuffled on the device per epoch
   uint64_t shuffle_seed = 0;   // ... keyed by (shuffle_seed, epoch, list)
+  std::string pred_write = "host";  // device: prediction rows formatted on the GPU
 };
 
 // sgd_learner.h:65-69
@@ -171,6 +187,17 @@ std::string Text(const Progress& p) {
   return buf;
 }
 
+// pred_write=device, after the "Prediction:" line: what the device writer did (a sharded run:
+// this process's shards)
+void PrintPredWriteLine(const DevicePredWriter::Stats& st, double pass_s) {
+  std::printf("pred_write=device: %lld rows, pass %.3f s, the host waited %.3f s for text\n",
+              (long long)st.rows, pass_s, st.wait_s);
+  if (st.host_batches)
+    std::printf("pred_write=device: %lld batch%s written by the host (a row outside the device "
+                "formatter's domain)\n",
+                (long long)st.host_batches, st.host_batches == 1 ? "" : "es");
+}
+
 // the batch cache's list of a part: one per (job kind, part)
 int64_t CacheList(const Param& P, bool train, int part) {
   return (int64_t)(train ? 0 : 1) * P.num_jobs_per_epoch + part;
@@ -190,7 +217,7 @@ Progress RunEpoch(GpuSGDLearner* learner, const Param& P, int epoch, int job_typ
                   DeviceBatchReader::Times* times = nullptr, double* step_s = nullptr,
                   DeviceBatchCache* cache = nullptr, bool record = false,
                   std::vector<std::unique_ptr<DeviceReshuffler>>* resh = nullptr,
-                  double* shuffle_wait = nullptr) {
+                  double* shuffle_wait = nullptr, DevicePredWriter* dev_writer = nullptr) {
   Progress prog;
   std::vector<real_t> pred;
   const bool train = job_type == GpuSGDLearner::kTraining;
@@ -240,15 +267,17 @@ Progress RunEpoch(GpuSGDLearner* learner, const Param& P, int epoch, int job_typ
         const dfx_batch& b = reader.Value();
         if (rec) cache->Append(b);
         const double ts = Now();
+        const float* dpred = nullptr;
         learner->ProcessDeviceBatch(b, job_type, train && epoch == 0,
-                                    pred_file ? &pred : nullptr);
+                                    pred_file && !dev_writer ? &pred : nullptr, nullptr,
+                                    dev_writer ? &dpred : nullptr);
+        // (before Consumed: the ring entry's labels are read behind the step)
+        if (dev_writer) dev_writer->Submit(b.label, dpred, b.size);
         reader.Consumed();
         if (step_s) step_s[0] += Now() - ts;
         if (rec_loc) cache->AppendLoc();
-        const float* label = reader.HostLabels();
-        for (size_t i = 0; pred_file && i < pred.size(); ++i)  // SavePred
-          std::fprintf(pred_file, "%g\t%g\n", label[i],
-                       P.pred_prob ? 1.0 / (1.0 + std::exp(-pred[i])) : (double)pred[i]);
+        if (pred_file && !dev_writer)
+          WritePredRows(pred_file, reader.HostLabels(), pred.data(), pred.size(), P.pred_prob);
       }
       fallback += reader.FallbackChunks();
       if (times) {
@@ -276,13 +305,17 @@ Progress RunEpoch(GpuSGDLearner* learner, const Param& P, int epoch, int job_typ
         const auto& v = reader.Value();
         if (v.Size() == 0) continue;
         dfx_batch db;
-        learner->ProcessBatch(v.GetBlock(), job_type, false, pred_file ? &pred : nullptr,
-                              rec ? &db : nullptr);
+        const float* dpred = nullptr;
+        learner->ProcessBatch(v.GetBlock(), job_type, false,
+                              pred_file && !dev_writer ? &pred : nullptr,
+                              rec || dev_writer ? &db : nullptr, dev_writer ? &dpred : nullptr);
         if (rec) cache->Append(db);
         if (rec_loc) cache->AppendLoc();
-        for (size_t i = 0; pred_file && i < pred.size(); ++i)  // SavePred
-          std::fprintf(pred_file, "%g\t%g\n", v.label[i],
-                       P.pred_prob ? 1.0 / (1.0 + std::exp(-pred[i])) : (double)pred[i]);
+        // (the feeder's slot of this batch is uploaded into again two batches on; the writer is
+        // done reading a batch when the next Submit returns)
+        if (dev_writer) dev_writer->Submit(db.label, dpred, db.size);
+        if (pred_file && !dev_writer)
+          WritePredRows(pred_file, v.label.data(), pred.data(), pred.size(), P.pred_prob);
       }
     }
     if (rec) cache->Seal();
@@ -362,9 +395,12 @@ class ShardRunner {
   virtual void AllReduceSum(std::vector<double>* v) = 0;
   /** one step of every local shard.  record: the host blocks are also appended to `list` of
    * the shards' caches.  preds (evaluation jobs): the step runs before the call returns and
-   * preds[l] holds local shard l's predictions; without it the step may only be queued */
+   * preds[l] holds local shard l's predictions; without it the step may only be queued.
+   * writers (with preds, pred_write=device): nothing comes down; local shard l's predictions
+   * and device labels go to writers[l] instead and preds is left alone */
   virtual void Step(const std::vector<Item>& items, int64_t list, bool record, int job_type,
-                    bool push_cnt, std::vector<std::vector<real_t>>* preds) = 0;
+                    bool push_cnt, std::vector<std::vector<real_t>>* preds,
+                    std::vector<std::unique_ptr<DevicePredWriter>>* writers = nullptr) = 0;
   /** run what is queued and apply the last push */
   virtual void Flush() = 0;
   // the batch cache (cache=device, cache=auto): a sealed list's batches of local shard
@@ -427,7 +463,8 @@ class A2aRunner : public ShardRunner {
   const char* tag() const override { return ""; }
   void AllReduceSum(std::vector<double>* v) override { ex_->AllReduceSum(v); }
   void Step(const std::vector<Item>& items, int64_t list, bool record, int job_type,
-            bool push_cnt, std::vector<std::vector<real_t>>* preds) override {
+            bool push_cnt, std::vector<std::vector<real_t>>* preds,
+            std::vector<std::unique_ptr<DevicePredWriter>>* writers) override {
     const int L = nlocal();
     std::vector<dfx_batch> bs(L);
     for (int l = 0; l < L; ++l) {
@@ -456,6 +493,11 @@ class A2aRunner : public ShardRunner {
     }
     store_->Submit(bs, job_type, push_cnt, dp);
     store_->Flush();
+    if (writers) {  // (a DevBatch is uploaded into again three steps on)
+      for (int l = 0; l < L; ++l)
+        if (bs[l].size) (*writers)[l]->Submit(bs[l].label, dp[l], bs[l].size);
+      return;
+    }
     preds->resize(L);
     for (int l = 0; l < L; ++l) {
       (*preds)[l].resize((size_t)bs[l].size);
@@ -524,7 +566,8 @@ class SplitRunner : public ShardRunner {
   const char* tag() const override { return ", split"; }
   void AllReduceSum(std::vector<double>* v) override { sl_->AllReduceSum(v); }
   void Step(const std::vector<Item>& items, int64_t list, bool record, int job_type,
-            bool push_cnt, std::vector<std::vector<real_t>>* preds) override {
+            bool push_cnt, std::vector<std::vector<real_t>>* preds,
+            std::vector<std::unique_ptr<DevicePredWriter>>* writers) override {
     const int L = nlocal();
     std::vector<dmlc::RowBlock<feaid_t>> blk(L);
     std::vector<dfx_batch> dev(L);
@@ -540,6 +583,13 @@ class SplitRunner : public ShardRunner {
     }
     const bool rec = record && !caches_.empty();
     std::vector<dfx_batch> up;
+    if (preds && writers) {  // (a staging slot is uploaded into again three steps on)
+      std::vector<const float*> dp;
+      sl_->ProcessDeviceBatches(it, job_type, push_cnt, nullptr, &up, &dp);
+      for (int l = 0; l < L; ++l)
+        if (up[l].size) (*writers)[l]->Submit(up[l].label, dp[l], up[l].size);
+      return;
+    }
     sl_->ProcessDeviceBatches(it, job_type, push_cnt, preds, rec ? &up : nullptr);
     // the copies run on the contexts' input streams, behind the uploads and before the staging
     // slots are reused (as the single-GPU path's, RunEpoch)
@@ -609,7 +659,8 @@ class PartReader {
 // pred_files (prediction): local shard l's rows go to pred_files[l] in the order read.
 // host_s (optional): += the host seconds inside Step and inside the per-step all-reduce.
 Progress ShardedPass(ShardRunner* run, const Param& P, int epoch, int job_type, bool record,
-                     const std::vector<FILE*>* pred_files = nullptr, double* host_s = nullptr) {
+                     const std::vector<FILE*>* pred_files = nullptr, double* host_s = nullptr,
+                     std::vector<std::unique_ptr<DevicePredWriter>>* writers = nullptr) {
   const int nlocal = run->nlocal(), nshards = run->nranks();
   const bool train = job_type == GpuSGDLearner::kTraining;
   const int nparts = P.num_jobs_per_epoch * nshards;
@@ -645,19 +696,20 @@ Progress ShardedPass(ShardRunner* run, const Param& P, int epoch, int job_type, 
           items[l].replay = pos[l]++;
       }
       const double ts = host_s ? Now() : 0;
-      run->Step(items, list, rec, job_type, train && epoch == 0, pred_files ? &preds : nullptr);
+      run->Step(items, list, rec, job_type, train && epoch == 0, pred_files ? &preds : nullptr,
+                pred_files ? writers : nullptr);
       if (host_s) host_s[0] += Now() - ts;
-      for (int l = 0; pred_files && l < nlocal; ++l) {  // SavePred
+      for (int l = 0; pred_files && !writers && l < nlocal; ++l) {
         if (!items[l].host) continue;
-        const auto& label = items[l].host->label;
-        for (size_t i = 0; i < preds[l].size(); ++i)
-          std::fprintf((*pred_files)[l], "%g\t%g\n", label[i],
-                       P.pred_prob ? 1.0 / (1.0 + std::exp(-preds[l][i])) : (double)preds[l][i]);
+        WritePredRows((*pred_files)[l], items[l].host->label.data(), preds[l].data(),
+                      preds[l].size(), P.pred_prob);
       }
     }
     if (rec) run->SealList();
   }
   run->Flush();
+  if (writers)
+    for (auto& w : *writers) w->Finish();
   std::vector<double> pr(3, 0.0);
   for (int l = 0; l < nlocal; ++l) {
     dfx_progress p;
@@ -715,10 +767,30 @@ int RunSharded(const Param& P, const KWArgs& rest) {
         }
       }
     }
+    // pred_write=device: one writer per local shard, on the shard's context (they go before
+    // the runner, which owns the contexts)
+    std::vector<std::unique_ptr<DevicePredWriter>> writers;
+    if (P.pred_write == "device")
+      for (size_t l = 0; l < files.size(); ++l)
+        writers.emplace_back(new DevicePredWriter(run->ctx((int)l), files[l], P.pred_prob));
+    const double tp = Now();
     const Progress pr = ShardedPass(run.get(), P, kfirst, GpuSGDLearner::kPrediction, false,
-                                    files.empty() ? nullptr : &files);
+                                    files.empty() ? nullptr : &files, nullptr,
+                                    writers.empty() ? nullptr : &writers);
+    const double pass_s = Now() - tp;
     for (FILE* f : files) std::fclose(f);
     if (rank == 0) std::printf("Prediction: %s\n", Text(pr).c_str());
+    if (P.pred_write == "device") {
+      DevicePredWriter::Stats sum;
+      for (auto& w : writers) {
+        const DevicePredWriter::Stats st = w->GetStats();
+        sum.rows += st.rows;
+        sum.host_batches += st.host_batches;
+        sum.wait_s += st.wait_s;
+      }
+      PrintPredWriteLine(sum, pass_s);
+    }
+    writers.clear();
     return 0;
   }
   const double t0 = Now();
@@ -818,6 +890,7 @@ int main(int argc, char** argv) {
     else if (k == "cache_loc") P.cache_loc = std::stoi(v) != 0;
     else if (k == "epoch_shuffle") P.epoch_shuffle = std::stoi(v) != 0;
     else if (k == "shuffle_seed") P.shuffle_seed = std::stoull(v);
+    else if (k == "pred_write") P.pred_write = v;
     else {
       fused_given = fused_given || k == "fused";
       rest.push_back({k, v});
@@ -945,6 +1018,20 @@ int main(int argc, char** argv) {
     }
     P.cache = dev ? "device" : "none";
   }
+  if (P.pred_write != "host" && P.pred_write != "device") {
+    std::fprintf(stderr, "pred_write must be host or device\n");
+    return 2;
+  }
+  if (P.pred_write == "device") {  // no silent fall-back to the host writer
+    bool fused = true;
+    for (const auto& kv : rest)
+      if (kv.first == "fused") fused = std::stoi(kv.second) != 0;
+    if (!fused) {
+      std::fprintf(stderr, "pred_write=device needs the fused path (fused=1): the interface "
+                           "path keeps its predictions on the host\n");
+      return 2;
+    }
+  }
   if (sharded && P.task == 2 && (P.model_in.empty() || P.data_val.empty())) {
     std::fprintf(stderr, "prediction needs model_in and data_val\n");  // before any context
     return 2;
@@ -982,9 +1069,19 @@ int main(int argc, char** argv) {
         return 1;
       }
     }
-    const Progress pr = RunEpoch(&learner, P, k0, GpuSGDLearner::kPrediction, pf, feed.get());
+    std::unique_ptr<DevicePredWriter> writer;
+    if (pf && P.pred_write == "device")
+      writer.reset(new DevicePredWriter(learner.context(), pf, P.pred_prob));
+    const double tp = Now();
+    const Progress pr = RunEpoch(&learner, P, k0, GpuSGDLearner::kPrediction, pf, feed.get(),
+                                 nullptr, nullptr, nullptr, false, nullptr, nullptr, writer.get());
+    if (writer) writer->Finish();
+    const double pass_s = Now() - tp;
     if (pf) std::fclose(pf);
     std::printf("Prediction: %s\n", Text(pr).c_str());
+    if (P.pred_write == "device")
+      PrintPredWriteLine(writer ? writer->GetStats() : DevicePredWriter::Stats(), pass_s);
+    writer.reset();
     return 0;
   }
   const double t0 = Now();

@@ -619,6 +619,83 @@ def gather_rows_valued(ctx, src, rows=None, begin=0, n=None, dst=None, r0=0):
     check(_lib.lib().dfx_parse_criteo_wait(ctx.h, _p(stat_dev), st))
 
 
+PRED_ROW_BYTES = 26  # a formatted prediction row at most (csrc/fmtg.h kMaxRow)
+
+
+def format_pred_raw(ctx, label, pred, pred_prob, text, cap_bytes, values=None):
+    """dfx_format_pred on device tensors (float32 label / pred, uint8 text, float64 values or
+    None) -> [bytes written, rows flagged, first flagged row or -1, bytes the text needs];
+    joins the context stream."""
+    n = label.numel()
+    stat_dev = torch.empty(4, dtype=torch.int64, device=ctx.device)
+    check(_lib.lib().dfx_format_pred(ctx.h, _p(label), _p(pred), n, int(bool(pred_prob)),
+                                     _p(text), int(cap_bytes), _p(stat_dev), _p(values)))
+    ctx.sync()
+    return [int(x) for x in stat_dev.cpu().tolist()]
+
+
+def format_pred(ctx, label, pred, pred_prob=True, values=False):
+    """SavePred's lines (sgd_learner.h:72-83), "label\\tvalue\\n" with both fields as %g and
+    value = 1 / (1 + exp(-pred)) under pred_prob, formatted on the device (dfx_format_pred)
+    -> (text bytes, rows flagged[, the float64 values]).  A flagged row (a field outside
+    1e-12 <= |x| < 1e12 and not 0) is missing from the text: have the host write those."""
+    label = ctx.tensor(np.asarray(label, np.float32), torch.float32)
+    pred = ctx.tensor(np.asarray(pred, np.float32), torch.float32)
+    n = label.numel()
+    assert pred.numel() == n
+    cap = PRED_ROW_BYTES * n
+    text = torch.empty(max(cap, 1), dtype=torch.uint8, device=ctx.device)
+    vals = torch.empty(max(n, 1), dtype=torch.float64, device=ctx.device) if values else None
+    stat = format_pred_raw(ctx, label, pred, pred_prob, text, cap, vals)
+    out = bytes(text[:stat[0]].cpu().numpy().tobytes())
+    if values:
+        return out, stat[1], vals[:n].cpu().numpy()
+    return out, stat[1]
+
+
+class PredText:
+    """Two slots of device-formatted prediction text with pinned copies (dfx_predtext_*):
+    submit(slot, label, pred) behind the step that wrote pred, take(slot) while the next step
+    runs."""
+
+    def __init__(self, ctx, rows_hint=0):
+        self.ctx = ctx
+        h = ctypes.c_void_p()
+        check(_lib.lib().dfx_predtext_create(ctx.h, int(rows_hint), ctypes.byref(h)))
+        self.h = h
+
+    def submit(self, slot, label, pred, pred_prob=True):
+        """label, pred: float32 device tensors of one length"""
+        assert label.numel() == pred.numel()
+        check(_lib.lib().dfx_predtext_submit(self.h, int(slot), _p(label), _p(pred),
+                                             label.numel(), int(bool(pred_prob))))
+
+    def take(self, slot):
+        """-> dict(text=bytes, rows, flagged, first_flagged, label, pred): copies of the slot"""
+        o = _lib.PredTextOut()
+        check(_lib.lib().dfx_predtext_take(self.h, int(slot), ctypes.byref(o)))
+
+        def arr(p, n):
+            if not n:
+                return np.zeros(0, np.float32)
+            return np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_float)),
+                                         shape=(n,)).copy()
+        return dict(text=ctypes.string_at(o.text, o.bytes) if o.bytes else b"", rows=o.rows,
+                    flagged=o.flagged, first_flagged=o.first_flagged, label=arr(o.label, o.rows),
+                    pred=arr(o.pred, o.rows))
+
+    def close(self):
+        if getattr(self, "h", None):
+            h, self.h = self.h, None
+            check(_lib.lib().dfx_predtext_destroy(h))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # main-stream phases of dfx_train_step (the Localizer runs on its own lane; "localize" is
 # the part of it the main stream waits for)
 PHASES = ("localize", "probe_pull", "feacnt", "forward", "eval_auc", "backward_update", "initv")

@@ -432,6 +432,56 @@ int dfx_reshuffle_next(dfx_reshuffle* rs, dfx_batch* batch, int* has);
 int dfx_reshuffle_consumed(dfx_reshuffle* rs);
 int dfx_reshuffle_stats(dfx_reshuffle* rs, int64_t* out); /* out[4] */
 
+/* ---- prediction rows as text on the device (difacto_amd/csrc/predtext.hip) ----------------
+ * SGDLearner::SavePred (src/sgd/sgd_learner.h:72-83) writes one line per row,
+ *   label '\t' (pred_prob ? 1 / (1 + exp(-pred)) : pred) '\n',  both fields as "%g";
+ * the driver's host loop prints fprintf("%g\t%g\n", label, pred_prob ? 1.0 / (1.0 +
+ * std::exp(-pred)) : (double)pred) with label and pred floats.  dfx_format_pred forms those
+ * bytes on the device (csrc/fmtg.h: glibc's expf restated, IEEE double add and divide, %g as
+ * integer arithmetic, round half to even on the exact binary value): text_dev[0, bytes) holds
+ * the rows' lines in order, identical to the host loop's, for every row whose two fields are
+ * +-0 or 1e-12 <= |x| < 1e12 (csrc/fmtg.h widens this a little).  Any other row (non-finite, a
+ * probability below 1e-14, ...) is FLAGGED: it contributes no bytes, and the caller has the host
+ * write the batch.  stat_dev[4] (device) = {bytes written, rows flagged, the first flagged row
+ * or -1, bytes the text needs}; [3] > [0] iff cap_bytes was too small: the text is then cut at
+ * cap_bytes and no byte at or past it is written.  26 * n bytes always suffice.  value_out
+ * (optional, device, n doubles): the double each row's second field printed.  Three launches
+ * and a one-thread init on the context stream (rows to 32-byte records and tile totals, one
+ * block over the totals, the write pass); nothing waits on another block.  Scratch is the
+ * context's (32 bytes a row, grow-only; growing may synchronise).  DFX_ERR_ARG, nothing queued:
+ * a null ctx or stat_dev, n < 0 or n > 2^26, null label / pred / text with n > 0, cap_bytes < 0.
+ *
+ * A dfx_predtext double-buffers that for a prediction pass: two slots of device text, pinned
+ * host text and pinned copies of the batch's labels and predictions (what the host loop needs
+ * when a row was flagged).
+ *   dfx_predtext_submit   slot 0 | 1, not pending: on the context stream, so behind the step
+ *                         that wrote pred_dev, formats the n rows into the slot, then queues the
+ *                         copies down and the slot's event.  The slot grows to n rows on demand
+ *                         (that may synchronise).  label_dev and pred_dev are free for reuse by
+ *                         later work on the context stream.
+ *   dfx_predtext_take     waits for that slot's event alone and hands out the pinned text and
+ *                         arrays, valid until the slot's next submit; the slot is free again.
+ *                         Slot t is written to the file while the step of t + 1 runs.
+ *   dfx_predtext_destroy  joins the context stream.
+ * DFX_ERR_ARG: a slot outside 0..1, submit on a pending slot, take on one that is not, n as
+ * above; a rejected call queues nothing. */
+typedef struct dfx_predtext dfx_predtext;
+typedef struct dfx_predtext_out {
+  const char* text;  /* pinned: bytes of text */
+  int64_t bytes, rows;
+  int64_t flagged, first_flagged; /* rows the device did not format; the first, or -1 */
+  const float* label; /* pinned: the batch's labels and raw predictions, rows each */
+  const float* pred;
+} dfx_predtext_out;
+int dfx_format_pred(dfx_ctx* ctx, const float* label_dev, const float* pred_dev, int64_t n,
+                    int pred_prob, char* text_dev, int64_t cap_bytes, int64_t* stat_dev,
+                    double* value_out);
+int dfx_predtext_create(dfx_ctx* ctx, int64_t rows_hint, dfx_predtext** out);
+int dfx_predtext_submit(dfx_predtext* pt, int slot, const float* label_dev, const float* pred_dev,
+                        int64_t n, int pred_prob);
+int dfx_predtext_take(dfx_predtext* pt, int slot, dfx_predtext_out* out);
+int dfx_predtext_destroy(dfx_predtext* pt);
+
 /* ---- Localizer::Compact (localizer.h:41-51) -------------------------------------------
  * keys = ReverseBytes(index % max_index); uniq[U] ascending, cnt[U] occurrence counts
  * (float, may be NULL), col[nnz] = rank of each nnz's key (the u32 CSR index).  Offsets,
