@@ -33,11 +33,12 @@ TPBIN = build/textparse_tests
 LSBIN = build/libsvmparse_tests
 SEBIN = build/shard_eval_tests
 SDBIN = build/split_device_tests
+SPBIN = build/shard_parse_tests
 
 DISTLIB = difacto_amd/libdfx_dist.so
 
 all: $(LIB) $(DISTLIB) oracle $(HOSTBIN) $(TRAINBIN) $(READERBIN) $(GENBIN) $(CONVBIN) $(RBENCH) \
-  $(TPBIN) $(LSBIN) $(SEBIN) $(SDBIN) build/expf_check build/strtof_check build/gen_libsvm build/locbench \
+  $(TPBIN) $(LSBIN) $(SEBIN) $(SDBIN) $(SPBIN) build/expf_check build/strtof_check build/gen_libsvm build/locbench \
   build/reshuffle_check build/fmtg_check
 
 $(RBENCH): difacto_amd/host/reader.cc tools/reader_bench.cc difacto_amd/host/reader.h $(CITYHDR)
@@ -121,6 +122,16 @@ $(SDBIN): $(HOSTLIB) difacto_amd/host/split_learner.cc tests/host/split_device_t
 	@mkdir -p build
 	g++ $(HOSTFLAGS) -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -o $@ $(HOSTLIB) \
 	  difacto_amd/host/split_learner.cc tests/host/split_device_tests.cc build/obj/dist_host.o \
+	  -Ldifacto_amd -ldifacto_amd -ldfx_dist -L/opt/rocm/lib -lrccl -lamdhip64 \
+	  -Wl,-rpath,'$$ORIGIN/../difacto_amd' -Wl,-rpath,/opt/rocm/lib
+
+# both sharded stores fed by DeviceBatchReaders (late marking of the text feed's ring entries and
+# slots) against the same stores fed the host reader's blocks, bit for bit
+$(SPBIN): $(HOSTLIB) difacto_amd/host/split_learner.cc tests/host/shard_parse_tests.cc $(HOSTHDR) \
+  build/obj/dist_host.o $(LIB) $(DISTLIB)
+	@mkdir -p build
+	g++ $(HOSTFLAGS) -o $@ $(HOSTLIB) difacto_amd/host/split_learner.cc \
+	  tests/host/shard_parse_tests.cc build/obj/dist_host.o \
 	  -Ldifacto_amd -ldifacto_amd -ldfx_dist -L/opt/rocm/lib -lrccl -lamdhip64 \
 	  -Wl,-rpath,'$$ORIGIN/../difacto_amd' -Wl,-rpath,/opt/rocm/lib
 

@@ -131,6 +131,10 @@ _SIGS = {
     "dfx_textfeed_batch_end": (ctypes.c_int, [vp, c_i64, c_i64, ctypes.c_int,
                                               ctypes.POINTER(Batch)]),
     "dfx_textfeed_consumed": (ctypes.c_int, [vp]),
+    "dfx_textfeed_consumed_back": (ctypes.c_int, [vp, ctypes.c_int]),
+    "dfx_textfeed_counts": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int),
+                                           ctypes.POINTER(ctypes.c_int),
+                                           ctypes.POINTER(ctypes.c_int)]),
     "dfx_textfeed_slot_batch": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int,
                                                ctypes.POINTER(Batch)]),
     "dfx_textfeed_slot_consumed": (ctypes.c_int, [vp, ctypes.c_int]),

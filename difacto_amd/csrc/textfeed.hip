@@ -387,9 +387,27 @@ extern "C" int dfx_textfeed_batch_end(dfx_textfeed* f, int64_t rows, int64_t nnz
   return DFX_OK;
 }
 
-extern "C" int dfx_textfeed_consumed(dfx_textfeed* f) {
+extern "C" int dfx_textfeed_consumed(dfx_textfeed* f) { return dfx_textfeed_consumed_back(f, 0); }
+
+// Late marking (as dfx_feeder_consumed_back): a store that defers a step queues the last reader
+// of a batch calls after it was handed out.  An event wait sees only the last record made
+// before the wait is issued, so the entry begun `back` begins ago is marked here, by the call
+// that follows the one that queued its last reader, and before dfx_textfeed_batch_begin comes
+// round to it (the caller's ring is deeper than its deferral).  The readers run on the context
+// stream (the sharded stores' fwd_bwd / combine), so that is where the event goes.
+extern "C" int dfx_textfeed_consumed_back(dfx_textfeed* f, int back) {
+  const int n = f ? (int)f->ring.size() : 0;
   DFX_CHECK_ARG(f && f->cur >= 0, "textfeed_consumed: no batch begun");
-  DFX_HIP(hipEventRecord(f->ring[f->cur].consumed, f->ctx->c.stream));
+  DFX_CHECK_ARG(back >= 0 && back < n, "textfeed_consumed_back: back outside the ring");
+  DFX_HIP(hipEventRecord(f->ring[(f->cur - back + n) % n].consumed, f->ctx->c.stream));
+  return DFX_OK;
+}
+
+extern "C" int dfx_textfeed_counts(dfx_textfeed* f, int* nslots, int* nring, int* cur) {
+  DFX_CHECK_ARG(f, "textfeed_counts: null argument");
+  if (nslots) *nslots = (int)f->slot.size();
+  if (nring) *nring = (int)f->ring.size();
+  if (cur) *cur = f->cur;
   return DFX_OK;
 }
 

@@ -15,17 +15,74 @@ static double Seconds() {
 }
 
 DeviceTextFeed::DeviceTextFeed(dfx_ctx* ctx, size_t batch_size, size_t shuf_buf,
-                               const std::string& format)
+                               const std::string& format, int nslots, int nring)
     : batch_size_(batch_size ? batch_size : 1),
       shuf_buf_(shuf_buf),
       format_(format == "libsvm" ? DFX_TEXT_LIBSVM : DFX_TEXT_CRITEO) {
-  DfxCheck(dfx_textfeed_create(ctx, kSlots, kRing, (int64_t)batch_size_, (int64_t)shuf_buf_,
+  DfxCheck(dfx_textfeed_create(ctx, nslots, nring, (int64_t)batch_size_, (int64_t)shuf_buf_,
                                format_, &h_),
            "dfx_textfeed_create");
+  slot_held_.assign((size_t)nslots, false);
+  ring_out_.assign((size_t)nring, false);
 }
 
 DeviceTextFeed::~DeviceTextFeed() {
   if (h_) dfx_textfeed_destroy(h_);
+}
+
+void DeviceTextFeed::BeginBatch() {
+  int cur = -1;
+  DfxCheck(dfx_textfeed_counts(h_, nullptr, nullptr, &cur), "dfx_textfeed_counts");
+  const int next = (cur + 1) % nring();
+  if (ring_out_[next])
+    throw FeedProtocolError(
+        "text feed: the ring came round to a batch that was handed out and never marked (a "
+        "missing Consumed / Mark, or a ring no deeper than the caller's deferral)");
+  DfxCheck(dfx_textfeed_batch_begin(h_), "dfx_textfeed_batch_begin");
+}
+
+void DeviceTextFeed::HandOutEntry() {
+  int cur = -1;
+  DfxCheck(dfx_textfeed_counts(h_, nullptr, nullptr, &cur), "dfx_textfeed_counts");
+  if (cur < 0) throw FeedProtocolError("text feed: no batch begun");
+  ring_out_[cur] = true;
+  out_.push_back(Out{next_ticket_++, false, cur});
+}
+
+void DeviceTextFeed::HandOutSlot(int slot) {
+  if (slot < 0 || slot >= nslots() || slot_held_[slot])
+    throw FeedProtocolError("text feed: a slot handed out twice");
+  slot_held_[slot] = true;
+  out_.push_back(Out{next_ticket_++, true, slot});
+}
+
+int DeviceTextFeed::SlotsHeld() const {
+  int n = 0;
+  for (bool b : slot_held_) n += b;
+  return n;
+}
+
+void DeviceTextFeed::Mark(uint64_t ticket) {
+  for (auto it = out_.begin(); it != out_.end(); ++it) {
+    if (it->ticket != ticket) continue;
+    const Out o = *it;
+    out_.erase(it);
+    if (o.is_slot) {
+      DfxCheck(dfx_textfeed_slot_consumed(h_, o.idx), "dfx_textfeed_slot_consumed");
+      slot_held_[o.idx] = false;
+      if (on_slot_free_) on_slot_free_(o.idx);
+    } else {
+      // (an unmarked entry was not begun again: BeginBatch would have thrown)
+      int cur = -1;
+      DfxCheck(dfx_textfeed_counts(h_, nullptr, nullptr, &cur), "dfx_textfeed_counts");
+      DfxCheck(dfx_textfeed_consumed_back(h_, (cur - o.idx + nring()) % nring()),
+               "dfx_textfeed_consumed_back");
+      ring_out_[o.idx] = false;
+    }
+    return;
+  }
+  if (ticket >= next_ticket_)
+    throw FeedProtocolError("text feed: a mark for a batch not handed out yet");
 }
 
 // src -> dst over up to nthreads threads; returns the number of '\n' bytes copied; blanks
@@ -81,7 +138,8 @@ DeviceBatchReader::DeviceBatchReader(DeviceTextFeed* feed, const std::string& pa
                                      const std::string& format, int part, int nparts,
                                      size_t batch_size, size_t shuf_buf, float neg_sampling,
                                      int nthreads, size_t chunk_bytes)
-    : f_(feed->h()),
+    : feed_(feed),
+      f_(feed->h()),
       reader_(path, format, part, nparts, chunk_bytes, nthreads, 0),
       train_(format != "criteo_test"),
       valued_(feed->valued()),
@@ -100,11 +158,24 @@ DeviceBatchReader::DeviceBatchReader(DeviceTextFeed* feed, const std::string& pa
         },
         [this](const GatherOp& op) { Gather(op); }));
   }
-  for (int s = 0; s < DeviceTextFeed::kSlots; ++s) free_.push_back(s);
+  // a slot an earlier reader's batch still holds (handed out, not marked yet) stays away from
+  // the loader; it comes here when it is marked.  This reader's own current chunk goes back at
+  // the next FetchChunk, as ever.
+  for (int s = 0; s < feed_->nslots(); ++s)
+    if (!feed_->SlotHeld(s)) free_.push_back(s);
+  feed_->OnSlotFree([this](int s) {
+    if (s == cur_slot_) return;
+    {
+      std::lock_guard<std::mutex> lk(mu_);
+      free_.push_back(s);
+    }
+    cv_.notify_all();
+  });
   loader_ = std::thread([this]() { Load(); });
 }
 
 DeviceBatchReader::~DeviceBatchReader() {
+  feed_->OnSlotFree(nullptr);
   {
     std::lock_guard<std::mutex> lk(mu_);
     stop_ = true;
@@ -175,6 +246,10 @@ void DeviceBatchReader::SubmitFilled(bool wait) {
 
 void DeviceBatchReader::ReleaseChunk() {
   if (cur_slot_ < 0) return;
+  if (feed_->SlotHeld(cur_slot_)) {  // its batch is not marked yet: freed by the mark
+    cur_slot_ = -1;
+    return;
+  }
   {
     std::lock_guard<std::mutex> lk(mu_);
     free_.push_back(cur_slot_);
@@ -266,6 +341,12 @@ bool DeviceBatchReader::Next() {
     size_t rows = 0;
     const uint64_t* off;
     const float* lab;
+    // held slots wait for their marks; with one slot left to circulate, marks are missing (or
+    // the feed has fewer slots than the caller's deferral + 2): the loader would starve next
+    if (feed_->SlotsHeld() >= feed_->nslots() - 1)
+      throw FeedProtocolError(
+          "text feed: every text slot but one holds a batch that was handed out and never "
+          "marked (a missing Consumed / Mark, or fewer slots than the caller's deferral + 2)");
     do {
       if (!FetchChunk(&rows, &off, &lab)) return false;
     } while (rows == 0);
@@ -273,11 +354,12 @@ bool DeviceBatchReader::Next() {
     for (size_t r = 0; chunk_flag_ && r < chunk_rows_ && !valued; ++r) valued = chunk_flag_[r];
     DfxCheck(dfx_textfeed_slot_batch(f_, cur_slot_, valued ? 1 : 0, &batch_),
              "dfx_textfeed_slot_batch");
+    feed_->HandOutSlot(cur_slot_);
     slot_batch_ = true;
     return true;
   }
   const double t0 = Seconds();
-  DfxCheck(dfx_textfeed_batch_begin(f_), "dfx_textfeed_batch_begin");
+  feed_->BeginBatch();
   times_.wait_step += Seconds() - t0;
   size_t rows, nnz;
   batch_valued_ = false;
@@ -285,16 +367,13 @@ bool DeviceBatchReader::Next() {
   DfxCheck(
       dfx_textfeed_batch_end(f_, (int64_t)rows, (int64_t)nnz, batch_valued_ ? 1 : 0, &batch_),
       "dfx_textfeed_batch_end");
+  feed_->HandOutEntry();
   slot_batch_ = false;
   return true;
 }
 
 void DeviceBatchReader::Consumed() {
-  if (slot_batch_) {
-    DfxCheck(dfx_textfeed_slot_consumed(f_, cur_slot_), "dfx_textfeed_slot_consumed");
-  } else {
-    DfxCheck(dfx_textfeed_consumed(f_), "dfx_textfeed_consumed");
-  }
+  feed_->MarkBack(0);
 }
 
 }  // namespace difacto

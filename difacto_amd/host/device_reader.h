@@ -31,8 +31,10 @@
 
 #include <condition_variable>
 #include <deque>
+#include <functional>
 #include <memory>
 #include <mutex>
+#include <stdexcept>
 #include <string>
 #include <thread>
 #include <vector>
@@ -42,15 +44,31 @@
 
 namespace difacto {
 
+/** a misuse of the feed's marking protocol (below): thrown on the host, before anything is reused */
+struct FeedProtocolError : std::logic_error {
+  explicit FeedProtocolError(const std::string& what) : std::logic_error(what) {}
+};
+
 /** the device side shared by the readers of a run: pinned text slots, parsed chunks, the
  * shuffle buffer and the batch ring (dfx_textfeed); its loader stream is the context's input
  * stream while it lives */
+//
+// Marking.  Every batch a reader hands out holds a ring entry or a text slot of the feed until
+// it is marked: the mark records the entry's event on the context stream, so it must be made
+// after the call that queued the batch's last reader.  The single-GPU step is queued when
+// dfx_train_step returns (DeviceBatchReader::Consumed right after it); the sharded stores run a
+// step one Submit later or at a flush, and their runners mark the batch then (Mark with the
+// batch's ticket, or MarkBack), readers of later parts having been made on the same feed
+// meanwhile.  So the handed-out / marked state lives here, in the feed, and outlives a reader:
+// an unmarked slot is kept from the loader, and coming round to an unmarked ring entry, or
+// running out of slots because marks are missing, throws FeedProtocolError instead of racing.
 class DeviceTextFeed {
  public:
   static constexpr int kSlots = 3, kRing = 3;
-  /** format: "libsvm" makes a DFX_TEXT_LIBSVM feed, anything else a DFX_TEXT_CRITEO one */
+  /** format: "libsvm" makes a DFX_TEXT_LIBSVM feed, anything else a DFX_TEXT_CRITEO one.
+   * nslots, nring: a caller that marks a batch `d` hand-outs late needs both >= d + 2 */
   DeviceTextFeed(dfx_ctx* ctx, size_t batch_size, size_t shuf_buf,
-                 const std::string& format = "criteo");
+                 const std::string& format = "criteo", int nslots = kSlots, int nring = kRing);
   ~DeviceTextFeed();
   DeviceTextFeed(const DeviceTextFeed&) = delete;
   DeviceTextFeed& operator=(const DeviceTextFeed&) = delete;
@@ -59,11 +77,42 @@ class DeviceTextFeed {
   size_t shuf_buf() const { return shuf_buf_; }
   int format() const { return format_; }
   bool valued() const { return format_ == DFX_TEXT_LIBSVM; }
+  int nslots() const { return (int)slot_held_.size(); }
+  int nring() const { return (int)ring_out_.size(); }
+
+  /** the batch handed out last (by any reader of this feed); tickets count up by one */
+  uint64_t LastTicket() const { return next_ticket_ - 1; }
+  /** the last reader of the batch was queued: records its event now.  Marking twice is a no-op */
+  void Mark(uint64_t ticket);
+  /** Mark of the batch handed out `back` batches ago */
+  void MarkBack(int back) { Mark(LastTicket() - (uint64_t)back); }
+  /** batches handed out and not marked */
+  int Unmarked() const { return (int)out_.size(); }
+
+  // ---- the readers' side ----
+  /** dfx_textfeed_batch_begin; throws if the entry it comes round to is handed out and unmarked */
+  void BeginBatch();
+  /** the entry last begun / the slot goes out as a batch */
+  void HandOutEntry();
+  void HandOutSlot(int slot);
+  bool SlotHeld(int slot) const { return slot_held_[slot]; }
+  int SlotsHeld() const;
+  /** called with the slot when a held slot is marked (the live reader takes it back) */
+  void OnSlotFree(std::function<void(int)> fn) { on_slot_free_ = std::move(fn); }
 
  private:
+  struct Out {
+    uint64_t ticket;
+    bool is_slot;
+    int idx;
+  };
   dfx_textfeed* h_ = nullptr;
   size_t batch_size_, shuf_buf_;
   int format_;
+  std::vector<bool> slot_held_, ring_out_;
+  std::deque<Out> out_;  // unmarked, oldest first
+  uint64_t next_ticket_ = 0;
+  std::function<void(int)> on_slot_free_;
 };
 
 class DeviceBatchReader {
@@ -80,8 +129,12 @@ class DeviceBatchReader {
   /** the next batch, queued on the device (asynchronous); false at the end of the part */
   bool Next();
   const dfx_batch& Value() const { return batch_; }
-  /** after the dfx_train_step that took Value() was queued: its arrays are in use until then */
+  /** after the dfx_train_step that took Value() was queued: its arrays are in use until then
+   * (DeviceTextFeed::MarkBack(0)).  A caller whose step is queued later marks the batch through
+   * the feed instead, with Ticket(), once that has happened. */
   void Consumed();
+  /** the feed's ticket of Value() */
+  uint64_t Ticket() const { return feed_->LastTicket(); }
   /** whole-chunk mode: the current chunk's labels on the host (the copy back of the parse) */
   const float* HostLabels() const { return chunk_lab_; }
   /** chunks the device handed back to the host parser so far */
@@ -105,6 +158,7 @@ class DeviceBatchReader {
   void SubmitFilled(bool wait); // queue the parses of the filled slots
   bool FetchChunk(size_t* rows, const uint64_t** off, const float** lab);
   void ReleaseChunk();
+  DeviceTextFeed* feed_;
   dfx_textfeed* f_;
   TextReader reader_;
   bool train_, valued_;

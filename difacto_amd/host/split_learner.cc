@@ -5,6 +5,7 @@
 #include <condition_variable>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <limits>
 #include <mutex>
 #include <string>
@@ -45,6 +46,8 @@ struct GpuSplitLearner::Impl {
   // the queued (pipelined) step's batch of worker l sits in its feeder's newest slot: a device
   // item or none holds no slot, and the learner owes it nothing
   std::vector<bool> queued_host;
+  // ... a device item with a release hook is owed the call, once the queued step ran
+  std::vector<std::function<void()>> queued_release;
   int arrived = 0;
   int64_t gen = 0;
   std::string failure;
@@ -75,6 +78,7 @@ struct GpuSplitLearner::Impl {
     if (store) DistCheck(dfx_split_store_sync(store), "dfx_split_store_sync");
     queued = false;
     queued_host.assign(L, false);
+    Released();
     for (dfx_ctx* c : ctxs) DfxCheck(dfx_sync(c), "dfx_sync");
     for (dfx_feeder* f : feeders) DfxCheck(dfx_feeder_destroy(f), "dfx_feeder_destroy");
     feeders.assign(L, nullptr);
@@ -85,12 +89,22 @@ struct GpuSplitLearner::Impl {
                "dfx_feeder_create_slots");
   }
 
-  // the queued step ran (a flush): the staging slots of its host items are free behind it
+  // the queued step's device items had their last reader (the combine) queued
+  void Released() {
+    for (auto& r : queued_release) {
+      if (r) r();
+      r = nullptr;
+    }
+  }
+
+  // the queued step ran (a flush): the staging slots of its host items are free behind it, and
+  // its device items' owners hear of it
   void QueuedRan() {
     for (int l = 0; l < L; ++l)
       if (queued_host[l]) DfxCheck(dfx_feeder_consumed(feeders[l]), "dfx_feeder_consumed");
     queued_host.assign(L, false);
     queued = false;
+    Released();
   }
 
   // the last local worker's call: every pending host batch uploaded, one step submitted
@@ -146,7 +160,18 @@ struct GpuSplitLearner::Impl {
               "dfx_split_store_submit");
     // a pipelined submit queued the previous step, the last reader of the previous batch: of a
     // worker whose previous item was a host block, that is the slot one back when this item
-    // took a slot too, else still the feeder's newest.  Device items are never counted.
+    // took a slot too, else still the feeder's newest.  Device items are never counted: one
+    // whose owner reuses its arrays (a text feed's ring entry or slot) carries a release hook,
+    // called on the same schedule, after the submit that queued the item's combine.
+    if (pipelined) Released();
+    for (int l = 0; l < L; ++l) {
+      if (pend[l].release) {
+        if (pipelined)
+          queued_release[l] = pend[l].release;
+        else
+          pend[l].release();
+      }
+    }
     for (int l = 0; l < L; ++l) {
       const bool host = pend[l].host != nullptr;
       if (pipelined) {
@@ -269,6 +294,7 @@ GpuSplitLearner::GpuSplitLearner(std::unique_ptr<Impl> impl) : impl_(std::move(i
   impl_->pend_cnt.assign(impl_->L, 0);
   impl_->pend_pred.assign(impl_->L, nullptr);
   impl_->queued_host.assign(impl_->L, false);
+  impl_->queued_release.assign(impl_->L, nullptr);
 }
 
 GpuSplitLearner::~GpuSplitLearner() {}

@@ -23,6 +23,7 @@
 #ifndef DIFACTO_AMD_HOST_SPLIT_LEARNER_H_
 #define DIFACTO_AMD_HOST_SPLIT_LEARNER_H_
 
+#include <functional>
 #include <memory>
 #include <vector>
 
@@ -59,11 +60,23 @@ class GpuSplitLearner {
   void ProcessBatches(const std::vector<const dmlc::RowBlock<feaid_t>*>& batches, int job_type,
                       bool push_cnt, std::vector<std::vector<real_t>>* preds = nullptr);
   /** a local worker's batch of one step: a host row block (staged and uploaded, as
-   * ProcessBatches'), or a batch in device memory (a DeviceBatchCache's: ready by the context's
-   * input stream's order and alive until the learner is gone), or neither: an empty batch */
+   * ProcessBatches'), or a batch in device memory (ready by the context's input stream's
+   * order; a DeviceBatchCache's, alive until the learner is gone, or one alive until its release
+   * hook is called), or neither: an empty batch.
+   * The input stream: the learner makes its feeders, whose loader stream replaces the context's
+   * input stream, only when a step holds a host item (Impl::Feeders).  A caller that keeps a
+   * DeviceTextFeed on a shard's context gives that shard no host item while the feed lives, so
+   * the input stream stays the feed's: its gathers, a cache's Append copies and the store's wait
+   * for the device items are ordered by it. */
   struct Item {
     const dmlc::RowBlock<feaid_t>* host = nullptr;
     const dfx_batch* dev = nullptr;
+    /** a device item whose arrays the owner reuses (a DeviceTextFeed's ring entry or text
+     * slot): called on the submitting thread once the item's last reader, the step's combine on
+     * the context stream, has been queued — inside this call when pipelined=0, inside the next
+     * submit or the flush (Flush, Sync, a step that asks for predictions) when pipelined=1.
+     * An event recorded on the context stream from the hook is behind that reader. */
+    std::function<void()> release;
   };
   /** one step from a single caller thread, like ProcessBatches (its all-host case); host and
    * device items may be mixed in a step.  A device item goes to the split store as it is: no

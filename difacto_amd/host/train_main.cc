@@ -6,7 +6,8 @@
 //                   [num_jobs_per_epoch=10] [stop_rel_objv=1e-5] [stop_val_auc=1e-5]
 //                   [model_in=F] [model_out=F]
 //                   [load_epoch=-1] [has_aux=0] [task=0|2] [pred_out=F] [pred_prob=1]
-//                   [fused=1] [nthreads=8] [parse=host|device|auto] [cache=none|device|auto]
+//                   [fused=1] [nthreads=8] [parse=host|device|auto|auto-sharded]
+//                   [cache=none|device|auto]
 //                   [cache_mb=16384] [cache_loc=0] [epoch_shuffle=0] [shuffle_seed=0]
 //                   [pred_write=host|device]
 //                   [V_dim=..] [lr=..] [l1=..] ... (SGDUpdaterParam)
@@ -23,6 +24,21 @@
 // are) and the run is the single-GPU fused path, else the host reader; one line at the start
 // says which and why, e.g. "parse: device (libsvm)" or "parse: host (exchange=split)".
 // parse=device keeps its contract: Criteo formats only, anything else is an error.
+//
+// parse=auto-sharded is parse=auto that takes the device parser in the sharded runs too
+// (shards=N, shards=-1, WORLD_SIZE > 1; both exchanges; pipelined=0|1; training, data_val
+// validation and task=2): every local shard reads its parts with a DeviceBatchReader on a text
+// feed of its own (DeviceTextFeed on the shard's context, alive for the run), the same parts,
+// chunks and batches as the host reader's, so the same results.  The sharded stores queue a
+// step's last reader of its batch one Step call late when pipelined, so a feed batch is marked
+// by the runner at that call or at the flush (ShardRunner::Mark), not when it is handed over,
+// and the feeds are 4 slots and 4 ring entries deep.  Rank 0 prints "parse: device (<format>,
+// <n> shards)" or, for a format with no device parser, "parse: host (data_format=<f>)"; without
+// shards the value is parse=auto and prints its line.  cache=device|auto records the feed's
+// batches; pred_write=host writes from the chunk's labels the parse copied back, pred_write=
+// device reads the device labels before the batch is marked.  Chunks handed back to the host
+// parser are summed over shards and ranks and reported by rank 0.  A training epoch that read
+// also prints where the device readers' time went.
 //
 // cache=device (the single-GPU fused path with either parse and any data_format, training and
 // data_val validation; the sharded exchange=a2a runs): the first epoch the run executes (after
@@ -385,7 +401,30 @@ class ShardRunner {
   struct Item {
     const RowBlockContainer<feaid_t>* host = nullptr;
     int64_t replay = -1;
+    // parse=auto-sharded: a batch the shard's DeviceBatchReader formed.  It holds a ring entry
+    // or a text slot of `feed` until the runner marks `ticket`, which it does after the call
+    // that queued the batch's last reader (see Mark below)
+    const dfx_batch* dev = nullptr;
+    DeviceTextFeed* feed = nullptr;
+    uint64_t ticket = 0;
   };
+  // A feed batch's mark.  Both stores read a worker's batch twice: at the submit that takes it
+  // (a2a: the Localizer, dfx_dist_localize; split: dfx_split_partition), and in the step's main
+  // part (a2a: dfx_dist_fwd_bwd reads offsets, values, labels; split: dfx_split_combine reads
+  // the labels for the loss), which runs on the context stream — inside the same submit with
+  // pipelined=0, inside the NEXT submit or the flush with pipelined=1.  Nothing later reads it
+  // (the gradient push and the split's backward work on the step's own buffers).  So the
+  // deferral is one Step call at most, the mark's event goes on the context stream, and a
+  // sharded feed has kShardFeedDepth >= 1 + 2 ring entries and slots.
+  struct Mark {
+    DeviceTextFeed* feed;
+    uint64_t ticket;
+  };
+  static void MarkAll(std::vector<Mark>* v) {
+    for (const Mark& m : *v) m.feed->Mark(m.ticket);
+    v->clear();
+  }
+  static constexpr int kShardFeedDepth = 4;
   virtual ~ShardRunner() {}
   virtual int nlocal() const = 0;
   virtual int nranks() const = 0;
@@ -416,7 +455,7 @@ class ShardRunner {
 
 class A2aRunner : public ShardRunner {
  public:
-  A2aRunner(const Param& P, const KWArgs& rest) {
+  A2aRunner(const Param& P, const KWArgs& rest) : pipelined_(P.pipelined) {
     const char* ws = std::getenv("WORLD_SIZE");
     const int world = ws ? std::atoi(ws) : 1;
     const bool rccl = world > 1 || P.shards < 0;
@@ -467,9 +506,16 @@ class A2aRunner : public ShardRunner {
             std::vector<std::unique_ptr<DevicePredWriter>>* writers) override {
     const int L = nlocal();
     std::vector<dfx_batch> bs(L);
+    std::vector<Mark> now;  // this step's feed batches
     for (int l = 0; l < L; ++l) {
       if (items[l].replay >= 0) {
         bs[l] = caches_[l]->Get(list, items[l].replay);
+        continue;
+      }
+      if (items[l].dev) {  // as it is; the cache's copy runs on the feed's stream, behind the gathers
+        bs[l] = *items[l].dev;
+        if (record) caches_[l]->Append(bs[l]);
+        now.push_back(Mark{items[l].feed, items[l].ticket});
         continue;
       }
       DevBatch& db = dev_[l][ring_];  // three per shard: a queued step still reads the last
@@ -480,6 +526,14 @@ class A2aRunner : public ShardRunner {
     ring_ = (ring_ + 1) % 3;
     if (!preds) {
       store_->Submit(bs, job_type, push_cnt);
+      // pipelined: this Submit ran the step before, whose fwd_bwd was its batches' last reader;
+      // else this step ran
+      if (pipelined_) {
+        MarkAll(&queued_marks_);
+        queued_marks_.swap(now);
+      } else {
+        MarkAll(&now);
+      }
       return;
     }
     // a submitted step runs at the next Submit or at Flush: flush, then its predictions come
@@ -496,15 +550,21 @@ class A2aRunner : public ShardRunner {
     if (writers) {  // (a DevBatch is uploaded into again three steps on)
       for (int l = 0; l < L; ++l)
         if (bs[l].size) (*writers)[l]->Submit(bs[l].label, dp[l], bs[l].size);
-      return;
     }
+    // every step ran, and the writers' reads of the device labels are queued
+    MarkAll(&queued_marks_);
+    MarkAll(&now);
+    if (writers) return;
     preds->resize(L);
     for (int l = 0; l < L; ++l) {
       (*preds)[l].resize((size_t)bs[l].size);
       dpred_[l]->download((*preds)[l].data(), (size_t)bs[l].size);
     }
   }
-  void Flush() override { store_->Flush(); }
+  void Flush() override {
+    store_->Flush();
+    MarkAll(&queued_marks_);  // the queued step ran
+  }
   bool has_cache() const override { return !caches_.empty(); }
   int64_t Cached(int l, int64_t list) override { return caches_[l]->Count(list); }
   void BeginList(int64_t list) override {
@@ -525,6 +585,8 @@ class A2aRunner : public ShardRunner {
   }
 
  private:
+  const bool pipelined_;
+  std::vector<Mark> queued_marks_;  // the queued step's feed batches (pipelined)
   std::vector<dfx_ctx*> ctxs_;
   std::unique_ptr<ShardExchange> ex_;
   std::unique_ptr<GpuShardedStore> store_;
@@ -572,10 +634,27 @@ class SplitRunner : public ShardRunner {
     std::vector<dmlc::RowBlock<feaid_t>> blk(L);
     std::vector<dfx_batch> dev(L);
     std::vector<GpuSplitLearner::Item> it(L);
+    std::vector<Mark> now;  // feed batches this call marks itself
     for (int l = 0; l < L; ++l) {
       if (items[l].replay >= 0) {
         dev[l] = caches_[l]->Get(list, items[l].replay);
         it[l].dev = &dev[l];
+      } else if (items[l].dev) {
+        // a feed's batch, as it is.  The learner makes no feeder while no host item is pending
+        // (Impl::Feeders), and a run with feeds gives it none, so the context's input stream
+        // stays the feed's.  The learner calls the release hook after the submit that queued
+        // the batch's combine; with a writer the step runs inside the call and the mark waits
+        // for the writer's read of the labels instead (below).
+        dev[l] = *items[l].dev;
+        it[l].dev = &dev[l];
+        DeviceTextFeed* const feed = items[l].feed;
+        const uint64_t ticket = items[l].ticket;
+        if (preds && writers)
+          now.push_back(Mark{feed, ticket});
+        else
+          it[l].release = [feed, ticket]() { feed->Mark(ticket); };
+        // recorded on the feed's stream, behind the gathers and before the partition's wait
+        if (record && !caches_.empty()) caches_[l]->Append(dev[l]);
       } else if (items[l].host) {
         blk[l] = items[l].host->GetBlock();
         it[l].host = &blk[l];
@@ -588,6 +667,7 @@ class SplitRunner : public ShardRunner {
       sl_->ProcessDeviceBatches(it, job_type, push_cnt, nullptr, &up, &dp);
       for (int l = 0; l < L; ++l)
         if (up[l].size) (*writers)[l]->Submit(up[l].label, dp[l], up[l].size);
+      MarkAll(&now);
       return;
     }
     sl_->ProcessDeviceBatches(it, job_type, push_cnt, preds, rec ? &up : nullptr);
@@ -658,29 +738,45 @@ class PartReader {
 // store is flushed and the progress summed over every shard of every rank.
 // pred_files (prediction): local shard l's rows go to pred_files[l] in the order read.
 // host_s (optional): += the host seconds inside Step and inside the per-step all-reduce.
+// feeds (parse=auto-sharded): local shard l's parts are read by a DeviceBatchReader on
+// (*feeds)[l] instead of a PartReader: the same parts, chunks and batches, formed on the device.
+// A reader lives for one job; the batches it handed out may be marked after it is gone (the
+// feed keeps that state).  times (optional): += the device readers' Times.
 Progress ShardedPass(ShardRunner* run, const Param& P, int epoch, int job_type, bool record,
                      const std::vector<FILE*>* pred_files = nullptr, double* host_s = nullptr,
-                     std::vector<std::unique_ptr<DevicePredWriter>>* writers = nullptr) {
+                     std::vector<std::unique_ptr<DevicePredWriter>>* writers = nullptr,
+                     std::vector<std::unique_ptr<DeviceTextFeed>>* feeds = nullptr,
+                     DeviceBatchReader::Times* times = nullptr) {
   const int nlocal = run->nlocal(), nshards = run->nranks();
   const bool train = job_type == GpuSGDLearner::kTraining;
   const int nparts = P.num_jobs_per_epoch * nshards;
   std::vector<std::vector<real_t>> preds;
+  double fallback = 0;
   for (int job = 0; job < P.num_jobs_per_epoch; ++job) {
     const int64_t list = CacheList(P, train, job);
     const bool rec = record && run->has_cache();
     std::vector<std::unique_ptr<PartReader>> rd(nlocal);
+    std::vector<std::unique_ptr<DeviceBatchReader>> drd(nlocal);
     std::vector<int64_t> n_cached(nlocal, -1), pos(nlocal, 0);
     for (int l = 0; l < nlocal; ++l) {
       if (run->has_cache() && !record) n_cached[l] = run->Cached(l, list);
-      if (n_cached[l] < 0)
-        rd[l].reset(new PartReader(P, train, job * nshards + run->rank(l), nparts));
+      if (n_cached[l] >= 0) continue;
+      const int part = job * nshards + run->rank(l);
+      if (feeds)  // training: minibatches out of 64 MB chunks; else whole 256 MB chunks (RunEpoch)
+        drd[l].reset(new DeviceBatchReader(
+            (*feeds)[l].get(), train ? P.data_in : P.data_val, P.data_format, part, nparts,
+            train ? P.batch_size : 0, train ? P.batch_size * P.shuffle : 0,
+            train ? P.neg_sampling : 1.f, P.nthreads, train ? (size_t)64 << 20 : (size_t)256 << 20));
+      else
+        rd[l].reset(new PartReader(P, train, part, nparts));
     }
     if (rec) run->BeginList(list);
     std::vector<bool> more(nlocal, true);
     for (;;) {
       std::vector<double> any(1, 0.0);
       for (int l = 0; l < nlocal; ++l) {
-        if (more[l]) more[l] = rd[l] ? rd[l]->Next() : pos[l] < n_cached[l];
+        if (more[l])
+          more[l] = drd[l] ? drd[l]->Next() : rd[l] ? rd[l]->Next() : pos[l] < n_cached[l];
         if (more[l]) any[0] += 1;
       }
       const double ta = host_s ? Now() : 0;
@@ -690,26 +786,51 @@ Progress ShardedPass(ShardRunner* run, const Param& P, int epoch, int job_type, 
       std::vector<ShardRunner::Item> items(nlocal);
       for (int l = 0; l < nlocal; ++l) {
         if (!more[l]) continue;
-        if (rd[l])
+        if (drd[l]) {
+          items[l].dev = &drd[l]->Value();
+          items[l].feed = (*feeds)[l].get();
+          items[l].ticket = drd[l]->Ticket();
+        } else if (rd[l]) {
           items[l].host = &rd[l]->Value();
-        else
+        } else {
           items[l].replay = pos[l]++;
+        }
       }
       const double ts = host_s ? Now() : 0;
       run->Step(items, list, rec, job_type, train && epoch == 0, pred_files ? &preds : nullptr,
                 pred_files ? writers : nullptr);
       if (host_s) host_s[0] += Now() - ts;
       for (int l = 0; pred_files && !writers && l < nlocal; ++l) {
-        if (!items[l].host) continue;
-        WritePredRows((*pred_files)[l], items[l].host->label.data(), preds[l].data(),
-                      preds[l].size(), P.pred_prob);
+        if (!items[l].host && !items[l].dev) continue;
+        // (a feed's batch: the chunk's labels as the parse copied them back, until the next Next)
+        WritePredRows((*pred_files)[l],
+                      items[l].dev ? drd[l]->HostLabels() : items[l].host->label.data(),
+                      preds[l].data(), preds[l].size(), P.pred_prob);
       }
     }
     if (rec) run->SealList();
+    for (int l = 0; l < nlocal; ++l) {
+      if (!drd[l]) continue;
+      fallback += (double)drd[l]->FallbackChunks();
+      if (times) {
+        const DeviceBatchReader::Times t = drd[l]->TimesSpent();
+        times->copy += t.copy;
+        times->wait_text += t.wait_text;
+        times->wait_parse += t.wait_parse;
+        times->wait_step += t.wait_step;
+      }
+    }
   }
   run->Flush();
   if (writers)
     for (auto& w : *writers) w->Finish();
+  if (feeds) {  // every rank calls: the chunks the device handed back, over shards and ranks
+    std::vector<double> fb(1, fallback);
+    run->AllReduceSum(&fb);
+    if (fb[0] > 0 && run->rank(0) == 0)
+      std::printf("parse=device: %.0f chunk%s parsed by the host (needs_host)\n", fb[0],
+                  fb[0] == 1 ? "" : "s");
+  }
   std::vector<double> pr(3, 0.0);
   for (int l = 0; l < nlocal; ++l) {
     dfx_progress p;
@@ -752,6 +873,28 @@ int RunSharded(const Param& P, const KWArgs& rest) {
       }
     }
   }
+  // parse=auto-sharded: one text feed per local shard on the shard's context, for the whole run.
+  // Its loader stream is the context's input stream while it lives.  The feeds go before the
+  // runner, which owns the contexts, and after a flush: a queued step reads a feed's batch and
+  // its mark calls into the feed.
+  struct Feeds {
+    ShardRunner* run;
+    std::vector<std::unique_ptr<DeviceTextFeed>> v;
+    ~Feeds() {
+      if (v.empty()) return;
+      try {
+        run->Flush();
+      } catch (...) {
+      }
+      v.clear();
+    }
+  } feeds{run.get(), {}};
+  if (P.parse == "sharded-device")
+    for (int l = 0; l < nlocal; ++l)
+      feeds.v.emplace_back(new DeviceTextFeed(run->ctx(l), P.batch_size, P.batch_size * P.shuffle,
+                                              P.data_format, ShardRunner::kShardFeedDepth,
+                                              ShardRunner::kShardFeedDepth));
+  std::vector<std::unique_ptr<DeviceTextFeed>>* const fp = feeds.v.empty() ? nullptr : &feeds.v;
   const int kfirst = std::max(0, P.load_epoch > 0 ? P.load_epoch + 1 : 0);
   if (P.task == 2) {  // one pass over data_val; every worker saves its own rows (SavePred)
     std::vector<FILE*> files;
@@ -776,7 +919,7 @@ int RunSharded(const Param& P, const KWArgs& rest) {
     const double tp = Now();
     const Progress pr = ShardedPass(run.get(), P, kfirst, GpuSGDLearner::kPrediction, false,
                                     files.empty() ? nullptr : &files, nullptr,
-                                    writers.empty() ? nullptr : &writers);
+                                    writers.empty() ? nullptr : &writers, fp);
     const double pass_s = Now() - tp;
     for (FILE* f : files) std::fclose(f);
     if (rank == 0) std::printf("Prediction: %s\n", Text(pr).c_str());
@@ -802,8 +945,9 @@ int RunSharded(const Param& P, const KWArgs& rest) {
     const bool timed = run->has_cache() && P.exchange == "split";
     double host_s[2] = {0, 0};
     if (timed) (void)run->TakeThrottleSeconds();
+    DeviceBatchReader::Times rt;
     const Progress tr = ShardedPass(run.get(), P, k, GpuSGDLearner::kTraining, record, nullptr,
-                                    timed ? host_s : nullptr);
+                                    timed ? host_s : nullptr, nullptr, fp, &rt);
     const double dt = Now() - te;
     if (rank == 0)
       std::printf("Epoch[%d] Training: %s  (%.0f ex/s incl. parse+PCIe, %d shards%s, %.2f s)\n", k,
@@ -812,11 +956,18 @@ int RunSharded(const Param& P, const KWArgs& rest) {
       std::printf("  split: epoch %.3f s; the host spent %.3f s in Step (of it %.3f s waiting on "
                   "the store's run-ahead bound) and %.3f s in the per-step all-reduce\n",
                   dt, host_s[0], run->TakeThrottleSeconds(), host_s[1]);
+    // where this process's device readers' time went, summed over its shards (Times); an
+    // epoch that replayed every part from the cache made no reader and prints nothing
+    if (fp && rank == 0 && rt.copy + rt.wait_text + rt.wait_parse + rt.wait_step > 0)
+      std::printf("  reader: epoch %.3f s, host copy %.3f s (loader threads); the caller waited "
+                  "for text %.3f s, for the parse %.3f s, for a ring batch %.3f s\n",
+                  dt, rt.copy, rt.wait_text, rt.wait_parse, rt.wait_step);
     Progress va;
     if (!P.data_val.empty()) {
       // (the pass above flushed: the 1-step-stale schedule's last push is applied)
       const double tv = Now();
-      va = ShardedPass(run.get(), P, k, GpuSGDLearner::kValidation, record);
+      va = ShardedPass(run.get(), P, k, GpuSGDLearner::kValidation, record, nullptr, nullptr,
+                       nullptr, fp);
       if (rank == 0)
         std::printf("Epoch[%d] Validation: %s  (%.0f ex/s)\n", k, Text(va).c_str(),
                     va.nrows / (Now() - tv));
@@ -902,9 +1053,28 @@ int main(int argc, char** argv) {
   }
   const char* ws = std::getenv("WORLD_SIZE");
   const bool sharded = P.shards != 0 || (ws && std::atoi(ws) > 1);
-  if (P.parse != "host" && P.parse != "device" && P.parse != "auto") {
-    std::fprintf(stderr, "parse must be host, device or auto\n");
+  if (P.parse != "host" && P.parse != "device" && P.parse != "auto" &&
+      P.parse != "auto-sharded") {
+    std::fprintf(stderr, "parse must be host, device, auto or auto-sharded\n");
     return 2;
+  }
+  if (P.parse == "auto-sharded") {
+    if (!sharded) {
+      P.parse = "auto";  // the single-GPU run: parse=auto and its line, below
+    } else {  // the device parser in the sharded run too, where the format has one
+      const bool dev = P.data_format == "criteo" || P.data_format == "criteo_test" ||
+                       P.data_format == "libsvm";
+      const int nshards = P.shards > 0 ? P.shards : ws && std::atoi(ws) > 1 ? std::atoi(ws) : 1;
+      const char* rk = std::getenv("RANK");
+      if (!rk || std::atoi(rk) == 0) {  // rank 0 prints, as the cache's line
+        if (dev)
+          std::printf("parse: device (%s, %d shards)\n", P.data_format.c_str(), nshards);
+        else
+          std::printf("parse: host (data_format=%s)\n", P.data_format.c_str());
+        std::fflush(stdout);
+      }
+      P.parse = dev ? "sharded-device" : "host";
+    }
   }
   if (P.parse == "auto") {  // the device parser where there is one, and a line saying which
     bool fused = true;

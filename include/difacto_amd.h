@@ -262,6 +262,15 @@ int dfx_textfeed_gather(dfx_textfeed* f, int src, int to_batch, const uint32_t* 
 int dfx_textfeed_batch_end(dfx_textfeed* f, int64_t rows, int64_t nnz, int valued,
                            dfx_batch* out);
 int dfx_textfeed_consumed(dfx_textfeed* f);
+/* Late marking, for callers whose step is not queued when their call returns (the sharded
+ * stores run step t at submit t + 1 or at a flush): marks the ring entry begun `back`
+ * dfx_textfeed_batch_begin calls ago (0: the current one; back < nring), after the call that
+ * queued its last reader and before _batch_begin comes round to it.  A slot batch is marked late
+ * with dfx_textfeed_slot_consumed, which names its slot; the slot must not be filled or
+ * submitted again before.  dfx_textfeed_counts: the feed's slot and ring counts and the ring
+ * entry last begun (-1: none); any of the three may be NULL. */
+int dfx_textfeed_consumed_back(dfx_textfeed* f, int back);
+int dfx_textfeed_counts(dfx_textfeed* f, int* nslots, int* nring, int* cur);
 int dfx_textfeed_slot_batch(dfx_textfeed* f, int slot, int valued, dfx_batch* out);
 int dfx_textfeed_slot_consumed(dfx_textfeed* f, int slot);
 
