@@ -11,8 +11,10 @@
 //   owner   owner_begin   the received sub-rows of all workers, concatenated in rank order, go
 //           through the Localizer (sorted unique keys, occurrences in (worker, row, nnz) order =
 //           the concatenated batch's order); epoch 0: Update(kFeaCount) + ranked InitV
-//   owner   owner_forward per received row its partial [XV(d) | XXVV(d) | sum w x | 0 0 0] over
-//           the owner's keys (the fused forward, fm.hip, in partial mode)
+//   owner   owner_forward per received row its partial over the owner's keys, summed in the
+//           row's nnz order (the fused forward, fm.hip, in partial mode): N > 1 owners
+//           [XV(d) | sum w x | sum_l XXVV_l | 0 0], the XXVV sum serial over l from 0.0f; one
+//           owner [XV(d) | XXVV(d) | sum w x | 0 0 0] (split_part_floats)
 //   -> alltoallv partials back
 //   worker  combine       per row the owners' partials summed in rank order -> pred (clip), p,
 //           logloss, the AUC snapshot, and the row [XV*p (d) | p | 0 0 0] (fm_loss.h:67-203)
@@ -21,9 +23,15 @@
 //           rows' p and XV*p from the received records; ranked InitV
 // Per row that is ~40 keys + N partials + N records (~1.9 KB at d = 16, N = 8) instead of
 // ~5.8 KB, and each owner touches a key's entry and V once per step as the fused step does.
-// At N = 1 the partial is the whole row and the step equals the fused step bit for bit; at
-// N > 1 the forward's sums are regrouped by owner (within the 1e-5 tolerance), the gradients
-// are summed over the occurrences in the concatenated batch's order.
+// At N = 1 the partial is the whole row and the step equals the fused step bit for bit.  At
+// N > 1 the forward's sums are regrouped by owner, in a fixed order: the combine sums the owners'
+// sum w x, XV_l and sum_l XXVV_l from 0.0f in rank order, then s = sum_l XV_l^2 serially over l,
+// s -= the XXVV sum, pred = float(double(sum w x) + .5 double(s)), clipped; the gradients are
+// summed over the occurrences in the concatenated batch's (worker, row, nnz) order, long keys
+// through the chunk plan.  tests/split_ref.py restates that order in numpy and
+// tests/test_gpu_split_exact.py pins every lane layout to it bit for bit; against the unsharded
+// reference the regrouped predictions differ in their last bits on most rows and stay within
+// 1e-5 (tests/test_gpu_split.py).
 #include "fm_args.h"
 
 namespace dfx {

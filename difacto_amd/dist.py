@@ -729,12 +729,14 @@ SPLIT_PHASES = ("partition", "xchg_keys", "owner_begin", "owner_forward", "xchg_
 
 
 def split_step(shards, dblks, comm, job_type=kTraining, push_cnt=False, max_index=MAX_INDEX,
-               preds=None, mark=None):
+               preds=None, mark=None, keep=None):
     """One bulk-synchronous step of the owner-computes split (csrc/split.hip; oracle:
     AggOracle.step, the single reference updater on the concatenated batch).  Every worker is
     padded to M = the largest batch's rows with empty rows, so the row-sized collectives are
     equal-size: the partials an all-to-all of M rows per owner, the [XV*p | p] rows an
-    all-gather.  mark(i): called after phase SPLIT_PHASES[i] is issued (and with -1 first)."""
+    all-gather.  mark(i): called after phase SPLIT_PHASES[i] is issued (and with -1 first).
+    keep (a dict): receives the step's intermediates — parts (per owner, N workers x M rows of
+    partials), rparts (per worker, N owners x M rows), pxv (per worker, M rows) and M."""
     mark = mark or (lambda i: None)
     mark(-1)
     n = len(shards)
@@ -790,6 +792,8 @@ def split_step(shards, dblks, comm, job_type=kTraining, push_cnt=False, max_inde
     pxv = [shards[i].split_combine(dblks[i], rparts[i], M, 0, preds[i] if preds else None)
            for i in range(n)]
     mark(5)
+    if keep is not None:
+        keep.update(parts=parts, rparts=rparts, pxv=pxv, M=M)
     if job_type == kTraining:
         PX = _lib.lib().dfx_split_pxv_floats(shards[0].ctx.h)
         allp = comm.allgather_rows(pxv, M, PX)

@@ -135,10 +135,13 @@ def combine(parts, d):
 
 
 # ---- the backward --------------------------------------------------------------------------
-def backward(offs, col, val, label, rweight, W, wp, vp, U, d, pred, debug=False):
+def backward(offs, col, val, label, rweight, W, wp, vp, U, d, pred, debug=False, XVp=None,
+             p=None):
     """-> grad f32 in the layout of W (O.fm_calcgrad's arguments and result; grad starts at
     zero).  debug: -> (grad, dict) with the sorted terms and the long keys' double sums before
-    their rounding."""
+    their rounding.  XVp f32[B, d], p f32[B]: the rows' XV * p and p as given (the owner-computes
+    split's backward reads them from the workers' combined rows, tests/split_ref.py) instead of
+    this batch's own forward; pred, label and rweight are then unused."""
     offs = np.asarray(offs, np.int64)
     col = np.asarray(col, np.int64)
     W = np.asarray(W, f32)
@@ -146,7 +149,7 @@ def backward(offs, col, val, label, rweight, W, wp, vp, U, d, pred, debug=False)
     x = np.ones(nnz, f32) if val is None else np.asarray(val, f32)
     wp = np.arange(U, dtype=np.int64) if wp is None else np.asarray(wp, np.int64)
     vp = np.full(U, -1, np.int64) if (vp is None or d == 0) else np.asarray(vp, np.int64)
-    p = row_p(label, pred, rweight)
+    p = row_p(label, pred, rweight) if p is None else np.asarray(p, f32)
     row = np.repeat(np.arange(B), np.diff(offs))
     order = np.argsort(col, kind="stable")    # occurrence order: ascending (row, nnz) per key
     cnt = np.bincount(col, minlength=U).astype(np.int64)
@@ -157,7 +160,9 @@ def backward(offs, col, val, label, rweight, W, wp, vp, U, d, pred, debug=False)
     T = None
     if d > 0:
         with np.errstate(invalid="ignore", over="ignore"):
-            XVp = (xv_rows(offs, col, x, W, vp, d) * p[:, None]).astype(f32)
+            if XVp is None:
+                XVp = (xv_rows(offs, col, x, W, vp, d) * p[:, None]).astype(f32)
+            XVp = np.asarray(XVp, f32)
             T = v_terms(XVp, row[order], x[order])
     ar = np.arange(d)
     Vk = np.zeros((U, d), f32)
@@ -233,16 +238,24 @@ PLANTED = (897, 1024, 1, 8, 9, 127, 128, 129, 256, 257, 896, 1025, 4096) + \
     tuple(129 + (i % 7) for i in range(480)) + (4097,)
 
 
-def planted_key(i):
-    """the Localizer key (ReverseBytes of the id) of planted key i: ascending in i"""
-    return np.uint64((i + 1) << 24)
+def owner_base(o, owners):
+    """the first key of owner o's range of `owners` (floor(key * owners / 2^64) == o, csrc/split.hip
+    split_owner): ceil(o 2^64 / owners)"""
+    return -(-(int(o) << 64) // int(owners))
 
 
-def planted_batch(rows, per_row, counts, binary, seed, zero_weights=True):
+def planted_key(i, owners=1):
+    """the Localizer key (ReverseBytes of the id) of planted key i: ascending in i; owners > 1:
+    in owner (i % owners)'s key range, ascending in i within each owner"""
+    return np.uint64(((i + 1) << 24) + owner_base(i % owners, owners))
+
+
+def planted_batch(rows, per_row, counts, binary, seed, zero_weights=True, owners=1):
     """rows x per_row nnz; planted key i (planted_key(i)) occurs exactly counts[i] times, the
     other slots hold background keys of ~16 occurrences each; slots are shuffled, so a key's
     occurrences spread over the rows and repeat inside rows.  Row weights in (0.5, 1.5] with
-    every seventh 0.0 (both sides of p != 0)."""
+    every seventh 0.0 (both sides of p != 0).  owners > 1: planted key i and background key b lie
+    in the key ranges of owners i % owners and b % owners (planted_key)."""
     from difacto_amd import data as D
     from tests.localizer_ref import reverse_bytes
     rng = np.random.default_rng(seed)
@@ -253,6 +266,10 @@ def planted_batch(rows, per_row, counts, binary, seed, zero_weights=True):
     bg = rng.integers(0, nbg, n - len(planted)).astype(np.uint64)
     keys = np.concatenate([(planted + np.uint64(1)) << np.uint64(24),
                            (bg << np.uint64(1)) + np.uint64(1)])   # odd: never a planted key
+    if owners > 1:
+        base = np.array([owner_base(o, owners) for o in range(owners)], np.uint64)
+        who = np.concatenate([planted, bg]) % np.uint64(owners)
+        keys = keys + base[who.astype(np.int64)]
     keys = keys[rng.permutation(n)]
     offs = (np.arange(rows + 1) * per_row).astype(np.uint64)
     vals = None if binary else (1.0 - rng.random(n, dtype=np.float32)).astype(f32)

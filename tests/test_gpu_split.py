@@ -2,8 +2,12 @@
 against the single reference updater on the concatenated batch (one N-GPU step
 == one reference step, sgd_learner.cc:201-317, on the N batches in rank order), and at N = 1
 against the fused single-GPU step bit for bit.  N shards live on the one GPU and exchange
-through LoopbackComm.  Bars: predictions within 1e-5 relative (the forward's sums are regrouped
-by owner), loss 1e-5, model values 1e-5; keys, V rows, rand_r state and new_w exact."""
+through LoopbackComm.  Bars: predictions within 1e-5 relative, loss 1e-5, model values 1e-5; keys,
+V rows, rand_r state and new_w exact.  These are the semantic bars against the UNSHARDED
+reference: at N > 1 an owner's partial is [XV | sum w x | sum_l XXVV_l | 0 0] and the forward's
+sums are regrouped by owner (owners in rank order, then serially over l), so most rows differ
+from the reference's in their last bits.  The regrouped order itself is pinned bit for bit, on
+every lane layout and on chunked keys, by tests/test_gpu_split_exact.py against tests/split_ref.py."""
 import numpy as np
 import pytest
 import torch
