@@ -21,8 +21,8 @@ HOSTSRC = $(HOSTLIB) difacto_amd/host/dist_store.cc difacto_amd/host/split_learn
   tests/host/host_tests.cc
 HOSTHDR = difacto_amd/host/iface.h difacto_amd/host/gpu_adapters.h difacto_amd/host/reader.h \
   difacto_amd/host/dist_host.h difacto_amd/host/dist_store.h difacto_amd/host/split_learner.h \
-  difacto_amd/host/device_reader.h include/difacto_amd.h include/difacto_amd_dist.h $(CITYHDR) \
-  $(CSRC)/reshuffle.h
+  difacto_amd/host/device_reader.h difacto_amd/host/train_options.h include/difacto_amd.h \
+  include/difacto_amd_dist.h $(CITYHDR) $(CSRC)/reshuffle.h
 HOSTFLAGS = -std=c++14 -O2 -Wall -pthread
 
 READERBIN = build/reader_tests
@@ -39,7 +39,7 @@ DISTLIB = difacto_amd/libdfx_dist.so
 
 all: $(LIB) $(DISTLIB) oracle $(HOSTBIN) $(TRAINBIN) $(READERBIN) $(GENBIN) $(CONVBIN) $(RBENCH) \
   $(TPBIN) $(LSBIN) $(SEBIN) $(SDBIN) $(SPBIN) build/expf_check build/strtof_check build/gen_libsvm build/locbench \
-  build/reshuffle_check build/fmtg_check
+  build/reshuffle_check build/fmtg_check build/train_options_tests
 
 $(RBENCH): difacto_amd/host/reader.cc tools/reader_bench.cc difacto_amd/host/reader.h $(CITYHDR)
 	@mkdir -p build
@@ -60,6 +60,12 @@ $(READERBIN): difacto_amd/host/reader.cc tests/host/reader_tests.cc difacto_amd/
   difacto_amd/host/iface.h $(CITYHDR)
 	@mkdir -p build
 	g++ $(HOSTFLAGS) -o $@ difacto_amd/host/reader.cc tests/host/reader_tests.cc -ldl
+
+# dfx_train's option rules alone (CPU only, no library): ResolveOptions' truth table
+build/train_options_tests: tests/host/train_options_tests.cc difacto_amd/host/train_options.h \
+  difacto_amd/host/iface.h
+	@mkdir -p build
+	g++ $(HOSTFLAGS) -o $@ tests/host/train_options_tests.cc
 
 # the device text parser, the row gather and DeviceBatchReader against the host reader
 # (dfx_parse_criteo / dfx_gather_rows vs ParseCriteo / GatherRows / BatchReader), plus the CPU

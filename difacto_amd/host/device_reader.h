@@ -144,6 +144,13 @@ class DeviceBatchReader {
    * parse (upload + parse kernels), on a ring batch being consumed (the step) */
   struct Times {
     double copy = 0, wait_text = 0, wait_parse = 0, wait_step = 0;
+    Times& operator+=(const Times& t) {
+      copy += t.copy;
+      wait_text += t.wait_text;
+      wait_parse += t.wait_parse;
+      wait_step += t.wait_step;
+      return *this;
+    }
   };
   Times TimesSpent() const { return times_; }
 

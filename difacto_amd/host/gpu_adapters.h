@@ -304,6 +304,13 @@ class DevicePredWriter {
   struct Stats {
     int64_t rows = 0, batches = 0, host_batches = 0;  // host_batches: written by WritePredRows
     double wait_s = 0;                                // the host waited for text
+    Stats& operator+=(const Stats& s) {  // over a process's shards
+      rows += s.rows;
+      batches += s.batches;
+      host_batches += s.host_batches;
+      wait_s += s.wait_s;
+      return *this;
+    }
   };
   Stats GetStats() const { return stats_; }
 

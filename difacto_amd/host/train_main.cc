@@ -12,6 +12,10 @@
 //                   [pred_write=host|device]
 //                   [V_dim=..] [lr=..] [l1=..] ... (SGDUpdaterParam)
 //
+// What each option does is described below.  The rules themselves — which combinations are
+// refused, with which message and in which order, and the "parse:" / "cache:" lines — are one
+// function, ResolveOptions in train_options.h; the code here reads the RunPlan it fills.
+//
 // parse=device (data_format=criteo|criteo_test, the single-GPU fused path: training, data_val
 // validation and task=2 prediction): the raw text is copied to pinned memory and uploaded, the
 // device parses it (dfx_parse_criteo) and forms the batches (DeviceBatchReader,
@@ -143,8 +147,6 @@
 #include <chrono>
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <vector>
 #include <string>
 
@@ -154,32 +156,11 @@
 #include "gpu_adapters.h"
 #include "reader.h"
 #include "split_learner.h"
+#include "train_options.h"
 
 using namespace difacto;
 
 namespace {
-struct Param {
-  std::string data_in, data_val, data_format = "libsvm", model_in, model_out, pred_out;
-  size_t batch_size = 100, shuffle = 10;
-  float neg_sampling = 1.f;
-  int max_num_epochs = 20, num_jobs_per_epoch = 10, nthreads = 8;
-  int load_epoch = -1, task = 0;
-  int shards = 0;  // > 0: that many loopback shards in this process; -1: one shard, RCCL
-  int model_in_parts = 0;  // servers that saved model_in, when not this run's shard count
-  bool pipelined = true;
-  std::string exchange = "a2a";  // a2a: GpuShardedStore (KVStoreDist); split: GpuSplitLearner
-  bool has_aux = false, pred_prob = true;
-  double stop_rel_objv = 1e-5;
-  double stop_val_auc = 1e-5;  // sgd_param.h:73
-  std::string parse = "host";  // device: DeviceBatchReader (text parsed on the GPU); auto
-  std::string cache = "none";  // device: formed batches kept in HBM, replayed after the first epoch
-  int64_t cache_mb = 16384;    // its budget (per shard)
-  bool cache_loc = false;      // the Localizer's outputs kept with the cached batches too
-  bool epoch_shuffle = false;  // replayed training parts are reshuffled on the device per epoch
-  uint64_t shuffle_seed = 0;   // ... keyed by (shuffle_seed, epoch, list)
-  std::string pred_write = "host";  // device: prediction rows formatted on the GPU
-};
-
 // sgd_learner.h:65-69
 std::string ModelNamePart(const std::string& prefix, int iter, int rank) {
   std::string name = prefix;
@@ -219,134 +200,199 @@ int64_t CacheList(const Param& P, bool train, int part) {
   return (int64_t)(train ? 0 : 1) * P.num_jobs_per_epoch + part;
 }
 
-// cache (optional): record = the recording pass, every batch is also appended to its part's
-// list (the step still takes the original batch); else a part whose list was sealed is replayed
-// from the cache with no reader, any other part is read as without the cache
 // after the recording epoch: what the batch cache holds (a sharded run: summed over the shards)
 void PrintCacheLine(double batches, double bytes, double dropped, double parts) {
   std::printf("cache=device: %.0f batches, %.1f MB held, %.0f of %.0f parts not cached\n", batches,
               bytes / (1 << 20), dropped, parts);
 }
 
-Progress RunEpoch(GpuSGDLearner* learner, const Param& P, int epoch, int job_type,
-                  FILE* pred_file = nullptr, DeviceTextFeed* feed = nullptr,
-                  DeviceBatchReader::Times* times = nullptr, double* step_s = nullptr,
-                  DeviceBatchCache* cache = nullptr, bool record = false,
-                  std::vector<std::unique_ptr<DeviceReshuffler>>* resh = nullptr,
-                  double* shuffle_wait = nullptr, DevicePredWriter* dev_writer = nullptr) {
+// stop criteria (sgd_learner.cc:89-108) on an epoch's sums: the training loss's relative change,
+// then the validation AUC's gain; an epoch that does not stop becomes the next one's "pre"
+bool ShouldStop(const Progress& tr, const Progress& va, double* pre_loss, double* pre_val_auc,
+                const Param& P, bool say) {
+  double eps = std::fabs(tr.loss - *pre_loss) / *pre_loss;
+  if (eps < P.stop_rel_objv) {
+    if (say) std::printf("Change of loss [%g] < stop_rel_objv [%g]\n", eps, P.stop_rel_objv);
+    return true;
+  }
+  if (va.auc > 0) {
+    eps = (va.auc - *pre_val_auc) / va.nrows;
+    if (eps < P.stop_val_auc) return true;
+  }
+  *pre_loss = tr.loss;
+  *pre_val_auc = va.auc;
+  return false;
+}
+
+// a part's device reader: training forms minibatches out of 64 MB chunks, shuffled and
+// down-sampled; validation and prediction take whole 256 MB chunks, one batch per chunk
+std::unique_ptr<DeviceBatchReader> MakeDeviceReader(const Param& P, DeviceTextFeed* feed,
+                                                    bool train, int part, int nparts) {
+  return std::unique_ptr<DeviceBatchReader>(new DeviceBatchReader(
+      feed, train ? P.data_in : P.data_val, P.data_format, part, nparts, train ? P.batch_size : 0,
+      train ? P.batch_size * P.shuffle : 0, train ? P.neg_sampling : 1.f, P.nthreads,
+      train ? (size_t)64 << 20 : (size_t)256 << 20));
+}
+
+// what a RunEpoch pass may use (null: not in this run) and what it reports (accumulated)
+struct PassIO {
+  DeviceTextFeed* feed = nullptr;  // parse=device: the parts are read by a DeviceBatchReader
+  // record: the recording pass, every batch is also appended to its part's list (the step still
+  // takes the original batch); else a part whose list was sealed is replayed from the cache
+  // with no reader, any other part is read as without the cache
+  DeviceBatchCache* cache = nullptr;
+  bool record = false;
+  std::vector<std::unique_ptr<DeviceReshuffler>>* resh = nullptr;  // epoch_shuffle=1: per part
+  FILE* pred_file = nullptr;               // prediction: the rows, written by the host loop
+  DevicePredWriter* dev_writer = nullptr;  // ... or from text the device formatted
+  DeviceBatchReader::Times times;          // the device readers'
+  double step_s[2] = {0, 0};        // inside dfx_train_step calls; the parts' final joins
+  double shuffle_wait[2] = {0, 0};  // the host's wait for the batches' sizes; parts reshuffled
+};
+
+// one RunEpoch call, as the four sources of a part's batches see it
+struct Pass {
+  GpuSGDLearner* learner;
+  const Param& P;
+  const RunPlan& plan;
+  int job_type;
+  bool train, push_cnt;
+  PassIO* io;
+  std::vector<real_t> pred;  // a batch's predictions, where the host loop writes them
+  size_t fallback = 0;       // chunks the device handed back to the host parser
+  std::vector<real_t>* host_pred() { return io->pred_file && !io->dev_writer ? &pred : nullptr; }
+};
+
+// epoch_shuffle=1: the part's rows in this epoch's order, gathered out of the cached batches
+void StepReshuffled(Pass* s, DeviceReshuffler* rs) {
+  dfx_batch b;
+  while (rs->Next(&b)) {
+    const double ts = Now();
+    s->learner->ProcessDeviceBatch(b, s->job_type, s->push_cnt);
+    rs->Consumed();
+    s->io->step_s[0] += Now() - ts;
+  }
+  s->io->shuffle_wait[1] += 1;
+}
+
+// a sealed list's n batches as they were recorded (cache_loc=1: with their Localizer outputs)
+void StepReplayed(Pass* s, int64_t list, int64_t n) {
+  DeviceBatchCache* cache = s->io->cache;
+  for (int64_t i = 0; i < n; ++i) {
+    const dfx_batch b = cache->Get(list, i);
+    dfx_loc loc;
+    if (s->plan.cache_loc) loc = cache->GetLoc(list, i);
+    const double ts = Now();
+    s->learner->ProcessDeviceBatch(b, s->job_type, s->push_cnt, nullptr,
+                                   s->plan.cache_loc ? &loc : nullptr);
+    s->io->step_s[0] += Now() - ts;
+  }
+}
+
+// parse=device: the same parts, chunks and batches, formed on the device
+void StepDeviceReader(Pass* s, int part, bool rec) {
+  PassIO& io = *s->io;
+  const auto reader = MakeDeviceReader(s->P, io.feed, s->train, part, s->P.num_jobs_per_epoch);
+  while (reader->Next()) {
+    const dfx_batch& b = reader->Value();
+    if (rec) io.cache->Append(b);
+    const double ts = Now();
+    const float* dpred = nullptr;
+    s->learner->ProcessDeviceBatch(b, s->job_type, s->push_cnt, s->host_pred(), nullptr,
+                                   io.dev_writer ? &dpred : nullptr);
+    // (before Consumed: the ring entry's labels are read behind the step)
+    if (io.dev_writer) io.dev_writer->Submit(b.label, dpred, b.size);
+    reader->Consumed();
+    io.step_s[0] += Now() - ts;
+    if (rec && s->plan.cache_loc) io.cache->AppendLoc();
+    if (s->host_pred())
+      WritePredRows(io.pred_file, reader->HostLabels(), s->pred.data(), s->pred.size(),
+                    s->P.pred_prob);
+  }
+  s->fallback += reader->FallbackChunks();
+  io.times += reader->TimesSpent();
+}
+
+// the host readers behind the pinned-staging feeder
+void StepHostReader(Pass* s, int part, bool rec) {
+  const Param& P = s->P;
+  PassIO& io = *s->io;
+  const bool rec_loc = rec && s->plan.cache_loc;  // each step's Localizer outputs with its batch
+  if (s->train) {
+    // sgd_learner.cc:273-280
+    ThreadedBatchReader reader(P.data_in, P.data_format, part, P.num_jobs_per_epoch, P.batch_size,
+                               P.batch_size * P.shuffle, P.neg_sampling, P.nthreads);
+    while (reader.Next()) {
+      const auto blk = reader.Value().GetBlock();
+      dfx_batch db;
+      s->learner->ProcessBatch(blk, s->job_type, s->push_cnt, nullptr, rec ? &db : nullptr);
+      if (rec) io.cache->Append(db);
+      if (rec_loc) io.cache->AppendLoc();
+    }
+    return;
+  }
+  // sgd_learner.cc:281-286: validation reads whole 256 MB chunks as one batch
+  TextReader reader(P.data_val, P.data_format, part, P.num_jobs_per_epoch, 256 << 20, P.nthreads);
+  while (reader.Next()) {
+    const auto& v = reader.Value();
+    if (v.Size() == 0) continue;
+    dfx_batch db;
+    const float* dpred = nullptr;
+    s->learner->ProcessBatch(v.GetBlock(), s->job_type, false, s->host_pred(),
+                             rec || io.dev_writer ? &db : nullptr,
+                             io.dev_writer ? &dpred : nullptr);
+    if (rec) io.cache->Append(db);
+    if (rec_loc) io.cache->AppendLoc();
+    // (the feeder's slot of this batch is uploaded into again two batches on; the writer is
+    // done reading a batch when the next Submit returns)
+    if (io.dev_writer) io.dev_writer->Submit(db.label, dpred, db.size);
+    if (s->host_pred())
+      WritePredRows(io.pred_file, v.label.data(), s->pred.data(), s->pred.size(), P.pred_prob);
+  }
+}
+
+Progress RunEpoch(GpuSGDLearner* learner, const Param& P, const RunPlan& plan, int epoch,
+                  int job_type, PassIO* io) {
   Progress prog;
-  std::vector<real_t> pred;
   const bool train = job_type == GpuSGDLearner::kTraining;
-  const std::string& path = train ? P.data_in : P.data_val;
-  size_t fallback = 0;
+  Pass s{learner, P, plan, job_type, train, train && epoch == 0, io, {}, 0};
   for (int part = 0; part < P.num_jobs_per_epoch; ++part) {
     const int64_t list = CacheList(P, train, part);
-    const bool rec = cache && record;
-    const bool rec_loc = rec && P.cache_loc;  // each step's Localizer outputs with its batch
-    const int64_t n_cached = cache && !record ? cache->Count(list) : -1;
-    if (rec) cache->Begin(list);
+    const bool rec = io->cache && io->record;
+    const int64_t n_cached = io->cache && !io->record ? io->cache->Count(list) : -1;
+    if (rec) io->cache->Begin(list);
     // epoch_shuffle=1: the part's rows in this epoch's order; -1: its ring no longer fits
-    DeviceReshuffler* rs = train && n_cached >= 0 && resh && (*resh)[part] ? (*resh)[part].get()
-                                                                          : nullptr;
+    DeviceReshuffler* rs = train && n_cached >= 0 && io->resh && (*io->resh)[part]
+                               ? (*io->resh)[part].get()
+                               : nullptr;
     int64_t n_shuffled = -1;
     if (rs) {
       const double tb = Now();
       n_shuffled = rs->BeginEpoch(rs_epoch_key(P.shuffle_seed, (uint64_t)epoch, (uint64_t)list));
-      if (shuffle_wait) shuffle_wait[0] += Now() - tb;
+      io->shuffle_wait[0] += Now() - tb;
     }
-    if (n_shuffled >= 0) {
-      dfx_batch b;
-      while (rs->Next(&b)) {
-        const double ts = Now();
-        learner->ProcessDeviceBatch(b, job_type, train && epoch == 0);
-        rs->Consumed();
-        if (step_s) step_s[0] += Now() - ts;
-      }
-      if (shuffle_wait) shuffle_wait[1] += 1;
-    } else if (n_cached >= 0) {
-      for (int64_t i = 0; i < n_cached; ++i) {
-        const dfx_batch b = cache->Get(list, i);
-        dfx_loc loc;
-        if (P.cache_loc) loc = cache->GetLoc(list, i);
-        const double ts = Now();
-        learner->ProcessDeviceBatch(b, job_type, train && epoch == 0, nullptr,
-                                    P.cache_loc ? &loc : nullptr);
-        if (step_s) step_s[0] += Now() - ts;
-      }
-    } else if (feed) {
-      // parse=device: the same parts, chunks and batches, formed on the device
-      DeviceBatchReader reader(feed, path, P.data_format, part, P.num_jobs_per_epoch,
-                               train ? P.batch_size : 0, train ? P.batch_size * P.shuffle : 0,
-                               train ? P.neg_sampling : 1.f, P.nthreads,
-                               train ? (size_t)64 << 20 : (size_t)256 << 20);
-      while (reader.Next()) {
-        const dfx_batch& b = reader.Value();
-        if (rec) cache->Append(b);
-        const double ts = Now();
-        const float* dpred = nullptr;
-        learner->ProcessDeviceBatch(b, job_type, train && epoch == 0,
-                                    pred_file && !dev_writer ? &pred : nullptr, nullptr,
-                                    dev_writer ? &dpred : nullptr);
-        // (before Consumed: the ring entry's labels are read behind the step)
-        if (dev_writer) dev_writer->Submit(b.label, dpred, b.size);
-        reader.Consumed();
-        if (step_s) step_s[0] += Now() - ts;
-        if (rec_loc) cache->AppendLoc();
-        if (pred_file && !dev_writer)
-          WritePredRows(pred_file, reader.HostLabels(), pred.data(), pred.size(), P.pred_prob);
-      }
-      fallback += reader.FallbackChunks();
-      if (times) {
-        const DeviceBatchReader::Times t = reader.TimesSpent();
-        times->copy += t.copy;
-        times->wait_text += t.wait_text;
-        times->wait_parse += t.wait_parse;
-        times->wait_step += t.wait_step;
-      }
-    } else if (train) {
-      // sgd_learner.cc:273-280
-      ThreadedBatchReader reader(path, P.data_format, part, P.num_jobs_per_epoch, P.batch_size,
-                                 P.batch_size * P.shuffle, P.neg_sampling, P.nthreads);
-      while (reader.Next()) {
-        const auto blk = reader.Value().GetBlock();
-        dfx_batch db;
-        learner->ProcessBatch(blk, job_type, epoch == 0, nullptr, rec ? &db : nullptr);
-        if (rec) cache->Append(db);
-        if (rec_loc) cache->AppendLoc();
-      }
-    } else {
-      // sgd_learner.cc:281-286: validation reads whole 256 MB chunks as one batch
-      TextReader reader(path, P.data_format, part, P.num_jobs_per_epoch, 256 << 20, P.nthreads);
-      while (reader.Next()) {
-        const auto& v = reader.Value();
-        if (v.Size() == 0) continue;
-        dfx_batch db;
-        const float* dpred = nullptr;
-        learner->ProcessBatch(v.GetBlock(), job_type, false,
-                              pred_file && !dev_writer ? &pred : nullptr,
-                              rec || dev_writer ? &db : nullptr, dev_writer ? &dpred : nullptr);
-        if (rec) cache->Append(db);
-        if (rec_loc) cache->AppendLoc();
-        // (the feeder's slot of this batch is uploaded into again two batches on; the writer is
-        // done reading a batch when the next Submit returns)
-        if (dev_writer) dev_writer->Submit(db.label, dpred, db.size);
-        if (pred_file && !dev_writer)
-          WritePredRows(pred_file, v.label.data(), pred.data(), pred.size(), P.pred_prob);
-      }
-    }
-    if (rec) cache->Seal();
+    if (n_shuffled >= 0)
+      StepReshuffled(&s, rs);
+    else if (n_cached >= 0)
+      StepReplayed(&s, list, n_cached);
+    else if (io->feed)
+      StepDeviceReader(&s, part, rec);
+    else
+      StepHostReader(&s, part, rec);
+    if (rec) io->cache->Seal();
     const double tj = Now();
     const Progress p = learner->TakeProgress();
-    if (step_s) step_s[1] += Now() - tj;
+    io->step_s[1] += Now() - tj;
     prog.nrows += p.nrows;
     prog.loss += p.loss;
     prog.auc += p.auc;
   }
-  if (fallback)
-    std::printf("parse=device: %zu chunk%s parsed by the host (needs_host)\n", fallback,
-                fallback == 1 ? "" : "s");
+  if (s.fallback)
+    std::printf("parse=device: %zu chunk%s parsed by the host (needs_host)\n", s.fallback,
+                s.fallback == 1 ? "" : "s");
   return prog;
 }
+
 // ---- the sharded store ----------------------------------------------------------------------
 // a batch in device memory, uploaded on the context's stream (three per shard in flight)
 struct DevBatch {
@@ -442,50 +488,57 @@ class ShardRunner {
                     std::vector<std::unique_ptr<DevicePredWriter>>* writers = nullptr) = 0;
   /** run what is queued and apply the last push */
   virtual void Flush() = 0;
-  // the batch cache (cache=device, cache=auto): a sealed list's batches of local shard
-  // l, -1 when the part has to be read; the recording pass's list brackets; the shards' sums
-  virtual bool has_cache() const { return false; }
-  virtual int64_t Cached(int, int64_t) { return -1; }
-  virtual void BeginList(int64_t) {}
-  virtual void SealList() {}
-  virtual void CacheSums(std::vector<double>* cs) { cs->assign(4, 0.0); }
   /** host seconds the store made the submitting thread wait on its run-ahead bound */
   virtual double TakeThrottleSeconds() { return 0; }
+  // the batch cache (cache=device, cache=auto): a sealed list's batches of local shard
+  // l, -1 when the part has to be read; the recording pass's list brackets; the shards' sums
+  bool has_cache() const { return !caches_.empty(); }
+  int64_t Cached(int l, int64_t list) { return caches_[l]->Count(list); }
+  void BeginList(int64_t list) {
+    for (auto& c : caches_) c->Begin(list);
+  }
+  void SealList() {
+    for (auto& c : caches_) c->Seal();
+  }
+  void CacheSums(std::vector<double>* cs) {
+    cs->assign(4, 0.0);
+    for (auto& c : caches_) {
+      const DeviceBatchCache::Stats s = c->GetStats();
+      (*cs)[0] += (double)s.batches;
+      (*cs)[1] += (double)s.bytes;
+      (*cs)[2] += (double)s.dropped;
+      (*cs)[3] += (double)(s.sealed + s.dropped);
+    }
+  }
+
+ protected:
+  // each local shard's batch cache on its own context, recorded in the first epoch this run
+  // executes.  A runner calls it once its contexts exist, and clears caches_ before they go.
+  void MakeCaches(const RunPlan& plan, int64_t bytes) {
+    for (int l = 0; plan.cache && l < nlocal(); ++l)
+      caches_.emplace_back(new DeviceBatchCache(ctx(l), bytes));
+  }
+  std::vector<std::unique_ptr<DeviceBatchCache>> caches_;
 };
 
 class A2aRunner : public ShardRunner {
  public:
-  A2aRunner(const Param& P, const KWArgs& rest) : pipelined_(P.pipelined) {
-    const char* ws = std::getenv("WORLD_SIZE");
-    const int world = ws ? std::atoi(ws) : 1;
-    const bool rccl = world > 1 || P.shards < 0;
-    const int rank = rccl && std::getenv("RANK") ? std::atoi(std::getenv("RANK")) : 0;
-    const int local = std::getenv("LOCAL_RANK") ? std::atoi(std::getenv("LOCAL_RANK")) : 0;
-    const int nlocal = rccl ? 1 : P.shards;
+  A2aRunner(const Param& P, const KWArgs& rest, const LaunchEnv& env, const RunPlan& plan)
+      : pipelined_(P.pipelined) {
+    const int nlocal = plan.rccl ? 1 : P.shards;
     ctxs_.assign(nlocal, nullptr);
     const std::string kw = KwString(rest);
     for (int l = 0; l < nlocal; ++l)
-      DfxCheck(dfx_ctx_create(rccl ? local : 0, kw.c_str(), &ctxs_[l]), "dfx_ctx_create");
-    if (rccl) {
-      std::string id_file;
-      if (const char* f = std::getenv("DFX_COMM_ID_FILE")) {
-        id_file = f;
-      } else {
-        const char* port = std::getenv("MASTER_PORT");
-        id_file = std::string("/tmp/dfx_comm_") + (port ? port : "0");
-      }
-      ex_ = MakeRcclExchange(ctxs_[0], rank, world, id_file);
-    } else {
+      DfxCheck(dfx_ctx_create(plan.rccl ? env.local_rank : 0, kw.c_str(), &ctxs_[l]),
+               "dfx_ctx_create");
+    if (plan.rccl)
+      ex_ = MakeRcclExchange(ctxs_[0], env.rank, env.world, env.comm_id_file);
+    else
       ex_ = MakeLoopbackExchange(ctxs_);
-    }
     store_.reset(new GpuShardedStore(ex_.get(), P.pipelined));
     dev_.resize(nlocal);
     for (auto& v : dev_) v.resize(3);
-    // cache=device: each local shard's batch cache on its own context, recorded in the first
-    // epoch this run executes (task=2 is one pass: nothing to replay)
-    if (P.cache == "device" && P.task != 2)
-      for (int l = 0; l < nlocal; ++l)
-        caches_.emplace_back(new DeviceBatchCache(ctxs_[l], P.cache_mb << 20));
+    MakeCaches(plan, P.cache_mb << 20);
   }
   ~A2aRunner() override {
     store_.reset();  // flushes and joins the contexts
@@ -565,24 +618,6 @@ class A2aRunner : public ShardRunner {
     store_->Flush();
     MarkAll(&queued_marks_);  // the queued step ran
   }
-  bool has_cache() const override { return !caches_.empty(); }
-  int64_t Cached(int l, int64_t list) override { return caches_[l]->Count(list); }
-  void BeginList(int64_t list) override {
-    for (auto& c : caches_) c->Begin(list);
-  }
-  void SealList() override {
-    for (auto& c : caches_) c->Seal();
-  }
-  void CacheSums(std::vector<double>* cs) override {
-    cs->assign(4, 0.0);
-    for (auto& c : caches_) {
-      const DeviceBatchCache::Stats s = c->GetStats();
-      (*cs)[0] += (double)s.batches;
-      (*cs)[1] += (double)s.bytes;
-      (*cs)[2] += (double)s.dropped;
-      (*cs)[3] += (double)(s.sealed + s.dropped);
-    }
-  }
 
  private:
   const bool pipelined_;
@@ -591,25 +626,18 @@ class A2aRunner : public ShardRunner {
   std::unique_ptr<ShardExchange> ex_;
   std::unique_ptr<GpuShardedStore> store_;
   std::vector<std::vector<DevBatch>> dev_;
-  std::vector<std::unique_ptr<DeviceBatchCache>> caches_;
   std::vector<std::unique_ptr<DevArray<float>>> dpred_;
   int ring_ = 0;
 };
 
 class SplitRunner : public ShardRunner {
  public:
-  SplitRunner(const Param& P, const KWArgs& rest) {
-    const char* ws = std::getenv("WORLD_SIZE");
-    const int world = ws ? std::atoi(ws) : 1;
-    const bool rccl = world > 1 || P.shards < 0;
+  SplitRunner(const Param& P, const KWArgs& rest, const RunPlan& plan) {
     KWArgs kw = rest;
     kw.push_back({"pipelined", P.pipelined ? "1" : "0"});
-    sl_ = rccl ? GpuSplitLearner::CreateRccl(kw) : GpuSplitLearner::CreateLoopback(P.shards, kw);
-    // the device cache (cache=auto): each local shard's batch cache on its own context, recorded
-    // in the first epoch this run executes (task=2 is one pass: nothing to replay)
-    if (P.cache == "device" && P.task != 2)
-      for (int l = 0; l < sl_->nlocal(); ++l)
-        caches_.emplace_back(new DeviceBatchCache(sl_->shard(l), P.cache_mb << 20));
+    sl_ = plan.rccl ? GpuSplitLearner::CreateRccl(kw)
+                    : GpuSplitLearner::CreateLoopback(P.shards, kw);
+    MakeCaches(plan, P.cache_mb << 20);
   }
   ~SplitRunner() override {
     // no queued step reads a cached batch any more; the caches go before the contexts, which
@@ -677,29 +705,10 @@ class SplitRunner : public ShardRunner {
       if (items[l].host) caches_[l]->Append(up[l]);
   }
   void Flush() override { sl_->Flush(); }
-  bool has_cache() const override { return !caches_.empty(); }
-  int64_t Cached(int l, int64_t list) override { return caches_[l]->Count(list); }
-  void BeginList(int64_t list) override {
-    for (auto& c : caches_) c->Begin(list);
-  }
-  void SealList() override {
-    for (auto& c : caches_) c->Seal();
-  }
-  void CacheSums(std::vector<double>* cs) override {
-    cs->assign(4, 0.0);
-    for (auto& c : caches_) {
-      const DeviceBatchCache::Stats s = c->GetStats();
-      (*cs)[0] += (double)s.batches;
-      (*cs)[1] += (double)s.bytes;
-      (*cs)[2] += (double)s.dropped;
-      (*cs)[3] += (double)(s.sealed + s.dropped);
-    }
-  }
   double TakeThrottleSeconds() override { return sl_->TakeThrottleSeconds(); }
 
  private:
   std::shared_ptr<GpuSplitLearner> sl_;
-  std::vector<std::unique_ptr<DeviceBatchCache>> caches_;
 };
 
 // a part's batches: training reads minibatches (sgd_learner.cc:273-280), validation and
@@ -736,17 +745,24 @@ class PartReader {
 // (or replays the batches it cached for it), the shards step together (an exhausted shard
 // gives empty batches until the all-reduced "any shard still has a batch" is 0), then the
 // store is flushed and the progress summed over every shard of every rank.
-// pred_files (prediction): local shard l's rows go to pred_files[l] in the order read.
-// host_s (optional): += the host seconds inside Step and inside the per-step all-reduce.
-// feeds (parse=auto-sharded): local shard l's parts are read by a DeviceBatchReader on
-// (*feeds)[l] instead of a PartReader: the same parts, chunks and batches, formed on the device.
-// A reader lives for one job; the batches it handed out may be marked after it is gone (the
-// feed keeps that state).  times (optional): += the device readers' Times.
+struct ShardIO {  // what a pass may use (null: not in this run) and what it reports (accumulated)
+  // prediction: local shard l's rows go to (*pred_files)[l] in the order read, through
+  // (*writers)[l] with pred_write=device
+  const std::vector<FILE*>* pred_files = nullptr;
+  std::vector<std::unique_ptr<DevicePredWriter>>* writers = nullptr;
+  // parse=auto-sharded: local shard l's parts are read by a DeviceBatchReader on (*feeds)[l]
+  // instead of a PartReader: the same parts, chunks and batches, formed on the device.  A
+  // reader lives for one job; the batches it handed out may be marked after it is gone (the
+  // feed keeps that state).
+  std::vector<std::unique_ptr<DeviceTextFeed>>* feeds = nullptr;
+  double host_s[2] = {0, 0};  // host seconds inside Step; inside the per-step all-reduce
+  DeviceBatchReader::Times times;  // the device readers'
+};
 Progress ShardedPass(ShardRunner* run, const Param& P, int epoch, int job_type, bool record,
-                     const std::vector<FILE*>* pred_files = nullptr, double* host_s = nullptr,
-                     std::vector<std::unique_ptr<DevicePredWriter>>* writers = nullptr,
-                     std::vector<std::unique_ptr<DeviceTextFeed>>* feeds = nullptr,
-                     DeviceBatchReader::Times* times = nullptr) {
+                     ShardIO* io) {
+  const std::vector<FILE*>* const pred_files = io->pred_files;
+  const auto writers = io->writers;
+  const auto feeds = io->feeds;
   const int nlocal = run->nlocal(), nshards = run->nranks();
   const bool train = job_type == GpuSGDLearner::kTraining;
   const int nparts = P.num_jobs_per_epoch * nshards;
@@ -762,11 +778,8 @@ Progress ShardedPass(ShardRunner* run, const Param& P, int epoch, int job_type, 
       if (run->has_cache() && !record) n_cached[l] = run->Cached(l, list);
       if (n_cached[l] >= 0) continue;
       const int part = job * nshards + run->rank(l);
-      if (feeds)  // training: minibatches out of 64 MB chunks; else whole 256 MB chunks (RunEpoch)
-        drd[l].reset(new DeviceBatchReader(
-            (*feeds)[l].get(), train ? P.data_in : P.data_val, P.data_format, part, nparts,
-            train ? P.batch_size : 0, train ? P.batch_size * P.shuffle : 0,
-            train ? P.neg_sampling : 1.f, P.nthreads, train ? (size_t)64 << 20 : (size_t)256 << 20));
+      if (feeds)
+        drd[l] = MakeDeviceReader(P, (*feeds)[l].get(), train, part, nparts);
       else
         rd[l].reset(new PartReader(P, train, part, nparts));
     }
@@ -779,9 +792,9 @@ Progress ShardedPass(ShardRunner* run, const Param& P, int epoch, int job_type, 
           more[l] = drd[l] ? drd[l]->Next() : rd[l] ? rd[l]->Next() : pos[l] < n_cached[l];
         if (more[l]) any[0] += 1;
       }
-      const double ta = host_s ? Now() : 0;
+      const double ta = Now();
       run->AllReduceSum(&any);
-      if (host_s) host_s[1] += Now() - ta;
+      io->host_s[1] += Now() - ta;
       if (any[0] == 0) break;
       std::vector<ShardRunner::Item> items(nlocal);
       for (int l = 0; l < nlocal; ++l) {
@@ -796,10 +809,10 @@ Progress ShardedPass(ShardRunner* run, const Param& P, int epoch, int job_type, 
           items[l].replay = pos[l]++;
         }
       }
-      const double ts = host_s ? Now() : 0;
+      const double ts = Now();
       run->Step(items, list, rec, job_type, train && epoch == 0, pred_files ? &preds : nullptr,
                 pred_files ? writers : nullptr);
-      if (host_s) host_s[0] += Now() - ts;
+      io->host_s[0] += Now() - ts;
       for (int l = 0; pred_files && !writers && l < nlocal; ++l) {
         if (!items[l].host && !items[l].dev) continue;
         // (a feed's batch: the chunk's labels as the parse copied them back, until the next Next)
@@ -812,13 +825,7 @@ Progress ShardedPass(ShardRunner* run, const Param& P, int epoch, int job_type, 
     for (int l = 0; l < nlocal; ++l) {
       if (!drd[l]) continue;
       fallback += (double)drd[l]->FallbackChunks();
-      if (times) {
-        const DeviceBatchReader::Times t = drd[l]->TimesSpent();
-        times->copy += t.copy;
-        times->wait_text += t.wait_text;
-        times->wait_parse += t.wait_parse;
-        times->wait_step += t.wait_step;
-      }
+      io->times += drd[l]->TimesSpent();
     }
   }
   run->Flush();
@@ -848,16 +855,12 @@ Progress ShardedPass(ShardRunner* run, const Param& P, int epoch, int job_type, 
 }
 
 // the sharded runs: training (with data_val: a validation pass after every epoch) and task=2
-int RunSharded(const Param& P, const KWArgs& rest) {
-  if (P.exchange != "a2a" && P.exchange != "split") {
-    std::fprintf(stderr, "exchange must be a2a or split\n");
-    return 2;
-  }
+int RunSharded(const Param& P, const KWArgs& rest, const LaunchEnv& env, const RunPlan& plan) {
   std::unique_ptr<ShardRunner> run;
   if (P.exchange == "split")
-    run.reset(new SplitRunner(P, rest));
+    run.reset(new SplitRunner(P, rest, plan));
   else
-    run.reset(new A2aRunner(P, rest));
+    run.reset(new A2aRunner(P, rest, env, plan));
   const int nlocal = run->nlocal(), nshards = run->nranks(), rank = run->rank(0);
   if (!P.model_in.empty()) {
     const int it = P.load_epoch > 0 ? P.load_epoch : -1;
@@ -889,7 +892,7 @@ int RunSharded(const Param& P, const KWArgs& rest) {
       v.clear();
     }
   } feeds{run.get(), {}};
-  if (P.parse == "sharded-device")
+  if (plan.parse == RunPlan::Parse::kDevice)
     for (int l = 0; l < nlocal; ++l)
       feeds.v.emplace_back(new DeviceTextFeed(run->ctx(l), P.batch_size, P.batch_size * P.shuffle,
                                               P.data_format, ShardRunner::kShardFeedDepth,
@@ -913,24 +916,21 @@ int RunSharded(const Param& P, const KWArgs& rest) {
     // pred_write=device: one writer per local shard, on the shard's context (they go before
     // the runner, which owns the contexts)
     std::vector<std::unique_ptr<DevicePredWriter>> writers;
-    if (P.pred_write == "device")
+    if (plan.pred_write_device)
       for (size_t l = 0; l < files.size(); ++l)
         writers.emplace_back(new DevicePredWriter(run->ctx((int)l), files[l], P.pred_prob));
+    ShardIO io;
+    io.pred_files = files.empty() ? nullptr : &files;
+    io.writers = writers.empty() ? nullptr : &writers;
+    io.feeds = fp;
     const double tp = Now();
-    const Progress pr = ShardedPass(run.get(), P, kfirst, GpuSGDLearner::kPrediction, false,
-                                    files.empty() ? nullptr : &files, nullptr,
-                                    writers.empty() ? nullptr : &writers, fp);
+    const Progress pr = ShardedPass(run.get(), P, kfirst, GpuSGDLearner::kPrediction, false, &io);
     const double pass_s = Now() - tp;
     for (FILE* f : files) std::fclose(f);
     if (rank == 0) std::printf("Prediction: %s\n", Text(pr).c_str());
-    if (P.pred_write == "device") {
+    if (plan.pred_write_device) {
       DevicePredWriter::Stats sum;
-      for (auto& w : writers) {
-        const DevicePredWriter::Stats st = w->GetStats();
-        sum.rows += st.rows;
-        sum.host_batches += st.host_batches;
-        sum.wait_s += st.wait_s;
-      }
+      for (auto& w : writers) sum += w->GetStats();
       PrintPredWriteLine(sum, pass_s);
     }
     writers.clear();
@@ -943,19 +943,19 @@ int RunSharded(const Param& P, const KWArgs& rest) {
     const bool record = k == kfirst;  // the first epoch this run executes records
     // exchange=split with the cache: where the submitting thread's time went
     const bool timed = run->has_cache() && P.exchange == "split";
-    double host_s[2] = {0, 0};
     if (timed) (void)run->TakeThrottleSeconds();
-    DeviceBatchReader::Times rt;
-    const Progress tr = ShardedPass(run.get(), P, k, GpuSGDLearner::kTraining, record, nullptr,
-                                    timed ? host_s : nullptr, nullptr, fp, &rt);
+    ShardIO io;
+    io.feeds = fp;
+    const Progress tr = ShardedPass(run.get(), P, k, GpuSGDLearner::kTraining, record, &io);
     const double dt = Now() - te;
+    const DeviceBatchReader::Times& rt = io.times;
     if (rank == 0)
       std::printf("Epoch[%d] Training: %s  (%.0f ex/s incl. parse+PCIe, %d shards%s, %.2f s)\n", k,
                   Text(tr).c_str(), tr.nrows / dt, nshards, run->tag(), Now() - t0);
     if (timed && rank == 0)
       std::printf("  split: epoch %.3f s; the host spent %.3f s in Step (of it %.3f s waiting on "
                   "the store's run-ahead bound) and %.3f s in the per-step all-reduce\n",
-                  dt, host_s[0], run->TakeThrottleSeconds(), host_s[1]);
+                  dt, io.host_s[0], run->TakeThrottleSeconds(), io.host_s[1]);
     // where this process's device readers' time went, summed over its shards (Times); an
     // epoch that replayed every part from the cache made no reader and prints nothing
     if (fp && rank == 0 && rt.copy + rt.wait_text + rt.wait_parse + rt.wait_step > 0)
@@ -966,8 +966,9 @@ int RunSharded(const Param& P, const KWArgs& rest) {
     if (!P.data_val.empty()) {
       // (the pass above flushed: the 1-step-stale schedule's last push is applied)
       const double tv = Now();
-      va = ShardedPass(run.get(), P, k, GpuSGDLearner::kValidation, record, nullptr, nullptr,
-                       nullptr, fp);
+      ShardIO vio;
+      vio.feeds = fp;
+      va = ShardedPass(run.get(), P, k, GpuSGDLearner::kValidation, record, &vio);
       if (rank == 0)
         std::printf("Epoch[%d] Validation: %s  (%.0f ex/s)\n", k, Text(va).c_str(),
                     va.nrows / (Now() - tv));
@@ -979,16 +980,9 @@ int RunSharded(const Param& P, const KWArgs& rest) {
       if (rank == 0) PrintCacheLine(cs[0], cs[1], cs[2], cs[3]);
     }
     std::fflush(stdout);
-    // stop criteria (sgd_learner.cc:92-106) on the all-reduced sums: the same on every rank,
-    // so all of them leave the loop in the same epoch
-    double eps = std::fabs(tr.loss - pre_loss) / pre_loss;
-    if (eps < P.stop_rel_objv) break;
-    if (va.auc > 0) {
-      eps = (va.auc - pre_val_auc) / va.nrows;
-      if (eps < P.stop_val_auc) break;
-    }
-    pre_loss = tr.loss;
-    pre_val_auc = va.auc;
+    // on the all-reduced sums: the same on every rank, so all of them leave the loop in the
+    // same epoch
+    if (ShouldStop(tr, va, &pre_loss, &pre_val_auc, P, false)) break;
   }
   run->Flush();
   if (!P.model_out.empty())
@@ -1000,223 +994,18 @@ int RunSharded(const Param& P, const KWArgs& rest) {
     }
   return 0;
 }
-}  // namespace
 
-int main(int argc, char** argv) {
-  Param P;
-  KWArgs rest;
-  bool fused_given = false;
-  for (int i = 1; i < argc; ++i) {
-    const char* eq = std::strchr(argv[i], '=');
-    if (!eq) {
-      std::fprintf(stderr, "argument '%s' is not key=value\n", argv[i]);
-      return 2;
-    }
-    const std::string k(argv[i], eq - argv[i]), v(eq + 1);
-    if (k == "data_in") P.data_in = v;
-    else if (k == "data_val") P.data_val = v;
-    else if (k == "data_format") P.data_format = v;
-    else if (k == "model_in") P.model_in = v;
-    else if (k == "model_out") P.model_out = v;
-    else if (k == "batch_size") P.batch_size = std::stoul(v);
-    else if (k == "shuffle") P.shuffle = std::stoul(v);
-    else if (k == "neg_sampling") P.neg_sampling = std::stof(v);
-    else if (k == "max_num_epochs") P.max_num_epochs = std::stoi(v);
-    else if (k == "num_jobs_per_epoch") P.num_jobs_per_epoch = std::stoi(v);
-    else if (k == "stop_rel_objv") P.stop_rel_objv = std::stod(v);
-    else if (k == "stop_val_auc") P.stop_val_auc = std::stod(v);
-    else if (k == "nthreads") P.nthreads = std::stoi(v);
-    else if (k == "load_epoch") P.load_epoch = std::stoi(v);
-    else if (k == "task") P.task = std::stoi(v);
-    else if (k == "pred_out") P.pred_out = v;
-    else if (k == "pred_prob") P.pred_prob = std::stoi(v) != 0;
-    else if (k == "has_aux") P.has_aux = std::stoi(v) != 0;
-    else if (k == "shards") P.shards = std::stoi(v);
-    else if (k == "pipelined") P.pipelined = std::stoi(v) != 0;
-    else if (k == "exchange") P.exchange = v;
-    else if (k == "model_in_parts") P.model_in_parts = std::stoi(v);
-    else if (k == "parse") P.parse = v;
-    else if (k == "cache") P.cache = v;
-    else if (k == "cache_mb") P.cache_mb = std::stoll(v);
-    else if (k == "cache_loc") P.cache_loc = std::stoi(v) != 0;
-    else if (k == "epoch_shuffle") P.epoch_shuffle = std::stoi(v) != 0;
-    else if (k == "shuffle_seed") P.shuffle_seed = std::stoull(v);
-    else if (k == "pred_write") P.pred_write = v;
-    else {
-      fused_given = fused_given || k == "fused";
-      rest.push_back({k, v});
-    }
-  }
-  if (P.data_in.empty() && P.task != 2) {
-    std::fprintf(stderr, "usage: %s data_in=FILE [key=value ...]\n", argv[0]);
-    return 2;
-  }
-  const char* ws = std::getenv("WORLD_SIZE");
-  const bool sharded = P.shards != 0 || (ws && std::atoi(ws) > 1);
-  if (P.parse != "host" && P.parse != "device" && P.parse != "auto" &&
-      P.parse != "auto-sharded") {
-    std::fprintf(stderr, "parse must be host, device, auto or auto-sharded\n");
-    return 2;
-  }
-  if (P.parse == "auto-sharded") {
-    if (!sharded) {
-      P.parse = "auto";  // the single-GPU run: parse=auto and its line, below
-    } else {  // the device parser in the sharded run too, where the format has one
-      const bool dev = P.data_format == "criteo" || P.data_format == "criteo_test" ||
-                       P.data_format == "libsvm";
-      const int nshards = P.shards > 0 ? P.shards : ws && std::atoi(ws) > 1 ? std::atoi(ws) : 1;
-      const char* rk = std::getenv("RANK");
-      if (!rk || std::atoi(rk) == 0) {  // rank 0 prints, as the cache's line
-        if (dev)
-          std::printf("parse: device (%s, %d shards)\n", P.data_format.c_str(), nshards);
-        else
-          std::printf("parse: host (data_format=%s)\n", P.data_format.c_str());
-        std::fflush(stdout);
-      }
-      P.parse = dev ? "sharded-device" : "host";
-    }
-  }
-  if (P.parse == "auto") {  // the device parser where there is one, and a line saying which
-    bool fused = true;
-    for (const auto& kv : rest)
-      if (kv.first == "fused") fused = std::stoi(kv.second) != 0;
-    std::string why;
-    if (sharded)
-      why = P.exchange == "split" ? "exchange=split" : "a sharded run";
-    else if (!fused)
-      why = "fused=0";
-    else if (P.data_format != "criteo" && P.data_format != "criteo_test" &&
-             P.data_format != "libsvm")
-      why = "data_format=" + P.data_format;
-    const bool dev = why.empty();
-    std::printf("parse: %s (%s)\n", dev ? "device" : "host",
-                dev ? P.data_format.c_str() : why.c_str());
-    std::fflush(stdout);
-    P.parse = dev ? "auto-device" : "host";
-  }
-  if (P.parse == "device") {  // no silent fall-back to the host reader
-    bool fused = true;
-    for (const auto& kv : rest)
-      if (kv.first == "fused") fused = std::stoi(kv.second) != 0;
-    const char* why = nullptr;
-    if (P.data_format != "criteo" && P.data_format != "criteo_test")
-      why = "data_format=criteo or criteo_test";
-    else if (!fused)
-      why = "the fused path (fused=1)";
-    else if (sharded)
-      why = "the single-GPU run (shards=0)";
-    if (why) {
-      std::fprintf(stderr, "parse=device needs %s\n", why);
-      return 2;
-    }
-  }
-  if (P.cache != "none" && P.cache != "device" && P.cache != "auto") {
-    std::fprintf(stderr, "cache must be none, device or auto\n");
-    return 2;
-  }
-  if (P.cache_loc) {  // no silent run without the kept outputs
-    bool fused = true;
-    for (const auto& kv : rest)
-      if (kv.first == "fused") fused = std::stoi(kv.second) != 0;
-    const char* why = nullptr;
-    if (P.cache != "device")
-      why = "cache=device (the outputs are kept with the cached batches)";
-    else if (!fused)
-      why = "the fused path (fused=1)";
-    else if (P.task == 2)
-      why = "a training run (task=2 is one pass: nothing is replayed)";
-    else if (sharded)
-      why = "the single-GPU run (shards=0): the sharded paths localize per shard";
-    if (why) {
-      std::fprintf(stderr, "cache_loc=1 needs %s\n", why);
-      return 2;
-    }
-  }
-  if (P.epoch_shuffle) {  // no silent run in the recorded order
-    bool fused = true;
-    for (const auto& kv : rest)
-      if (kv.first == "fused") fused = std::stoi(kv.second) != 0;
-    const char* why = nullptr;
-    if (P.cache != "device")
-      why = "cache=device (the rows are reshuffled out of the cached batches)";
-    else if (P.cache_loc)
-      why = "cache_loc=0 (reshuffled batches have no kept Localizer outputs)";
-    else if (!fused)
-      why = "the fused path (fused=1)";
-    else if (P.task == 2)
-      why = "a training run (task=2 is one pass: nothing is replayed)";
-    else if (sharded)
-      why = "the single-GPU run (shards=0)";
-    if (why) {
-      std::fprintf(stderr, "epoch_shuffle=1 needs %s\n", why);
-      return 2;
-    }
-  }
-  if (P.cache == "device") {  // no silent run without the cache
-    bool fused = true;
-    for (const auto& kv : rest)
-      if (kv.first == "fused") fused = std::stoi(kv.second) != 0;
-    const char* why = nullptr;
-    if (!fused)
-      why = "the fused path (fused=1)";
-    else if (sharded && P.exchange == "split")
-      why = "exchange=a2a in a sharded run (exchange=split replays under cache=auto)";
-    else if (P.cache_mb < 0)
-      why = "cache_mb >= 0";
-    if (why) {
-      std::fprintf(stderr, "cache=device needs %s\n", why);
-      return 2;
-    }
-  }
-  if (P.cache == "auto") {  // the device cache where batches replay, and a line saying which
-    if (P.cache_mb < 0) {
-      std::fprintf(stderr, "cache=auto needs cache_mb >= 0\n");
-      return 2;
-    }
-    bool fused = true;
-    for (const auto& kv : rest)
-      if (kv.first == "fused") fused = std::stoi(kv.second) != 0;
-    const bool dev = (sharded || fused) && P.task != 2;  // (task=2 is one pass: nothing to replay)
-    const std::string why = !sharded && !fused ? "fused=0"
-                            : P.task == 2      ? "task=2"
-                            : sharded          ? "exchange=" + P.exchange
-                                               : "fused";
-    const char* rk = std::getenv("RANK");
-    if (!sharded || !rk || std::atoi(rk) == 0) {
-      std::printf("cache: %s (%s)\n", dev ? "device" : "none", why.c_str());
-      std::fflush(stdout);
-    }
-    P.cache = dev ? "device" : "none";
-  }
-  if (P.pred_write != "host" && P.pred_write != "device") {
-    std::fprintf(stderr, "pred_write must be host or device\n");
-    return 2;
-  }
-  if (P.pred_write == "device") {  // no silent fall-back to the host writer
-    bool fused = true;
-    for (const auto& kv : rest)
-      if (kv.first == "fused") fused = std::stoi(kv.second) != 0;
-    if (!fused) {
-      std::fprintf(stderr, "pred_write=device needs the fused path (fused=1): the interface "
-                           "path keeps its predictions on the host\n");
-      return 2;
-    }
-  }
-  if (sharded && P.task == 2 && (P.model_in.empty() || P.data_val.empty())) {
-    std::fprintf(stderr, "prediction needs model_in and data_val\n");  // before any context
-    return 2;
-  }
-  if (sharded) return RunSharded(P, rest);
-  if (!fused_given) rest.push_back({"fused", "1"});
+// the single-GPU runs: training (with data_val: a validation pass after every epoch) and task=2
+int RunSingle(const Param& P, KWArgs rest, const RunPlan& plan) {
+  if (!plan.fused_given) rest.push_back({"fused", "1"});
   GpuSGDLearner learner(rest);
   std::unique_ptr<DeviceTextFeed> feed;
-  if (P.parse == "device" || P.parse == "auto-device")
+  if (plan.parse == RunPlan::Parse::kDevice)
     feed.reset(new DeviceTextFeed(learner.context(), P.batch_size, P.batch_size * P.shuffle,
                                   P.data_format));
   // (declared after the learner and the feed: destroyed, joining the context, before them)
   std::unique_ptr<DeviceBatchCache> cache;
-  if (P.cache == "device" && P.task != 2)
-    cache.reset(new DeviceBatchCache(learner.context(), P.cache_mb << 20));
+  if (plan.cache) cache.reset(new DeviceBatchCache(learner.context(), P.cache_mb << 20));
   // epoch_shuffle=1: one reshuffler per training part, made after the recording epoch (declared
   // after the cache: destroyed before it)
   std::vector<std::unique_ptr<DeviceReshuffler>> resh;
@@ -1227,10 +1016,6 @@ int main(int argc, char** argv) {
     if (P.load_epoch > 0) k0 = P.load_epoch + 1;
   }
   if (P.task == 2) {  // prediction, sgd_learner.cc:69-77
-    if (P.model_in.empty() || P.data_val.empty()) {
-      std::fprintf(stderr, "prediction needs model_in and data_val\n");
-      return 2;
-    }
     FILE* pf = nullptr;
     if (!P.pred_out.empty()) {
       pf = std::fopen((P.pred_out + "_part-0").c_str(), "w");
@@ -1240,16 +1025,19 @@ int main(int argc, char** argv) {
       }
     }
     std::unique_ptr<DevicePredWriter> writer;
-    if (pf && P.pred_write == "device")
+    if (pf && plan.pred_write_device)
       writer.reset(new DevicePredWriter(learner.context(), pf, P.pred_prob));
+    PassIO io;
+    io.feed = feed.get();
+    io.pred_file = pf;
+    io.dev_writer = writer.get();
     const double tp = Now();
-    const Progress pr = RunEpoch(&learner, P, k0, GpuSGDLearner::kPrediction, pf, feed.get(),
-                                 nullptr, nullptr, nullptr, false, nullptr, nullptr, writer.get());
+    const Progress pr = RunEpoch(&learner, P, plan, k0, GpuSGDLearner::kPrediction, &io);
     if (writer) writer->Finish();
     const double pass_s = Now() - tp;
     if (pf) std::fclose(pf);
     std::printf("Prediction: %s\n", Text(pr).c_str());
-    if (P.pred_write == "device")
+    if (plan.pred_write_device)
       PrintPredWriteLine(writer ? writer->GetStats() : DevicePredWriter::Stats(), pass_s);
     writer.reset();
     return 0;
@@ -1258,36 +1046,40 @@ int main(int argc, char** argv) {
   double pre_loss = 0, pre_val_auc = 0;  // sgd_learner.cc:52
   for (int k = k0; k < P.max_num_epochs; ++k) {
     const double te = Now();
-    DeviceBatchReader::Times rt;
-    double step_s[2] = {0, 0};  // inside dfx_train_step calls; the epoch's final join
     const bool record = k == k0;  // the first epoch this run executes records
-    double shuffle_wait[2] = {0, 0};  // the host's wait for the batches' sizes; parts reshuffled
-    const Progress tr = RunEpoch(&learner, P, k, GpuSGDLearner::kTraining, nullptr, feed.get(),
-                                 &rt, step_s, cache.get(), record,
-                                 resh.empty() ? nullptr : &resh, shuffle_wait);
+    PassIO io;
+    io.feed = feed.get();
+    io.cache = cache.get();
+    io.record = record;
+    io.resh = resh.empty() ? nullptr : &resh;
+    const Progress tr = RunEpoch(&learner, P, plan, k, GpuSGDLearner::kTraining, &io);
     const double dt = Now() - te;
     std::printf("Epoch[%d] Training: %s  (%.0f ex/s incl. parse+PCIe, %.2f s)\n", k,
                 Text(tr).c_str(), tr.nrows / dt, Now() - t0);
-    if (shuffle_wait[1] > 0)
+    if (io.shuffle_wait[1] > 0)
       std::printf("  epoch_shuffle: %.0f parts reshuffled, the host waited %.3f ms for their "
                   "batches' sizes\n",
-                  shuffle_wait[1], shuffle_wait[0] * 1e3);
+                  io.shuffle_wait[1], io.shuffle_wait[0] * 1e3);
     if (feed)  // where the device reader's time went (device_reader.h Times)
       std::printf("  reader: epoch %.3f s, host copy %.3f s (loader thread); caller waited for "
                   "text %.3f s, for the parse %.3f s, for a ring batch %.3f s, in dfx_train_step "
                   "%.3f s, in the final join %.3f s\n",
-                  dt, rt.copy, rt.wait_text, rt.wait_parse, rt.wait_step, step_s[0], step_s[1]);
+                  dt, io.times.copy, io.times.wait_text, io.times.wait_parse, io.times.wait_step,
+                  io.step_s[0], io.step_s[1]);
     Progress va;
     if (!P.data_val.empty()) {
-      va = RunEpoch(&learner, P, k, GpuSGDLearner::kValidation, nullptr, feed.get(), nullptr,
-                    nullptr, cache.get(), record);
+      PassIO vio;
+      vio.feed = feed.get();
+      vio.cache = cache.get();
+      vio.record = record;
+      va = RunEpoch(&learner, P, plan, k, GpuSGDLearner::kValidation, &vio);
       std::printf("Epoch[%d] Validation: %s\n", k, Text(va).c_str());
     }
     if (cache && record) {
       const DeviceBatchCache::Stats cs = cache->GetStats();
       PrintCacheLine((double)cs.batches, (double)cs.bytes, (double)cs.dropped,
                      (double)(cs.sealed + cs.dropped));
-      if (P.cache_loc) {
+      if (plan.cache_loc) {
         const DeviceBatchCache::LocStats ls = cache->GetLocStats();
         // (held counts whole blocks; the outputs' own bytes, each array rounded to 256)
         std::printf("cache_loc=1: %lld of %lld batches hold Localizer outputs, %.1f MB of the "
@@ -1295,7 +1087,7 @@ int main(int argc, char** argv) {
                     (long long)ls.batches, (long long)cs.batches, (double)ls.bytes / (1 << 20),
                     (double)cs.bytes / (1 << 20));
       }
-      if (P.epoch_shuffle) {
+      if (plan.epoch_shuffle) {
         int made = 0;
         int64_t ring = 0, scratch = 0;
         resh.resize((size_t)P.num_jobs_per_epoch);
@@ -1319,22 +1111,32 @@ int main(int argc, char** argv) {
       }
     }
     std::fflush(stdout);
-    // stop criteria, sgd_learner.cc:89-108
-    double eps = std::fabs(tr.loss - pre_loss) / pre_loss;
-    if (eps < P.stop_rel_objv) {
-      std::printf("Change of loss [%g] < stop_rel_objv [%g]\n", eps, P.stop_rel_objv);
-      break;
-    }
-    if (va.auc > 0) {
-      eps = (va.auc - pre_val_auc) / va.nrows;
-      if (eps < P.stop_val_auc) break;
-    }
-    pre_loss = tr.loss;
-    pre_val_auc = va.auc;
+    if (ShouldStop(tr, va, &pre_loss, &pre_val_auc, P, true)) break;
   }
   if (!P.model_out.empty()) {  // sgd_learner.cc:116-120
     FileStream fo(ModelName(P.model_out, -1).c_str(), "wb");
     learner.updater()->Save(P.has_aux, &fo);
   }
   return 0;
+}
+}  // namespace
+
+// parse argv, resolve the options (train_options.h: every rule and line), say what was
+// resolved, refuse or run
+int main(int argc, char** argv) {
+  Param P;
+  KWArgs rest;
+  RunPlan plan;
+  std::vector<std::string> lines;
+  std::string err;
+  const LaunchEnv env = LaunchEnv::FromEnvironment();
+  int rc = ParseArgs(argc, argv, &P, &rest, &err);
+  if (rc == 0) rc = ResolveOptions(P, rest, env, &plan, &lines, &err);
+  for (const std::string& line : lines) std::printf("%s\n", line.c_str());
+  std::fflush(stdout);
+  if (rc != 0) {
+    std::fprintf(stderr, "%s\n", err.c_str());
+    return rc;
+  }
+  return plan.sharded ? RunSharded(P, rest, env, plan) : RunSingle(P, rest, plan);
 }
