@@ -789,10 +789,21 @@ int launch_fwd_fused(const FwdArgs& a, hipStream_t st, int* nblk, bool spread) {
 
 // sharded store: forward over pulled records [V(d) | w | live | 0 | 0] (16-byte aligned rows
 // when d % 4 == 0), addressed through wpos / vpos
+// float4 lanes only when a lane's chunk of CPL coordinates lies wholly inside the record's V
+// (load_coords / store_coords): V_dim 260 at 8 per lane would read the record's {w, live} as
+// coordinates 260..263 and write XV*p over the row's p (every gradient then zero).  Such a V_dim
+// (a multiple of 4 above 256 that is no multiple of its CPL) takes the scalar lanes.
+static bool records_vec(int d) {
+  int G, CPL;
+  bool vec;
+  lanes_for(d, true, &G, &CPL, &vec);
+  return vec && d % CPL == 0;
+}
+
 int launch_fwd_records(const FwdArgs& a, hipStream_t st, int* nblk) {
   int G, CPL;
   bool vec;
-  lanes_for(a.d, true, &G, &CPL, &vec);
+  lanes_for(a.d, records_vec(a.d), &G, &CPL, &vec);
   const int64_t rpb = kFmNT / G;
   *nblk = (int)((a.B + rpb - 1) / rpb);
   return launch_fwd_gc<kFused, false>(a, G, CPL, vec, st);
@@ -1961,7 +1972,7 @@ int sum_live(const uint2* part, int64_t n, DevState* ds, hipStream_t st) {
 
 // sharded store: per-key gradient records in the pulled-record layout (aligned rows)
 int launch_bwd_positions(const BwdArgs& a, int64_t nseg_bound, hipStream_t st) {
-  return launch_bwd<false>(a, nseg_bound, st, true);
+  return launch_bwd<false>(a, nseg_bound, st, records_vec(a.d));
 }
 
 // ---- standalone CalcGrad support: CSC order of a compacted block ------------------------

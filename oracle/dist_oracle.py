@@ -38,9 +38,18 @@ def value_bounds(lens, bounds):
     return cum[bounds]
 
 
+def _rank_order(nranks, rank_order):
+    """the order a key's records are applied in: rank order unless a test asks for another
+    (tests/test_dist_ref.py: a reversed order must change the model's bits)"""
+    order = list(range(nranks)) if rank_order is None else [int(r) for r in rank_order]
+    assert sorted(order) == list(range(nranks))
+    return order
+
+
 class ShardedOracle:
-    def __init__(self, nranks, **kw):
+    def __init__(self, nranks, rank_order=None, **kw):
         self.N = int(nranks)
+        self.order = _rank_order(self.N, rank_order)
         self.up = [O.Updater(**kw) for _ in range(self.N)]
         self.d = self.up[0].V_dim
 
@@ -57,7 +66,7 @@ class ShardedOracle:
             loc.append((uniq, cnt, col, owner_bounds(uniq, N)))
         if push_cnt and d > 0:
             for g in range(N):
-                for r in range(N):
+                for r in self.order:
                     uniq, cnt, _, bd = loc[r]
                     if bd[g + 1] > bd[g]:
                         self.up[g].update(uniq[bd[g]:bd[g + 1]], O.Updater.kFeaCount,
@@ -101,7 +110,7 @@ class ShardedOracle:
         """the kGradient pushes: for each server, the workers in rank order"""
         N = self.N
         for g in range(N):
-            for r in range(N):
+            for r in self.order:
                 uniq, _, _, bd = st["loc"][r]
                 if bd[g + 1] == bd[g]:
                     continue
@@ -140,8 +149,9 @@ class AggOracle:
               order the owner adds the received records), then ONE Update in key order
     Same interface as ShardedOracle (begin / pull / compute / push / step / entry)."""
 
-    def __init__(self, nranks, **kw):
+    def __init__(self, nranks, rank_order=None, **kw):
         self.N = int(nranks)
+        self.order = _rank_order(self.N, rank_order)
         self.one = O.Updater(**kw)
         self.up = [self.one]
         self.d = self.one.V_dim
@@ -154,7 +164,8 @@ class AggOracle:
             uniq, cnt, col = O.localize(blk.offs, blk.ids, max_index, want_cnt=True)
             loc.append((uniq, cnt, col, owner_bounds(uniq, self.N)))
         if push_cnt and d > 0:
-            keys, cnts = self._union([l[0] for l in loc], [l[1] for l in loc], 1)
+            keys, cnts = self._union([loc[r][0] for r in self.order],
+                                     [loc[r][1] for r in self.order], 1)
             if len(keys):
                 self.one.update(keys, O.Updater.kFeaCount, cnts)
         return {"blocks": blocks, "loc": loc}
@@ -186,7 +197,7 @@ class AggOracle:
     def push(self, st):
         d = self.d
         keys, rows, lens_u = [], [], None
-        for r in range(self.N):
+        for r in self.order:
             uniq = st["loc"][r][0]
             vals, lens = st["pulled"][r]
             g = st["grads"][r]

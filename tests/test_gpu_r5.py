@@ -66,7 +66,7 @@ def test_walk_forward_bit_identical(H, rows, d, binary):
         qa, qb = H.progress(ca), H.progress(cb)
         got = pb.cpu().numpy()
         assert np.array_equal(pa.cpu().numpy().view(np.uint32), got.view(np.uint32)), step
-        # no key reaches a chunked (> 256 occurrences) gradient sum: the model stays the
+        # no key reaches a chunked (> kChunkOcc = 128 occurrences) gradient sum: the model stays the
         # oracle's, so predictions equal the reference's bit for bit
         assert np.array_equal(got.view(np.uint32), np.asarray(opred, np.float32).view(np.uint32))
         # per-block loss partials: the double sums differ in the last bits only
