@@ -39,7 +39,8 @@ DISTLIB = difacto_amd/libdfx_dist.so
 
 all: $(LIB) $(DISTLIB) oracle $(HOSTBIN) $(TRAINBIN) $(READERBIN) $(GENBIN) $(CONVBIN) $(RBENCH) \
   $(TPBIN) $(LSBIN) $(SEBIN) $(SDBIN) $(SPBIN) build/expf_check build/strtof_check build/gen_libsvm build/locbench \
-  build/reshuffle_check build/fmtg_check build/train_options_tests
+  build/reshuffle_check build/resample_check build/fmtg_check build/train_options_tests \
+  build/train_options_resample_tests
 
 $(RBENCH): difacto_amd/host/reader.cc tools/reader_bench.cc difacto_amd/host/reader.h $(CITYHDR)
 	@mkdir -p build
@@ -67,6 +68,12 @@ build/train_options_tests: tests/host/train_options_tests.cc difacto_amd/host/tr
 	@mkdir -p build
 	g++ $(HOSTFLAGS) -o $@ tests/host/train_options_tests.cc
 
+# ... and epoch_resample's rules, behind epoch_shuffle's
+build/train_options_resample_tests: tests/host/train_options_resample_tests.cc \
+  difacto_amd/host/train_options.h difacto_amd/host/iface.h
+	@mkdir -p build
+	g++ $(HOSTFLAGS) -o $@ tests/host/train_options_resample_tests.cc
+
 # the device text parser, the row gather and DeviceBatchReader against the host reader
 # (dfx_parse_criteo / dfx_gather_rows vs ParseCriteo / GatherRows / BatchReader), plus the CPU
 # modes: the batch planner, the raw-mode chunk cuts, the shared CityHash64
@@ -90,6 +97,11 @@ build/strtof_check: tools/strtof_check.cc $(CSRC)/strtof.h
 
 # test infrastructure: csrc/reshuffle.h (the reshuffler's permutation) printed from the host
 build/reshuffle_check: tools/reshuffle_check.cc $(CSRC)/reshuffle.h
+	@mkdir -p build
+	g++ -std=c++14 -O2 -Wall -o $@ $<
+
+# test infrastructure: csrc/reshuffle.h's per-epoch down-sample (rs_draw, rs_dropped) from the host
+build/resample_check: tools/resample_check.cc $(CSRC)/reshuffle.h
 	@mkdir -p build
 	g++ -std=c++14 -O2 -Wall -o $@ $<
 

@@ -69,6 +69,7 @@ _SIGS = {
     "dfx_prof_host": (ctypes.c_int, [vp, f64p]),
     "dfx_ctx_vdim": (ctypes.c_int, [vp]),
     "dfx_sync": (ctypes.c_int, [vp]),
+    "dfx_sync_input": (ctypes.c_int, [vp]),
     "dfx_malloc": (ctypes.c_int, [vp, ctypes.POINTER(vp), ctypes.c_size_t]),
     "dfx_free": (ctypes.c_int, [vp, vp]),
     "dfx_memcpy": (ctypes.c_int, [vp, vp, vp, ctypes.c_size_t, ctypes.c_int]),
@@ -156,6 +157,7 @@ _SIGS = {
                                             ctypes.POINTER(ctypes.c_int)]),
     "dfx_reshuffle_destroy": (ctypes.c_int, [vp]),
     "dfx_reshuffle_begin_epoch": (ctypes.c_int, [vp, c_u64, i64p]),
+    "dfx_reshuffle_begin_epoch_sampled": (ctypes.c_int, [vp, c_u64, ctypes.c_float, i64p, i64p]),
     "dfx_reshuffle_next": (ctypes.c_int, [vp, ctypes.POINTER(Batch),
                                           ctypes.POINTER(ctypes.c_int)]),
     "dfx_reshuffle_consumed": (ctypes.c_int, [vp]),

@@ -483,6 +483,13 @@ int dfx_sync(dfx_ctx* ctx) {
   return DFX_OK;
 }
 
+int dfx_sync_input(dfx_ctx* ctx) {
+  DFX_CHECK_ARG(ctx, "null ctx");
+  const Context& c = ctx->c;
+  DFX_HIP(hipStreamSynchronize(c.has_in_stream ? c.in_stream : c.stream));
+  return DFX_OK;
+}
+
 int dfx_malloc(dfx_ctx* ctx, void** ptr, size_t bytes) {
   DFX_CHECK_ARG(ctx && ptr, "dfx_malloc: null argument");
   DFX_HIP(hipSetDevice(ctx->c.device));

@@ -16,6 +16,23 @@
 //
 // Seed: rs_epoch_key(shuffle_seed, epoch, list) chains three splitmix64 steps:
 //   a = splitmix64(shuffle_seed), b = splitmix64(a ^ epoch), key = splitmix64(b ^ list).
+//
+// The per-epoch negative down-sample (dfx_reshuffle_begin_epoch_sampled): a keyed draw per row
+// beside the keyed position, read by the kernels, tools/resample_check.cc and the numpy
+// restatement tests/resample_ref.py.
+//   rs_draw(key, row)  u in [0, 1), a multiple of 2^-24 (exact in fp32): the top 24 bits of one
+//                      splitmix64 output of the state key ^ (0xA0761D6478BD642F * (row + 1))
+//   rs_dropped         the reader's own inequality (host/reader.cc, restating the reference's
+//                      batch_reader.cc:57-63), in fp32, its rand_r draw p replaced by u: a row
+//                      with label <= 0 is dropped when u > 1 - neg_sampling.  That drops a
+//                      negative with probability neg_sampling (the reference does the same,
+//                      whatever the parameter's doc comment says: the contract is its behaviour);
+//                      a positive row is never dropped, and neg_sampling >= 1 drops nothing: the
+//                      reader draws only when neg_sampling < 1 (reader.cc:817), and so does
+//                      this (without that guard u > 1 - 1 would drop every row but u = 0).
+//   row   the SOURCE row: its position in the concatenation of the list's batches, not the
+//         position the permutation gives it in the output
+//   key   the epoch key the permutation of that epoch uses (rs_epoch_key)
 #pragma once
 #include <stdint.h>
 
@@ -86,6 +103,17 @@ RS_HD inline uint32_t rs_apply(const rs_net& t, uint32_t j) {
 // position j of the output takes row rs_perm(j, N, key) of the input; N < 2^31
 RS_HD inline uint32_t rs_perm(uint32_t j, uint32_t N, uint64_t key) {
   return rs_apply(rs_make(N, key), j);
+}
+
+// u in [0, 1), a multiple of 2^-24, exact in fp32
+RS_HD inline float rs_draw(uint64_t key, uint32_t row) {
+  uint64_t s = key ^ (0xA0761D6478BD642Full * ((uint64_t)row + 1));
+  return (float)(rs_splitmix64(&s) >> 40) * (1.f / 16777216.f);  // 2^-24 (host code is C++14)
+}
+
+// the reader's own inequality (reader.cc:817-820), p replaced by the keyed draw
+RS_HD inline bool rs_dropped(uint64_t key, uint32_t row, float label, float neg_sampling) {
+  return neg_sampling < 1.f && label <= 0.f && rs_draw(key, row) > 1.f - neg_sampling;
 }
 
 RS_HD inline uint64_t rs_epoch_key(uint64_t shuffle_seed, uint64_t epoch, uint64_t list) {

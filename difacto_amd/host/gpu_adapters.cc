@@ -426,34 +426,55 @@ GpuSGDLearner::~GpuSGDLearner() {
   if (feeder_) dfx_feeder_destroy(feeder_);
 }
 
+// the batch into the feeder's next slot and up on its loader stream (the feeder is made, or
+// remade larger, here)
+dfx_batch GpuSGDLearner::Upload(const dmlc::RowBlock<feaid_t>& batch) {
+  const int64_t B = (int64_t)batch.size, nnz = B ? (int64_t)batch.offset[B] : 0;
+  dfx_ctx* c = updater_->context()->h();
+  if (!feeder_ || B > feed_rows_ || nnz > feed_nnz_) {
+    if (feeder_) {
+      DfxCheck(dfx_sync(c), "dfx_sync");
+      dfx_feeder_destroy(feeder_);
+    }
+    feed_rows_ = std::max<int64_t>(B, feed_rows_);
+    feed_nnz_ = std::max<int64_t>(nnz, feed_nnz_);
+    DfxCheck(dfx_feeder_create(c, feed_rows_, feed_nnz_, &feeder_), "dfx_feeder_create");
+  }
+  dfx_host_batch hb;
+  DfxCheck(dfx_feeder_slot(feeder_, &hb), "dfx_feeder_slot");
+  static_assert(sizeof(size_t) == sizeof(uint64_t), "size_t offsets");
+  std::memcpy(hb.offset, batch.offset, (B + 1) * 8);
+  ParallelCopy(hb.index, batch.index, nnz * 8);
+  if (batch.value) ParallelCopy(hb.value, batch.value, nnz * 4);
+  std::memcpy(hb.label, batch.label, B * 4);
+  if (batch.weight) std::memcpy(hb.weight, batch.weight, B * 4);
+  dfx_batch b;
+  DfxCheck(dfx_feeder_submit(feeder_, B, nnz, batch.value != nullptr, batch.weight != nullptr,
+                             &b),
+           "dfx_feeder_submit");
+  return b;
+}
+
+dfx_batch GpuSGDLearner::UploadBatch(const dmlc::RowBlock<feaid_t>& batch) {
+  DFX_HOST_CHECK(fused_, "UploadBatch: the fused path only");
+  return Upload(batch);
+}
+
+void GpuSGDLearner::UploadDone() {
+  // no step took the batch: its slot is free once the input stream is past the upload and
+  // whatever the caller queued there (the `consumed` mark alone would be recorded at once)
+  DfxCheck(dfx_sync_input(updater_->context()->h()), "dfx_sync_input");
+  DfxCheck(dfx_feeder_consumed(feeder_), "dfx_feeder_consumed");
+}
+
 void GpuSGDLearner::ProcessBatch(const dmlc::RowBlock<feaid_t>& batch, int job_type,
                                  bool push_cnt, std::vector<real_t>* pred_out,
                                  dfx_batch* dev_batch, const float** dev_pred) {
   push_cnt = push_cnt && job_type == kTraining && V_dim_ > 0;
   if (fused_) {
-    const int64_t B = (int64_t)batch.size, nnz = B ? (int64_t)batch.offset[B] : 0;
+    const int64_t B = (int64_t)batch.size;
+    const dfx_batch b = Upload(batch);
     dfx_ctx* c = updater_->context()->h();
-    if (!feeder_ || B > feed_rows_ || nnz > feed_nnz_) {
-      if (feeder_) {
-        DfxCheck(dfx_sync(c), "dfx_sync");
-        dfx_feeder_destroy(feeder_);
-      }
-      feed_rows_ = std::max<int64_t>(B, feed_rows_);
-      feed_nnz_ = std::max<int64_t>(nnz, feed_nnz_);
-      DfxCheck(dfx_feeder_create(c, feed_rows_, feed_nnz_, &feeder_), "dfx_feeder_create");
-    }
-    dfx_host_batch hb;
-    DfxCheck(dfx_feeder_slot(feeder_, &hb), "dfx_feeder_slot");
-    static_assert(sizeof(size_t) == sizeof(uint64_t), "size_t offsets");
-    std::memcpy(hb.offset, batch.offset, (B + 1) * 8);
-    ParallelCopy(hb.index, batch.index, nnz * 8);
-    if (batch.value) ParallelCopy(hb.value, batch.value, nnz * 4);
-    std::memcpy(hb.label, batch.label, B * 4);
-    if (batch.weight) std::memcpy(hb.weight, batch.weight, B * 4);
-    dfx_batch b;
-    DfxCheck(dfx_feeder_submit(feeder_, B, nnz, batch.value != nullptr, batch.weight != nullptr,
-                               &b),
-             "dfx_feeder_submit");
     if (dev_batch) *dev_batch = b;
     float* dp = nullptr;
     if (pred_out || dev_pred) {
@@ -692,6 +713,13 @@ DeviceReshuffler::~DeviceReshuffler() {
 int64_t DeviceReshuffler::BeginEpoch(uint64_t key) {
   int64_t n = 0;
   DfxCheck(dfx_reshuffle_begin_epoch(h_, key, &n), "dfx_reshuffle_begin_epoch");
+  return n;
+}
+
+int64_t DeviceReshuffler::BeginEpochSampled(uint64_t key, float neg_sampling, int64_t* rows) {
+  int64_t n = 0;
+  DfxCheck(dfx_reshuffle_begin_epoch_sampled(h_, key, neg_sampling, &n, rows),
+           "dfx_reshuffle_begin_epoch_sampled");
   return n;
 }
 

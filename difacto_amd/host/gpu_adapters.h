@@ -198,6 +198,12 @@ class GpuSGDLearner {
   void ProcessDeviceBatch(const dfx_batch& batch, int job_type, bool push_cnt,
                           std::vector<real_t>* pred = nullptr, const dfx_loc* loc = nullptr,
                           const float** dev_pred = nullptr);
+  /** ProcessBatch's upload alone (fused path): the batch on the device, in the feeder's buffers,
+   * and no step — the recording pass of epoch_resample=1 copies it into a DeviceBatchCache.
+   * UploadDone, after that copy was queued, waits for the context's input stream and frees the
+   * feeder's slot (no step's `consumed` mark would). */
+  dfx_batch UploadBatch(const dmlc::RowBlock<feaid_t>& batch);
+  void UploadDone();
   /** the learner's device context (the fused path's; null when a Store was given) */
   dfx_ctx* context() const { return updater_ ? updater_->context()->h() : nullptr; }
   /** sgd::Progress accumulated since the last call (joins the device) */
@@ -207,6 +213,7 @@ class GpuSGDLearner {
   bool fused() const { return fused_; }
 
  private:
+  dfx_batch Upload(const dmlc::RowBlock<feaid_t>& batch);
   bool fused_ = false;
   int V_dim_ = 0;
   std::shared_ptr<GpuSGDUpdater> updater_;
@@ -267,6 +274,10 @@ class DeviceReshuffler {
   bool kept() const { return h_ != nullptr; }
   /** the epoch keyed by `key` -> its batch count; -1: the ring no longer fits (replay the list) */
   int64_t BeginEpoch(uint64_t key);
+  /** ... without the negative rows this key's draw drops (dfx_reshuffle_begin_epoch_sampled: a
+   * fresh down-sample per epoch over a list that holds every row); *rows: the rows kept; -1: the
+   * compacted arrays or the ring do not fit (read the part through its reader) */
+  int64_t BeginEpochSampled(uint64_t key, float neg_sampling, int64_t* rows);
   /** the next batch, ready by the context's input stream's order; false past the last */
   bool Next(dfx_batch* b);
   /** after the step that took the batch */

@@ -9,7 +9,7 @@
 //                   [fused=1] [nthreads=8] [parse=host|device|auto|auto-sharded]
 //                   [cache=none|device|auto]
 //                   [cache_mb=16384] [cache_loc=0] [epoch_shuffle=0] [shuffle_seed=0]
-//                   [pred_write=host|device]
+//                   [epoch_resample=0] [pred_write=host|device]
 //                   [V_dim=..] [lr=..] [l1=..] ... (SGDUpdaterParam)
 //
 // What each option does is described below.  The rules themselves — which combinations are
@@ -95,6 +95,25 @@
 // waited for the batches' sizes (once per part).  Without cache=device, with cache_loc=1 (new
 // batches have no kept Localizer outputs), fused=0, task=2 or in a sharded run it is an error
 // (exit 2).  Default 0: the run as without it.
+//
+// epoch_resample=1 (with epoch_shuffle=1 and neg_sampling < 1): a reader decides once which
+// negative rows it drops and the cache records the survivors, so every replayed epoch trains on
+// the same sample and a dropped row is never seen; the reference makes a BatchReader per part per
+// epoch over a rand_r sequence that is never reseeded, so each of its epochs draws another
+// sample.  With this option the TRAINING readers of the recording epoch drop nothing
+// (neg_sampling 1), so the cache holds every row; each part is recorded WITHOUT training, its
+// list sealed and its reshuffler made, and then, in the recording epoch and in every later one,
+// stepped through DeviceReshuffler::BeginEpochSampled under rs_epoch_key(shuffle_seed, epoch,
+// list): this epoch's order without the negatives this epoch's keyed draw drops (csrc/reshuffle.h:
+// rs_dropped, the reader's own inequality; a negative is dropped with probability neg_sampling, as
+// the reference does).  Every epoch, the first included, sees a fresh order and a fresh sample;
+// push_cnt stays "epoch 0 of training"; validation readers and lists are as without it.  A part
+// whose list was dropped, whose reshuffler did not fit or whose sampled epoch does not fit is
+// never stepped unsampled out of the cache: it is read through its reader with the reader's own
+// sample (in the recording epoch that is a second read of the part).  One line after the cache's
+// and epoch_shuffle's says how many parts resample, and every epoch prints the rows kept of the
+// rows held.  Without epoch_shuffle=1, or with neg_sampling >= 1, it is an error (exit 2).
+// Default 0: the run as without it.
 //
 // pred_write=device (task=2 with pred_out; the single-GPU fused path with either parse, and the
 // sharded runs with both exchanges): every <pred_out>_part-<rank> is written from text the
@@ -225,13 +244,15 @@ bool ShouldStop(const Progress& tr, const Progress& va, double* pre_loss, double
 }
 
 // a part's device reader: training forms minibatches out of 64 MB chunks, shuffled and
-// down-sampled; validation and prediction take whole 256 MB chunks, one batch per chunk
+// down-sampled; validation and prediction take whole 256 MB chunks, one batch per chunk.
+// every_row: a training reader that drops no negative (epoch_resample=1's recording pass)
 std::unique_ptr<DeviceBatchReader> MakeDeviceReader(const Param& P, DeviceTextFeed* feed,
-                                                    bool train, int part, int nparts) {
+                                                    bool train, int part, int nparts,
+                                                    bool every_row = false) {
   return std::unique_ptr<DeviceBatchReader>(new DeviceBatchReader(
       feed, train ? P.data_in : P.data_val, P.data_format, part, nparts, train ? P.batch_size : 0,
-      train ? P.batch_size * P.shuffle : 0, train ? P.neg_sampling : 1.f, P.nthreads,
-      train ? (size_t)64 << 20 : (size_t)256 << 20));
+      train ? P.batch_size * P.shuffle : 0, train && !every_row ? P.neg_sampling : 1.f,
+      P.nthreads, train ? (size_t)64 << 20 : (size_t)256 << 20));
 }
 
 // what a RunEpoch pass may use (null: not in this run) and what it reports (accumulated)
@@ -248,6 +269,10 @@ struct PassIO {
   DeviceBatchReader::Times times;          // the device readers'
   double step_s[2] = {0, 0};        // inside dfx_train_step calls; the parts' final joins
   double shuffle_wait[2] = {0, 0};  // the host's wait for the batches' sizes; parts reshuffled
+  // epoch_resample=1: the rows kept of the rows held in the parts resampled; parts read through
+  // their readers (a dropped list, a reshuffler or a sample that did not fit)
+  int64_t resample_rows[2] = {0, 0};
+  int resample_read = 0;
 };
 
 // one RunEpoch call, as the four sources of a part's batches see it
@@ -351,12 +376,90 @@ void StepHostReader(Pass* s, int part, bool rec) {
   }
 }
 
+// epoch_resample=1, the recording pass of a training part: every row of the part (the reader
+// drops none) into the open list, and no step.  No step marks a batch consumed, so the host
+// waits for the input stream, where the batch was produced and copied, before its producer
+// takes the buffers back.
+void RecordPart(Pass* s, int part) {
+  const Param& P = s->P;
+  PassIO& io = *s->io;
+  if (io.feed) {
+    const auto reader = MakeDeviceReader(P, io.feed, true, part, P.num_jobs_per_epoch, true);
+    while (reader->Next()) {
+      io.cache->Append(reader->Value());
+      DfxCheck(dfx_sync_input(s->learner->context()), "dfx_sync_input");
+      reader->Consumed();
+    }
+    s->fallback += reader->FallbackChunks();
+    io.times += reader->TimesSpent();
+    return;
+  }
+  ThreadedBatchReader reader(P.data_in, P.data_format, part, P.num_jobs_per_epoch, P.batch_size,
+                             P.batch_size * P.shuffle, 1.f, P.nthreads);
+  while (reader.Next()) {
+    io.cache->Append(s->learner->UploadBatch(reader.Value().GetBlock()));
+    s->learner->UploadDone();
+  }
+}
+
+// epoch_resample=1, a training part: in the recording epoch its rows are recorded first and its
+// reshuffler made; then, in every epoch, the part is stepped through this epoch's order and this
+// epoch's sample of the cached rows.  A part that cannot be (its list was dropped, its
+// reshuffler or the sample's scratch did not fit) is read through its reader with the reader's
+// own sampling, never stepped unsampled out of the cache.
+void StepResampled(Pass* s, int epoch, int part) {
+  const Param& P = s->P;
+  PassIO& io = *s->io;
+  const int64_t list = CacheList(P, true, part);
+  std::unique_ptr<DeviceReshuffler>& rs = (*io.resh)[(size_t)part];
+  if (io.record) {
+    io.cache->Begin(list);
+    RecordPart(s, part);
+    if (io.cache->Seal() >= 0) {
+      rs.reset(new DeviceReshuffler(io.cache, list, (int64_t)P.batch_size, 4));
+      if (!rs->kept()) rs.reset();
+    }
+  }
+  int64_t n = -1, rows = 0;
+  if (rs) {
+    const double tb = Now();
+    n = rs->BeginEpochSampled(rs_epoch_key(P.shuffle_seed, (uint64_t)epoch, (uint64_t)list),
+                              P.neg_sampling, &rows);
+    io.shuffle_wait[0] += Now() - tb;
+  }
+  if (n >= 0) {
+    StepReshuffled(s, rs.get());
+    io.resample_rows[0] += rows;
+    io.resample_rows[1] += rs->GetStats().rows;
+    return;
+  }
+  // the sample's scratch or the ring did not fit while the part was recorded: the part reads
+  // through its reader in every epoch, its reshuffler's memory goes back to the cache, and the
+  // line after the cache's counts it among the parts read
+  if (rs && io.record) rs.reset();
+  io.resample_read += 1;
+  if (io.feed)
+    StepDeviceReader(s, part, false);
+  else
+    StepHostReader(s, part, false);
+}
+
 Progress RunEpoch(GpuSGDLearner* learner, const Param& P, const RunPlan& plan, int epoch,
                   int job_type, PassIO* io) {
   Progress prog;
   const bool train = job_type == GpuSGDLearner::kTraining;
   Pass s{learner, P, plan, job_type, train, train && epoch == 0, io, {}, 0};
   for (int part = 0; part < P.num_jobs_per_epoch; ++part) {
+    if (train && plan.epoch_resample && io->cache) {
+      StepResampled(&s, epoch, part);
+      const double tj = Now();
+      const Progress p = learner->TakeProgress();
+      io->step_s[1] += Now() - tj;
+      prog.nrows += p.nrows;
+      prog.loss += p.loss;
+      prog.auc += p.auc;
+      continue;
+    }
     const int64_t list = CacheList(P, train, part);
     const bool rec = io->cache && io->record;
     const int64_t n_cached = io->cache && !io->record ? io->cache->Count(list) : -1;
@@ -1051,11 +1154,23 @@ int RunSingle(const Param& P, KWArgs rest, const RunPlan& plan) {
     io.feed = feed.get();
     io.cache = cache.get();
     io.record = record;
+    // (epoch_resample=1 makes a part's reshuffler inside the recording epoch)
+    if (plan.epoch_resample && resh.empty()) resh.resize((size_t)P.num_jobs_per_epoch);
     io.resh = resh.empty() ? nullptr : &resh;
     const Progress tr = RunEpoch(&learner, P, plan, k, GpuSGDLearner::kTraining, &io);
     const double dt = Now() - te;
     std::printf("Epoch[%d] Training: %s  (%.0f ex/s incl. parse+PCIe, %.2f s)\n", k,
                 Text(tr).c_str(), tr.nrows / dt, Now() - t0);
+    if (plan.epoch_resample) {
+      std::printf("  epoch_resample: %lld of %lld rows kept in %.0f parts",
+                  (long long)io.resample_rows[0], (long long)io.resample_rows[1],
+                  io.shuffle_wait[1]);
+      if (io.resample_read)
+        std::printf(", %d part%s read through %s", io.resample_read,
+                    io.resample_read == 1 ? "" : "s",
+                    io.resample_read == 1 ? "its reader" : "their readers");
+      std::printf("\n");
+    }
     if (io.shuffle_wait[1] > 0)
       std::printf("  epoch_shuffle: %.0f parts reshuffled, the host waited %.3f ms for their "
                   "batches' sizes\n",
@@ -1093,11 +1208,15 @@ int RunSingle(const Param& P, KWArgs rest, const RunPlan& plan) {
         resh.resize((size_t)P.num_jobs_per_epoch);
         for (int part = 0; part < P.num_jobs_per_epoch; ++part) {
           const int64_t list = CacheList(P, true, part);
-          if (cache->Count(list) < 0) continue;  // not cached: read as without the option
-          resh[part].reset(new DeviceReshuffler(cache.get(), list, (int64_t)P.batch_size, 4));
-          if (!resh[part]->kept()) {
-            resh[part].reset();
-            continue;
+          if (plan.epoch_resample) {  // made, or found not to fit, while the part was recorded
+            if (!resh[part]) continue;
+          } else {
+            if (cache->Count(list) < 0) continue;  // not cached: read as without the option
+            resh[part].reset(new DeviceReshuffler(cache.get(), list, (int64_t)P.batch_size, 4));
+            if (!resh[part]->kept()) {
+              resh[part].reset();
+              continue;
+            }
           }
           const DeviceReshuffler::Stats rs = resh[part]->GetStats();
           ring += rs.ring_bytes;
@@ -1108,6 +1227,16 @@ int RunSingle(const Param& P, KWArgs rest, const RunPlan& plan) {
                     "%.1f MB\n",
                     made, P.num_jobs_per_epoch, (double)ring / (1 << 20),
                     (double)scratch / (1 << 20));
+        if (plan.epoch_resample) {
+          std::printf("epoch_resample=1: %d of %d training parts resample (neg_sampling=%g, every "
+                      "epoch a fresh sample of the rows held)",
+                      made, P.num_jobs_per_epoch, (double)P.neg_sampling);
+          if (made < P.num_jobs_per_epoch)
+            std::printf(", %d read through %s with the reader's sample",
+                        P.num_jobs_per_epoch - made,
+                        P.num_jobs_per_epoch - made == 1 ? "its reader" : "their readers");
+          std::printf("\n");
+        }
       }
     }
     std::fflush(stdout);

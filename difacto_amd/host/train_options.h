@@ -36,6 +36,7 @@ struct Param {
   bool cache_loc = false;      // the Localizer's outputs kept with the cached batches too
   bool epoch_shuffle = false;  // replayed training parts are reshuffled on the device per epoch
   uint64_t shuffle_seed = 0;   // ... keyed by (shuffle_seed, epoch, list)
+  bool epoch_resample = false;  // ... and negatives are down-sampled afresh per epoch there
   std::string pred_write = "host";  // host|device
 };
 
@@ -79,6 +80,7 @@ inline int ParseArgs(int argc, const char* const* argv, Param* Pp, KWArgs* rest,
     else if (k == "cache_loc") P.cache_loc = std::stoi(v) != 0;
     else if (k == "epoch_shuffle") P.epoch_shuffle = std::stoi(v) != 0;
     else if (k == "shuffle_seed") P.shuffle_seed = std::stoull(v);
+    else if (k == "epoch_resample") P.epoch_resample = std::stoi(v) != 0;
     else if (k == "pred_write") P.pred_write = v;
     else rest->push_back({k, v});
   }
@@ -118,13 +120,15 @@ struct RunPlan {
   Parse parse = Parse::kHost;  // kDevice: a DeviceTextFeed is made (per shard in a sharded run)
   bool cache = false;          // a DeviceBatchCache is made (never with task=2: one pass)
   bool cache_loc = false, epoch_shuffle = false;
+  bool epoch_resample = false;  // every training epoch draws its negatives out of the full cache
   bool pred_write_device = false;
   bool print_rank = true;  // rank 0, or an unsharded run: prints the run's lines
 };
 
 /** Every option rule of dfx_train, in the order that decides which refusal wins: the parse
- * value, auto-sharded, auto, device; the cache value, cache_loc, epoch_shuffle, cache=device,
- * cache=auto; the pred_write value, pred_write=device; the prediction inputs; exchange.  The
+ * value, auto-sharded, auto, device; the cache value, cache_loc, epoch_shuffle, epoch_resample,
+ * cache=device, cache=auto; the pred_write value, pred_write=device; the prediction inputs;
+ * exchange.  The
  * lines resolved before a refusal stay in out_lines (main prints them first).  0, or 2 with the
  * message in err.  Prints nothing and reads no environment. */
 inline int ResolveOptions(const Param& P, const KWArgs& rest, const LaunchEnv& env, RunPlan* plan,
@@ -199,8 +203,15 @@ inline int ResolveOptions(const Param& P, const KWArgs& rest, const LaunchEnv& e
       return refuse(what, "a training run (task=2 is one pass: nothing is replayed)");
     if (sharded) return refuse(what, "the single-GPU run (shards=0)");
   }
+  if (P.epoch_resample) {  // no silent run on the reader's one sample
+    const char* const what = "epoch_resample=1 needs ";
+    if (!P.epoch_shuffle)
+      return refuse(what, "epoch_shuffle=1 (the rows are drawn out of the reshuffled cache)");
+    if (!(P.neg_sampling < 1.f)) return refuse(what, "neg_sampling < 1");
+  }
   R.cache_loc = P.cache_loc;
   R.epoch_shuffle = P.epoch_shuffle;
+  R.epoch_resample = P.epoch_resample;
   if (P.cache == "device") {  // no silent run without the cache
     const char* const what = "cache=device needs ";
     if (!fused) return refuse(what, "the fused path (fused=1)");

@@ -519,6 +519,16 @@ class Reshuffler:
                                                    ctypes.byref(n)))
         return n.value
 
+    def begin_epoch_sampled(self, key, neg_sampling):
+        """the epoch keyed by ``key`` without the negative rows rs_dropped names (a fresh
+        down-sample per key) -> (its batch count, its rows); (-1, 0): the compacted arrays or the
+        ring do not fit the budget"""
+        n, rows = ctypes.c_int64(0), ctypes.c_int64(0)
+        check(_lib.lib().dfx_reshuffle_begin_epoch_sampled(
+            self.h, ctypes.c_uint64(int(key)), ctypes.c_float(neg_sampling), ctypes.byref(n),
+            ctypes.byref(rows)))
+        return n.value, rows.value
+
     def next(self):
         """-> the next batch (a CachedBatch whose pointers point into the ring), None past the
         last one"""

@@ -110,6 +110,10 @@ int dfx_ctx_set_lane_stream(dfx_ctx* ctx, int which, void* hip_stream);
 int dfx_ctx_set_input_stream(dfx_ctx* ctx, void* hip_stream);
 int dfx_ctx_vdim(dfx_ctx* ctx);
 int dfx_sync(dfx_ctx* ctx); /* waits for the stream and reports deferred device errors */
+/* waits for the input stream (the context stream when none is set): a batch that was produced
+ * and copied there (dfx_batchcache_append) but never stepped is then done with its producer's
+ * buffers, which the producer's `consumed` marks would otherwise tie to a step */
+int dfx_sync_input(dfx_ctx* ctx);
 int dfx_malloc(dfx_ctx* ctx, void** ptr, size_t bytes);
 int dfx_free(dfx_ctx* ctx, void* ptr);
 /* kind: 0 host->device, 1 device->host, 2 device->device; async on the stream.  A pageable
@@ -440,6 +444,34 @@ int dfx_reshuffle_begin_epoch(dfx_reshuffle* rs, uint64_t key, int64_t* n_batche
 int dfx_reshuffle_next(dfx_reshuffle* rs, dfx_batch* batch, int* has);
 int dfx_reshuffle_consumed(dfx_reshuffle* rs);
 int dfx_reshuffle_stats(dfx_reshuffle* rs, int64_t* out); /* out[4] */
+
+/* ---- a fresh negative down-sample per reshuffled epoch (difacto_amd/csrc/reshuffle.hip) -----
+ * A reader with neg_sampling < 1 decides once which negative rows it drops, and a cache that
+ * recorded its batches replays those survivors in every epoch; the reference makes a reader per
+ * part per epoch over a rand_r sequence that is never reseeded, so each of its epochs trains on
+ * another sample.  Over a list that holds EVERY row (recorded with neg_sampling 1),
+ *   dfx_reshuffle_begin_epoch_sampled
+ * opens an epoch as dfx_reshuffle_begin_epoch does, the rows in the order of rs_perm under `key`,
+ * without the rows rs_dropped(key, source row, label, neg_sampling) names (csrc/reshuffle.h: the
+ * reader's own inequality, label <= 0 and u > 1 - neg_sampling in fp32, u = rs_draw(key, source
+ * row) a keyed draw per SOURCE row; it drops a negative with probability neg_sampling, as the
+ * reference does).  On the context's input stream: a kernel computes every position's source,
+ * length and keep flag, a multi-launch scan of the flags (per-tile counts, one block over the
+ * tiles, per-tile ranks: the order is the scan's, never an atomic ticket's) compacts the kept
+ * rows' sources and lengths in permuted order, and the per-batch scan runs over the K kept rows,
+ * cut every batch_rows of them.  The per-batch nnz and K go to the pinned array and the host
+ * waits ONCE.  *n_batches = ceil(K / batch_rows), *n_rows = K; K = 0 is legal (*n_batches = 0,
+ * the first dfx_reshuffle_next gives *has = 0).  dfx_reshuffle_next then copies by the compacted
+ * sources (one launch a batch, a wave a row, the same ring, events, value and weight rules), and
+ * dfx_reshuffle_consumed is as above.  The compacted arrays, 8 bytes a row (and 4 per 2048 rows),
+ * are taken from the cache's budget at the first call, on 256-byte boundaries, and counted in
+ * dfx_reshuffle_stats' scratch from then on; if they do not fit, or the ring cannot be regrown,
+ * *n_batches = -1 (DFX_OK), the cache untouched, and dfx_reshuffle_begin_epoch still works.
+ * neg_sampling >= 1 drops nothing: the epoch's batches are dfx_reshuffle_begin_epoch's bit for
+ * bit.  Sampled and plain epochs may alternate.  DFX_ERR_ARG: a null argument, a NaN or negative
+ * neg_sampling; a rejected call queues nothing. */
+int dfx_reshuffle_begin_epoch_sampled(dfx_reshuffle* rs, uint64_t key, float neg_sampling,
+                                      int64_t* n_batches, int64_t* n_rows);
 
 /* ---- prediction rows as text on the device (difacto_amd/csrc/predtext.hip) ----------------
  * SGDLearner::SavePred (src/sgd/sgd_learner.h:72-83) writes one line per row,
