@@ -31,6 +31,7 @@ CONVBIN = build/dfx_convert
 RBENCH = build/reader_bench
 TPBIN = build/textparse_tests
 LSBIN = build/libsvmparse_tests
+ADBIN = build/adfeaparse_tests
 SEBIN = build/shard_eval_tests
 SDBIN = build/split_device_tests
 SPBIN = build/shard_parse_tests
@@ -38,9 +39,10 @@ SPBIN = build/shard_parse_tests
 DISTLIB = difacto_amd/libdfx_dist.so
 
 all: $(LIB) $(DISTLIB) oracle $(HOSTBIN) $(TRAINBIN) $(READERBIN) $(GENBIN) $(CONVBIN) $(RBENCH) \
-  $(TPBIN) $(LSBIN) $(SEBIN) $(SDBIN) $(SPBIN) build/expf_check build/strtof_check build/gen_libsvm build/locbench \
+  $(TPBIN) $(LSBIN) $(ADBIN) $(SEBIN) $(SDBIN) $(SPBIN) build/expf_check build/strtof_check \
+  build/gen_libsvm build/locbench \
   build/reshuffle_check build/resample_check build/fmtg_check build/train_options_tests \
-  build/train_options_resample_tests
+  build/train_options_resample_tests build/train_options_adfea_tests build/gen_adfea
 
 $(RBENCH): difacto_amd/host/reader.cc tools/reader_bench.cc difacto_amd/host/reader.h $(CITYHDR)
 	@mkdir -p build
@@ -74,6 +76,12 @@ build/train_options_resample_tests: tests/host/train_options_resample_tests.cc \
 	@mkdir -p build
 	g++ $(HOSTFLAGS) -o $@ tests/host/train_options_resample_tests.cc
 
+# ... and parse_adfea's, beside the parse value's
+build/train_options_adfea_tests: tests/host/train_options_adfea_tests.cc \
+  difacto_amd/host/train_options.h difacto_amd/host/iface.h
+	@mkdir -p build
+	g++ $(HOSTFLAGS) -o $@ tests/host/train_options_adfea_tests.cc
+
 # the device text parser, the row gather and DeviceBatchReader against the host reader
 # (dfx_parse_criteo / dfx_gather_rows vs ParseCriteo / GatherRows / BatchReader), plus the CPU
 # modes: the batch planner, the raw-mode chunk cuts, the shared CityHash64
@@ -88,6 +96,14 @@ $(TPBIN): $(HOSTLIB) tests/host/textparse_tests.cc $(HOSTHDR) $(LIB)
 $(LSBIN): $(HOSTLIB) tests/host/libsvmparse_tests.cc $(HOSTHDR) $(CSRC)/strtof.h $(LIB)
 	@mkdir -p build
 	g++ $(HOSTFLAGS) -o $@ $(HOSTLIB) tests/host/libsvmparse_tests.cc -Ldifacto_amd -ldifacto_amd \
+	  -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN/../difacto_amd' -Wl,-rpath,/opt/rocm/lib
+
+# the device adfea parser, the adfea text feed and DeviceBatchReader("adfea") against the host
+# reader (dfx_parse_adfea vs ParseAdfea / BatchReader), plus the CPU mode: the batch planner on
+# binary rows of varying length
+$(ADBIN): $(HOSTLIB) tests/host/adfeaparse_tests.cc $(HOSTHDR) $(LIB)
+	@mkdir -p build
+	g++ $(HOSTFLAGS) -o $@ $(HOSTLIB) tests/host/adfeaparse_tests.cc -Ldifacto_amd -ldifacto_amd \
 	  -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN/../difacto_amd' -Wl,-rpath,/opt/rocm/lib
 
 # test infrastructure: csrc/strtof.h (the device parser's numbers) against the host's strtof
@@ -112,6 +128,10 @@ build/fmtg_check: tools/fmtg_check.cc $(CSRC)/fmtg.h $(CSRC)/expf.h
 	g++ -std=c++17 -O2 -Wall -ffp-contract=off -o $@ $<
 
 build/gen_libsvm: tools/gen_libsvm.cc
+	@mkdir -p build
+	g++ -O2 -o $@ $<
+
+build/gen_adfea: tools/gen_adfea.cc
 	@mkdir -p build
 	g++ -O2 -o $@ $<
 

@@ -117,6 +117,7 @@ _SIGS = {
     "dfx_parse_libsvm": (ctypes.c_int, [vp, vp, c_i64, c_i64, c_i64, vp, vp, vp, vp, vp, vp]),
     "dfx_gather_rows_valued": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, c_i64, c_i64, vp, vp,
                                               vp, vp, vp, c_i64]),
+    "dfx_parse_adfea": (ctypes.c_int, [vp, vp, c_i64, c_i64, c_i64, vp, vp, vp, vp]),
     "dfx_textfeed_create": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, c_i64, c_i64,
                                            ctypes.c_int, ctypes.POINTER(vp)]),
     "dfx_textfeed_destroy": (ctypes.c_int, [vp]),

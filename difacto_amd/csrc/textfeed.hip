@@ -1,13 +1,15 @@
 // The text feed: raw text to device batches beside the step (the producer half of
 // sgd_learner.cc:289-314).  Pinned text slots, a loader stream, one parsed chunk per slot, a
 // shuffle buffer and a ring of device batches; the parsers (dfx_parse_criteo, textparse.hip;
-// dfx_parse_libsvm, libsvmparse.hip) and the row gather (textparse.hip) do the device work.
+// dfx_parse_libsvm, libsvmparse.hip; dfx_parse_adfea, adfeaparse.hip) and the row gather
+// (textparse.hip) do the device work.
 //
-// The format is fixed at dfx_textfeed_create and every later call takes its behaviour from it.
-// A Criteo feed's rows hold at most 39 ids, so rows alone size every array.  A libsvm feed is
-// valued: every CSR also holds values and row flags, a row has any number of features, and so
-// every CSR has an nnz capacity of its own: a slot's is the caller's bound for its chunk, the
-// shuffle buffer's and a ring entry's grow on demand and keep their contents.
+// The format is fixed at dfx_textfeed_create and every later call takes its behaviour from it,
+// through two properties.  Sized (libsvm, adfea): a row has any number of features, so every CSR
+// has an nnz capacity of its own: a slot's is the caller's bound for its chunk, the shuffle
+// buffer's and a ring entry's grow on demand and keep their contents.  A Criteo feed's rows hold
+// at most 39 ids, so rows alone size every array.  Valued (libsvm): every CSR also holds values
+// and row flags.  Criteo and adfea feeds are binary: no value arrays, no row flags.
 #include <algorithm>
 #include <vector>
 
@@ -16,20 +18,26 @@
 using namespace dfx;
 
 namespace {
+// what a feed's format means for its arrays (the head comment)
+struct FeedFmt {
+  bool sized = false;   // an nnz capacity of its own (DFX_TEXT_LIBSVM, DFX_TEXT_ADFEA)
+  bool valued = false;  // values and row flags (DFX_TEXT_LIBSVM)
+};
 struct DevCsr {
   uint64_t *off = nullptr, *idx = nullptr;
   float *lab = nullptr, *val = nullptr;  // val, flag: a valued CSR only
   uint8_t* flag = nullptr;
   int64_t cap = 0, nnz_cap = 0;  // rows, features
-  // room for rows / nnz; growth is x1.25 (at least 16 rows; valued: 64 features, else 39 ids for
+  // room for rows / nnz; growth is x1.25 (at least 16 rows; sized: 64 features, else 39 ids for
   // every row of the new capacity).  With st the first keep_rows rows and keep_nnz features are
   // kept: copied on st, in order behind whatever st holds that reads or writes the old arrays,
   // and joined before they are freed.
-  int reserve(int64_t rows, int64_t nnz, bool valued, hipStream_t st = nullptr,
+  int reserve(int64_t rows, int64_t nnz, FeedFmt fmt, hipStream_t st = nullptr,
               int64_t keep_rows = 0, int64_t keep_nnz = 0) {
+    const bool valued = fmt.valued;
     if (off && rows <= cap && nnz <= nnz_cap) return DFX_OK;
     const int64_t nr = off && rows <= cap ? cap : std::max<int64_t>(rows + rows / 4, 16);
-    const int64_t nn = !valued                 ? nr * kCols
+    const int64_t nn = !fmt.sized              ? nr * kCols
                        : off && nnz <= nnz_cap ? nnz_cap
                                                : std::max<int64_t>(nnz + nnz / 4, 64);
     DevCsr n;
@@ -87,7 +95,7 @@ struct dfx_textfeed {
     DevCsr csr;
     uint32_t *h_rows = nullptr, *d_rows = nullptr;  // the batch's row lists, appended
     int64_t used = 0;
-    int64_t nnz = 0;  // features gathered into the batch so far (the callers of a valued feed)
+    int64_t nnz = 0;  // features gathered into the batch so far (the callers of a sized feed)
     hipEvent_t consumed = nullptr;
   };
   std::vector<Slot> slot;
@@ -96,7 +104,8 @@ struct dfx_textfeed {
   int64_t shuf_nnz = 0;  // features in the shuffle buffer, as Ring::nnz
   int64_t batch_rows = 0;
   int cur = -1;
-  bool valued = false;  // DFX_TEXT_LIBSVM
+  int format = DFX_TEXT_CRITEO;
+  FeedFmt fmt;
 };
 
 extern "C" int dfx_textfeed_destroy(dfx_textfeed* f) {
@@ -133,12 +142,15 @@ extern "C" int dfx_textfeed_create(dfx_ctx* ctx, int nslots, int nring, int64_t 
                                    int64_t shuf_rows, int format, dfx_textfeed** out) {
   DFX_CHECK_ARG(ctx && out && nslots >= 2 && nslots <= 8 && nring >= 2 && nring <= 8 &&
                     batch_rows > 0 && batch_rows < (1ll << 31) && shuf_rows >= 0 &&
-                    (format == DFX_TEXT_CRITEO || format == DFX_TEXT_LIBSVM),
+                    (format == DFX_TEXT_CRITEO || format == DFX_TEXT_LIBSVM ||
+                     format == DFX_TEXT_ADFEA),
                 "textfeed_create: bad argument");
   DFX_HIP(hipSetDevice(ctx->c.device));
   dfx_textfeed* f = new dfx_textfeed();
   f->ctx = ctx;
-  f->valued = format == DFX_TEXT_LIBSVM;
+  f->format = format;
+  f->fmt.sized = format != DFX_TEXT_CRITEO;
+  f->fmt.valued = format == DFX_TEXT_LIBSVM;
   f->batch_rows = batch_rows;
   f->slot.resize((size_t)nslots);
   f->ring.resize((size_t)nring);
@@ -162,13 +174,13 @@ extern "C" int dfx_textfeed_create(dfx_ctx* ctx, int nslots, int nring, int64_t 
   for (auto& r : f->ring) {
     if (hipEventCreateWithFlags(&r.consumed, hipEventDisableTiming) != hipSuccess)
       return fail("event");
-    if (r.csr.reserve(batch_rows, batch_rows * kCols, f->valued) != DFX_OK)
+    if (r.csr.reserve(batch_rows, batch_rows * kCols, f->fmt) != DFX_OK)
       return fail("device batch");
     if (hipHostMalloc(&r.h_rows, (size_t)batch_rows * 4, hipHostMallocDefault) != hipSuccess ||
         hipMalloc(&r.d_rows, (size_t)batch_rows * 4) != hipSuccess)
       return fail("row lists");
   }
-  if (shuf_rows > 0 && f->shuf.reserve(shuf_rows, shuf_rows * kCols, f->valued) != DFX_OK)
+  if (shuf_rows > 0 && f->shuf.reserve(shuf_rows, shuf_rows * kCols, f->fmt) != DFX_OK)
     return fail("shuffle buffer");
   int rc = dfx_ctx_set_input_stream(ctx, f->stream);
   if (rc != DFX_OK) {
@@ -182,8 +194,15 @@ extern "C" int dfx_textfeed_create(dfx_ctx* ctx, int nslots, int nring, int64_t 
 #define DFX_FEED_SLOT(f, s, what) \
   DFX_CHECK_ARG((f) && (s) >= 0 && (s) < (int)(f)->slot.size(), what ": bad slot")
 // what only a valued feed has: its values, a batch handed out with them
-#define DFX_FEED_VALUED(f, asked, what) \
-  DFX_CHECK_ARG(!(asked) || (f)->valued, what ": a Criteo feed has no values")
+#define DFX_FEED_VALUED(f, asked, what)                                                    \
+  do {                                                                                     \
+    DFX_CHECK_ARG(!(asked) || (f)->format != DFX_TEXT_CRITEO,                              \
+                  what ": a Criteo feed has no values");                                   \
+    DFX_CHECK_ARG(!(asked) || (f)->fmt.valued, what ": an adfea feed has no values");      \
+  } while (0)
+// what only a sized feed takes: the features a gather appends
+#define DFX_FEED_SIZED(f, asked, what) \
+  DFX_CHECK_ARG(!(asked) || (f)->fmt.sized, what ": a Criteo feed has no values")
 
 extern "C" int dfx_textfeed_text(dfx_textfeed* f, int slot, int64_t bytes, char** pinned) {
   DFX_FEED_SLOT(f, slot, "textfeed_text");
@@ -206,7 +225,7 @@ extern "C" int dfx_textfeed_text(dfx_textfeed* f, int slot, int64_t bytes, char*
 
 // room for a chunk in the slot's CSR and in its pinned mirrors, which follow the CSR's rows
 static int feed_slot(dfx_textfeed* f, dfx_textfeed::Slot& s, int64_t rows, int64_t nnz) {
-  DFX_TRY(s.csr.reserve(rows, nnz, f->valued));
+  DFX_TRY(s.csr.reserve(rows, nnz, f->fmt));
   if (s.csr.cap > s.mirror_cap || !s.h_off) {
     for (void* p : {(void*)s.h_off, (void*)s.h_lab, (void*)s.h_flag})
       if (p) DFX_HIP(hipHostFree(p));
@@ -216,7 +235,8 @@ static int feed_slot(dfx_textfeed* f, dfx_textfeed::Slot& s, int64_t rows, int64
     s.mirror_cap = 0;
     DFX_HIP(hipHostMalloc(&s.h_off, (size_t)(s.csr.cap + 1) * 8, hipHostMallocDefault));
     DFX_HIP(hipHostMalloc(&s.h_lab, (size_t)s.csr.cap * 4, hipHostMallocDefault));
-    if (f->valued) DFX_HIP(hipHostMalloc(&s.h_flag, (size_t)s.csr.cap, hipHostMallocDefault));
+    if (f->fmt.valued)
+      DFX_HIP(hipHostMalloc(&s.h_flag, (size_t)s.csr.cap, hipHostMallocDefault));
     s.mirror_cap = s.csr.cap;
   }
   return DFX_OK;
@@ -229,7 +249,7 @@ extern "C" int dfx_textfeed_submit(dfx_textfeed* f, int slot, int64_t nbytes, in
   DFX_CHECK_ARG(nbytes >= 0 && nbytes <= s.text_cap && max_rows >= 0 && max_nnz >= 0,
                 "textfeed_submit: more bytes than dfx_textfeed_text reserved");
   DFX_HIP(hipSetDevice(f->ctx->c.device));
-  if (!f->valued) max_nnz = max_rows * kCols;
+  if (!f->fmt.sized) max_nnz = max_rows * kCols;
   DFX_TRY(feed_slot(f, s, max_rows, max_nnz));
   hipStream_t up = f->up_stream;
   // the gathers that read the slot's previous chunk, and a step that took it as its batch,
@@ -239,9 +259,12 @@ extern "C" int dfx_textfeed_submit(dfx_textfeed* f, int slot, int64_t nbytes, in
   if (nbytes)
     DFX_HIP(hipMemcpyAsync(s.d_text, s.h_text, (size_t)nbytes, hipMemcpyHostToDevice, up));
   const TpScratch ws{&f->tp[0], &f->tp[1], &f->tp[2], &f->tp[3], &f->tp[4], &f->tp[5]};
-  if (f->valued)
+  if (f->format == DFX_TEXT_LIBSVM)
     DFX_TRY(parse_libsvm_on(ws, up, s.d_text, nbytes, max_rows, max_nnz, s.csr.off, s.csr.idx,
                             s.csr.val, s.csr.lab, s.csr.flag, s.d_stat));
+  else if (f->format == DFX_TEXT_ADFEA)
+    DFX_TRY(parse_adfea_on(ws, up, s.d_text, nbytes, max_rows, max_nnz, s.csr.off, s.csr.idx,
+                           s.csr.lab, s.d_stat));
   else
     DFX_TRY(parse_criteo_on(ws, up, s.d_text, nbytes, is_train, max_rows, max_nnz, s.csr.off,
                             s.csr.idx, s.csr.lab, s.d_stat));
@@ -250,7 +273,7 @@ extern "C" int dfx_textfeed_submit(dfx_textfeed* f, int slot, int64_t nbytes, in
                          up));
   if (max_rows)
     DFX_HIP(hipMemcpyAsync(s.h_lab, s.csr.lab, (size_t)max_rows * 4, hipMemcpyDeviceToHost, up));
-  if (max_rows && f->valued)
+  if (max_rows && f->fmt.valued)
     DFX_HIP(hipMemcpyAsync(s.h_flag, s.csr.flag, (size_t)max_rows, hipMemcpyDeviceToHost, up));
   DFX_HIP(hipMemcpyAsync(s.h_stat, s.d_stat, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, up));
   DFX_HIP(hipEventRecord(s.parsed, up));
@@ -280,7 +303,7 @@ extern "C" int dfx_textfeed_upload(dfx_textfeed* f, int slot, int64_t rows, int6
   DFX_FEED_SLOT(f, slot, "textfeed_upload");
   DFX_FEED_VALUED(f, value, "textfeed_upload");
   DFX_CHECK_ARG(rows >= 0 && nnz >= 0 && offset && (index || !nnz) && (label || !rows) &&
-                    (value || !nnz || !f->valued) && (f->valued || nnz <= rows * kCols) &&
+                    (value || !nnz || !f->fmt.valued) && (f->fmt.sized || nnz <= rows * kCols) &&
                     offset[0] == 0 && (int64_t)offset[rows] == nnz,
                 "textfeed_upload: bad argument");
   auto& s = f->slot[slot];
@@ -288,23 +311,24 @@ extern "C" int dfx_textfeed_upload(dfx_textfeed* f, int slot, int64_t rows, int6
   hipStream_t up = f->up_stream;
   if (rows > s.csr.cap || nnz > s.csr.nnz_cap || !s.h_off) {
     DFX_HIP(hipStreamSynchronize(up));
-    DFX_TRY(feed_slot(f, s, rows, f->valued ? nnz : rows * kCols));
+    DFX_TRY(feed_slot(f, s, rows, f->fmt.sized ? nnz : rows * kCols));
   }
   // after the slot's own parse (dfx_textfeed_wait joined it); the gathers wait for `parsed`
   std::copy(offset, offset + rows + 1, s.h_off);
   if (rows) std::copy(label, label + rows, s.h_lab);
-  for (int64_t r = 0; r < rows && f->valued; ++r) {  // the row flags: a value that is not 1.0f
+  // the row flags: a value that is not 1.0f
+  for (int64_t r = 0; r < rows && f->fmt.valued; ++r) {
     uint8_t fl = 0;
     for (uint64_t k = offset[r]; k < offset[r + 1] && !fl; ++k) fl = value[k] != 1.f;
     s.h_flag[r] = fl;
   }
   DFX_HIP(hipMemcpyAsync(s.csr.off, s.h_off, (size_t)(rows + 1) * 8, hipMemcpyHostToDevice, up));
   if (nnz) DFX_HIP(hipMemcpyAsync(s.csr.idx, index, (size_t)nnz * 8, hipMemcpyHostToDevice, up));
-  if (nnz && f->valued)
+  if (nnz && f->fmt.valued)
     DFX_HIP(hipMemcpyAsync(s.csr.val, value, (size_t)nnz * 4, hipMemcpyHostToDevice, up));
   if (rows)
     DFX_HIP(hipMemcpyAsync(s.csr.lab, s.h_lab, (size_t)rows * 4, hipMemcpyHostToDevice, up));
-  if (rows && f->valued)
+  if (rows && f->fmt.valued)
     DFX_HIP(hipMemcpyAsync(s.csr.flag, s.h_flag, (size_t)rows, hipMemcpyHostToDevice, up));
   // the caller's arrays are pageable: staged before the calls return
   DFX_HIP(hipEventRecord(s.parsed, up));
@@ -332,7 +356,7 @@ extern "C" int dfx_textfeed_gather(dfx_textfeed* f, int src, int to_batch, const
                 "textfeed_gather: bad argument");
   DFX_CHECK_ARG(!to_batch || f->cur >= 0, "textfeed_gather: no batch begun");
   DFX_CHECK_ARG(src >= 0 || to_batch, "textfeed_gather: the shuffle buffer onto itself");
-  DFX_FEED_VALUED(f, nnz, "textfeed_gather");
+  DFX_FEED_SIZED(f, nnz, "textfeed_gather");
   if (n == 0) return DFX_OK;
   DFX_HIP(hipSetDevice(f->ctx->c.device));
   const DevCsr& S = src >= 0 ? f->slot[src].csr : f->shuf;
@@ -340,11 +364,11 @@ extern "C" int dfx_textfeed_gather(dfx_textfeed* f, int src, int to_batch, const
   int64_t& used = to_batch ? f->ring[f->cur].nnz : f->shuf_nnz;
   DFX_CHECK_ARG(r0 + n <= D.cap, "textfeed_gather: more rows than the destination holds");
   if (r0 == 0) used = 0;
-  // a valued destination grows by the caller's nnz; the copies of a growth run on the gathers'
+  // a sized destination grows by the caller's nnz; the copies of a growth run on the gathers'
   // stream: behind the gathers that filled the old arrays and, for the shuffle buffer, behind
   // the gathers that read them.  A Criteo destination holds 39 ids a row from the start: nnz
   // is 0 and this returns at once, nothing queued.
-  DFX_TRY(D.reserve(D.cap, used + nnz, f->valued, f->stream, r0, used));
+  DFX_TRY(D.reserve(D.cap, used + nnz, f->fmt, f->stream, r0, used));
   used += nnz;
   const uint32_t* rows_dev = nullptr;
   if (rows) {
@@ -358,7 +382,8 @@ extern "C" int dfx_textfeed_gather(dfx_textfeed* f, int src, int to_batch, const
     r.used += n;
   }
   if (src >= 0) DFX_HIP(hipStreamWaitEvent(f->stream, f->slot[src].parsed, 0));
-  if (f->valued)
+  // a sized feed: the valued gather, with no value and flag arrays on either side when binary
+  if (f->fmt.sized)
     DFX_TRY(gather_rows_on<true>(&f->ctx->c, f->stream, S.off, S.idx, S.lab, rows_dev, begin, n,
                                  D.off, D.idx, D.lab, r0, S.val, D.val, S.flag, D.flag));
   else

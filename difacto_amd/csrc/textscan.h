@@ -1,28 +1,33 @@
 // The scan helpers of the device text parsers (textparse.hip: Criteo, the row gather;
-// libsvmparse.hip: libsvm): a block scan, the plain multi-launch scan (tile totals, a scan of
-// the totals, apply - no look-back, nothing spins) and the launch helpers.  These sit in an
-// unnamed namespace: each .hip file that uses them gets kernels of its own.  In front of them:
-// what the text feed (textfeed.hip) calls of the two parsers and the gather.
+// libsvmparse.hip: libsvm; adfeaparse.hip: adfea): a block scan, the plain multi-launch scan
+// (tile totals, a scan of the totals, apply - no look-back, nothing spins) and the launch
+// helpers.  These sit in an unnamed namespace: each .hip file that uses them gets kernels of its
+// own.  In front of them: what the text feed (textfeed.hip) calls of the three parsers and the
+// gather.
 #pragma once
 #include "internal.h"
 
 namespace dfx {
 constexpr int kCols = 39;  // criteo feature columns (13 integer + 26 categorical)
 
-// a parser's scratch: the context's own set (dfx_parse_criteo / dfx_parse_libsvm, on the input
+// a parser's scratch: the context's own set (dfx_parse_criteo / _libsvm / _adfea, on the input
 // stream) or a text feed's (textfeed.hip; its parses run on a stream of their own).  The libsvm
-// parser uses tiles and stat only.
+// and adfea parsers use tiles and stat only.
 struct TpScratch {
   DevBuf *tiles, *cells, *lines, *pair, *tot, *stat;
 };
 // the parsers and the row gather on a stream of the caller's choice (textparse.hip,
-// libsvmparse.hip); capacity_status: DFX_ERR_CAPACITY when the stat a parser left says overflow
+// libsvmparse.hip, adfeaparse.hip); capacity_status: DFX_ERR_CAPACITY when the stat a parser
+// left says overflow
 int parse_criteo_on(const TpScratch& ws, hipStream_t st, const char* text, int64_t nbytes,
                     int is_train, int64_t max_rows, int64_t max_nnz, uint64_t* offset,
                     uint64_t* index, float* label, int64_t* stat_dev);
 int parse_libsvm_on(const TpScratch& ws, hipStream_t st, const char* text, int64_t nbytes,
                     int64_t max_rows, int64_t max_nnz, uint64_t* offset, uint64_t* index,
                     float* value, float* label, uint8_t* rowflag, int64_t* stat_dev);
+int parse_adfea_on(const TpScratch& ws, hipStream_t st, const char* text, int64_t nbytes,
+                   int64_t max_rows, int64_t max_nnz, uint64_t* offset, uint64_t* index,
+                   float* label, int64_t* stat_dev);
 int capacity_status(const int64_t* stat);
 template <bool kValued>
 int gather_rows_on(Context* c, hipStream_t st, const uint64_t* src_offset,

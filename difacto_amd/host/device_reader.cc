@@ -18,7 +18,9 @@ DeviceTextFeed::DeviceTextFeed(dfx_ctx* ctx, size_t batch_size, size_t shuf_buf,
                                const std::string& format, int nslots, int nring)
     : batch_size_(batch_size ? batch_size : 1),
       shuf_buf_(shuf_buf),
-      format_(format == "libsvm" ? DFX_TEXT_LIBSVM : DFX_TEXT_CRITEO) {
+      format_(format == "libsvm"  ? DFX_TEXT_LIBSVM
+              : format == "adfea" ? DFX_TEXT_ADFEA
+                                  : DFX_TEXT_CRITEO) {
   DfxCheck(dfx_textfeed_create(ctx, nslots, nring, (int64_t)batch_size_, (int64_t)shuf_buf_,
                                format_, &h_),
            "dfx_textfeed_create");
@@ -85,20 +87,29 @@ void DeviceTextFeed::Mark(uint64_t ticket) {
     throw FeedProtocolError("text feed: a mark for a batch not handed out yet");
 }
 
-// src -> dst over up to nthreads threads; returns the number of '\n' bytes copied; blanks
-// (libsvm): also counts the ' ' and '\t' bytes, which bound the chunk's features
+// src -> dst over up to nthreads threads; returns the number of '\n' bytes copied; blanks (a
+// sized feed): also counts the bytes that bound the chunk's features: the ' ' and '\t' bytes
+// (libsvm: a feature follows a blank) or, with colons, the ':' bytes (adfea: every feature
+// holds one)
 static size_t CopyCountLines(char* dst, const char* src, size_t bytes, int nthreads,
-                             size_t* blanks = nullptr) {
+                             size_t* blanks = nullptr, bool colons = false) {
   std::vector<size_t> nblank(std::max(nthreads, 1), 0);
   size_t* const nb = blanks ? nblank.data() : nullptr;
-  auto part = [nb](char* d, const char* s, size_t n, int t = 0) {
+  auto part = [nb, colons](char* d, const char* s, size_t n, int t = 0) {
     std::memcpy(d, s, n);
     size_t c = 0;
     if (nb) {
       size_t b = 0;
-      for (const char *p = d, *e = d + n; p < e; ++p) {
-        c += *p == '\n';
-        b += (*p == ' ') | (*p == '\t');
+      if (colons) {
+        for (const char *p = d, *e = d + n; p < e; ++p) {
+          c += *p == '\n';
+          b += *p == ':';
+        }
+      } else {
+        for (const char *p = d, *e = d + n; p < e; ++p) {
+          c += *p == '\n';
+          b += (*p == ' ') | (*p == '\t');
+        }
       }
       nb[t] = b;
       return c;
@@ -142,12 +153,17 @@ DeviceBatchReader::DeviceBatchReader(DeviceTextFeed* feed, const std::string& pa
       f_(feed->h()),
       reader_(path, format, part, nparts, chunk_bytes, nthreads, 0),
       train_(format != "criteo_test"),
+      sized_(feed->sized()),
       valued_(feed->valued()),
       batch_size_(batch_size),
       nthreads_(nthreads < 1 ? 1 : nthreads) {
-  DFX_HOST_CHECK(format == "criteo" || format == "criteo_test" || format == "libsvm",
-                 "the device reader parses criteo, criteo_test and libsvm, not " + format);
-  DFX_HOST_CHECK((format == "libsvm") == valued_, "the text feed was created for another format");
+  DFX_HOST_CHECK(format == "criteo" || format == "criteo_test" || format == "libsvm" ||
+                     format == "adfea",
+                 "the device reader parses criteo, criteo_test, libsvm and adfea, not " + format);
+  DFX_HOST_CHECK((format == "libsvm"  ? DFX_TEXT_LIBSVM
+                  : format == "adfea" ? DFX_TEXT_ADFEA
+                                      : DFX_TEXT_CRITEO) == feed->format(),
+                 "the text feed was created for another format");
   DFX_HOST_CHECK(batch_size <= feed->batch_size() && shuf_buf <= feed->shuf_buf(),
                  "batch or shuffle buffer larger than the text feed's");
   if (batch_size_) {
@@ -213,7 +229,8 @@ void DeviceBatchReader::Load() {
     DfxCheck(dfx_textfeed_text(f_, slot, (int64_t)size, &dst), "dfx_textfeed_text");
     const double t0 = Seconds();
     size_t blanks = 0;
-    const size_t nl = CopyCountLines(dst, data, size, nthreads_, valued_ ? &blanks : nullptr);
+    const size_t nl = CopyCountLines(dst, data, size, nthreads_, sized_ ? &blanks : nullptr,
+                                     feed_->format() == DFX_TEXT_ADFEA);
     {
       std::lock_guard<std::mutex> lk(mu_);
       times_.copy += Seconds() - t0;
@@ -236,7 +253,8 @@ void DeviceBatchReader::SubmitFilled(bool wait) {
   }
   for (const Filled& c : take) {
     // rows <= lines <= newlines: whole lines, the last one terminated (TextReader::NextRaw);
-    // libsvm: a feature follows a blank (the loader counts blanks for a valued feed only)
+    // libsvm: a feature follows a blank; adfea: a feature holds a ':' (the loader counts either
+    // for a sized feed only)
     DfxCheck(dfx_textfeed_submit(f_, c.slot, (int64_t)c.bytes, train_ ? 1 : 0,
                                  (int64_t)c.newlines, (int64_t)c.blanks),
              "dfx_textfeed_submit");
@@ -269,11 +287,16 @@ bool DeviceBatchReader::FetchChunk(size_t* rows, const uint64_t** off, const flo
   submitted_.pop_front();
   int64_t stat[4];
   const double t0 = Seconds();
-  DfxCheck(dfx_textfeed_wait(f_, c.slot, stat, off, lab, &chunk_flag_), "dfx_textfeed_wait");
+  const int rc = dfx_textfeed_wait(f_, c.slot, stat, off, lab, &chunk_flag_);
+  // adfea: the ':' bytes bound the features of every chunk inside the device's domain, so a
+  // chunk that needs more (tokens without ':' at feature places) is outside it: handed back too.
+  // Only nnz can be what overflowed: max_rows was the chunk's newline count and rows = newlines.
+  const bool outside = rc == DFX_ERR_CAPACITY && feed_->format() == DFX_TEXT_ADFEA;
+  if (!outside) DfxCheck(rc, "dfx_textfeed_wait");
   times_.wait_parse += Seconds() - t0;
   SubmitFilled(false);  // slots filled meanwhile: their parses run beside this chunk's batches
   *rows = (size_t)stat[0];
-  if (stat[2]) {  // needs_host: the host parser's rows into the same device arrays
+  if (stat[2] || outside) {  // needs_host: the host parser's rows into the same device arrays
     ++fallback_;
     char* text = nullptr;
     DfxCheck(dfx_textfeed_text(f_, c.slot, (int64_t)c.bytes, &text), "dfx_textfeed_text");
@@ -298,11 +321,11 @@ bool DeviceBatchReader::FetchChunk(size_t* rows, const uint64_t** off, const flo
   return true;
 }
 
-// one copy of the plan; a valued feed: its nnz from the mirrored row lengths, the flags carried
-// along
+// one copy of the plan; a sized feed: its nnz from the mirrored row lengths; a valued one: the
+// flags carried along
 void DeviceBatchReader::Gather(const GatherOp& op) {
   const bool from_shuf = op.src == GatherOp::kShuffle;
-  const size_t nnz = valued_ ? MirrorRows(op, from_shuf) : 0;
+  const size_t nnz = sized_ ? MirrorRows(op, from_shuf) : 0;
   DfxCheck(dfx_textfeed_gather(f_, from_shuf ? -1 : seq_slot_[op.src], op.to_batch ? 1 : 0,
                                op.rows.empty() ? nullptr : op.rows.data(), (int64_t)op.begin,
                                (int64_t)op.n, (int64_t)op.r0, (int64_t)nnz),
@@ -313,7 +336,10 @@ size_t DeviceBatchReader::MirrorRows(const GatherOp& op, bool from_shuf) {
   auto len = [&](size_t j) {
     return from_shuf ? (size_t)shuf_len_[j] : (size_t)(chunk_off_[j + 1] - chunk_off_[j]);
   };
-  auto flag = [&](size_t j) { return from_shuf ? shuf_flag_[j] : chunk_flag_[j]; };
+  // a binary feed (adfea) mirrors no flags: none is ever set
+  auto flag = [&](size_t j) {
+    return valued_ ? (from_shuf ? shuf_flag_[j] : chunk_flag_[j]) : (uint8_t)0;
+  };
   if (op.r0 == 0) {
     if (op.to_batch) {
       batch_valued_ = false;
@@ -330,7 +356,7 @@ size_t DeviceBatchReader::MirrorRows(const GatherOp& op, bool from_shuf) {
       batch_valued_ = batch_valued_ || flag(j);
     } else {
       shuf_len_.push_back((uint32_t)len(j));
-      shuf_flag_.push_back(flag(j));
+      if (valued_) shuf_flag_.push_back(flag(j));
     }
   }
   return nnz;

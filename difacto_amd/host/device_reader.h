@@ -1,12 +1,12 @@
-// device_reader.h — Criteo and libsvm minibatches formed on the device from raw text.
+// device_reader.h — Criteo, libsvm and adfea minibatches formed on the device from raw text.
 //
 // The host reader (reader.h) tokenises, hashes and copies every row on CPU threads.  Here the
 // host's per-byte work is one copy of the raw chunk into pinned memory; the device parses it
-// (dfx_parse_criteo / dfx_parse_libsvm), the batch planner (reader.h BatchPlanner) runs on the
-// host from the parsed chunk's offsets and labels (12 bytes a row), and the row copies of the
-// plan run on the device (dfx_gather_rows) into a ring of device batches — the batches
-// BatchReader forms (src/reader/batch_reader.cc:29-78) for the chunks TextReader cuts
-// (src/reader/reader.h:18-55).
+// (dfx_parse_criteo / dfx_parse_libsvm / dfx_parse_adfea), the batch planner (reader.h
+// BatchPlanner) runs on the host from the parsed chunk's offsets and labels (12 bytes a row),
+// and the row copies of the plan run on the device (dfx_gather_rows) into a ring of device
+// batches — the batches BatchReader forms (src/reader/batch_reader.cc:29-78) for the chunks
+// TextReader cuts (src/reader/reader.h:18-55).
 //
 //   loader thread   TextReader::NextRaw -> parallel copy into a pinned text slot, counting
 //                   newlines (max_rows; 39 ids a row at most size the rest)
@@ -16,16 +16,19 @@
 //
 // A chunk the device flags (needs_host: the forms listed in include/difacto_amd.h) is parsed
 // by TextReader::ParseChunk on the host and uploaded into the same device arrays, values
-// included; FallbackChunks counts them.
+// included; FallbackChunks counts them.  So is an adfea chunk that needs more features than its
+// ':' bytes (the reader's bound, which holds inside the device's domain).
 //
 // The feed's format decides what its calls do; the reader only carries more data when the feed
-// is valued (libsvm: rows have any number of features and carry values).  The loader then also
-// counts the chunk's blanks, which bound its features; the reader mirrors row lengths and the
-// row flags the feed hands out (a row holding a value that is not 1.0f) through the GatherOps it
-// carries out, chunk -> shuffle buffer -> batch, so it knows every copy's nnz (the feed sizes
-// its arrays by it) and hands a batch out with values iff one of its rows is flagged:
-// BatchReader::Next's all-ones test (batch_reader.cc:71-73) with no device read-back.
-// criteo, criteo_test and libsvm only.
+// is sized (libsvm, adfea: rows have any number of features) or valued (libsvm: rows carry
+// values).  For a sized feed the loader also counts the bytes that bound the chunk's features
+// (libsvm: its blanks; adfea: its ':' bytes), and the reader mirrors row lengths through the
+// GatherOps it carries out, chunk -> shuffle buffer -> batch, so it knows every copy's nnz (the
+// feed sizes its arrays by it).  For a valued feed it mirrors the row flags the feed hands out
+// (a row holding a value that is not 1.0f) the same way and hands a batch out with values iff
+// one of its rows is flagged: BatchReader::Next's all-ones test (batch_reader.cc:71-73) with no
+// device read-back.  An adfea feed is binary: no flags, every batch handed out unvalued.
+// criteo, criteo_test, libsvm and adfea only.
 #ifndef DIFACTO_AMD_HOST_DEVICE_READER_H_
 #define DIFACTO_AMD_HOST_DEVICE_READER_H_
 
@@ -65,7 +68,8 @@ struct FeedProtocolError : std::logic_error {
 class DeviceTextFeed {
  public:
   static constexpr int kSlots = 3, kRing = 3;
-  /** format: "libsvm" makes a DFX_TEXT_LIBSVM feed, anything else a DFX_TEXT_CRITEO one.
+  /** format: "libsvm" makes a DFX_TEXT_LIBSVM feed, "adfea" a DFX_TEXT_ADFEA one, anything
+   * else a DFX_TEXT_CRITEO one.
    * nslots, nring: a caller that marks a batch `d` hand-outs late needs both >= d + 2 */
   DeviceTextFeed(dfx_ctx* ctx, size_t batch_size, size_t shuf_buf,
                  const std::string& format = "criteo", int nslots = kSlots, int nring = kRing);
@@ -76,7 +80,9 @@ class DeviceTextFeed {
   size_t batch_size() const { return batch_size_; }
   size_t shuf_buf() const { return shuf_buf_; }
   int format() const { return format_; }
+  /** rows carry values and flags (libsvm) / have an nnz capacity of their own (libsvm, adfea) */
   bool valued() const { return format_ == DFX_TEXT_LIBSVM; }
+  bool sized() const { return format_ != DFX_TEXT_CRITEO; }
   int nslots() const { return (int)slot_held_.size(); }
   int nring() const { return (int)ring_out_.size(); }
 
@@ -157,10 +163,10 @@ class DeviceBatchReader {
  private:
   struct Filled {
     int slot;
-    size_t bytes, newlines, blanks;
+    size_t bytes, newlines, blanks;  // blanks: the bound of a sized feed's features
   };
   void Gather(const GatherOp& op);  // one copy of the plan
-  size_t MirrorRows(const GatherOp& op, bool from_shuf);  // valued: its lengths and flags; nnz
+  size_t MirrorRows(const GatherOp& op, bool from_shuf);  // sized: its lengths (flags); nnz
   void Load();                  // the loader thread
   void SubmitFilled(bool wait); // queue the parses of the filled slots
   bool FetchChunk(size_t* rows, const uint64_t** off, const float** lab);
@@ -168,7 +174,7 @@ class DeviceBatchReader {
   DeviceTextFeed* feed_;
   dfx_textfeed* f_;
   TextReader reader_;
-  bool train_, valued_;
+  bool train_, sized_, valued_;
   size_t batch_size_;
   int nthreads_;
   std::unique_ptr<BatchPlanner> planner_;
@@ -184,8 +190,8 @@ class DeviceBatchReader {
   RowBlockContainer<feaid_t> host_blk_;  // a flagged chunk, parsed on the host
   const float* chunk_lab_ = nullptr;
   // the current chunk's offsets and row flags (the feed's pinned mirror; none on a Criteo
-  // feed); valued: the shuffle buffer's row lengths and flags, whether a flagged row went into
-  // the batch being formed
+  // feed); sized: the shuffle buffer's row lengths; valued: its flags, whether a flagged row
+  // went into the batch being formed
   const uint64_t* chunk_off_ = nullptr;
   const uint8_t* chunk_flag_ = nullptr;
   size_t chunk_rows_ = 0;

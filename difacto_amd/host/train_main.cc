@@ -1,12 +1,12 @@
 // train_main.cc — dfx_train: the reference's `difacto` executable for the SGD learner
 // (src/main.cc + SGDLearner::RunScheduler, src/sgd/sgd_learner.cc:51-117) on one GPU.
 //
-//   build/dfx_train data_in=FILE [data_val=FILE] [data_format=libsvm|criteo|criteo_test]
+//   build/dfx_train data_in=FILE [data_val=FILE] [data_format=libsvm|criteo|criteo_test|adfea]
 //                   [batch_size=100] [shuffle=10] [neg_sampling=1] [max_num_epochs=20]
 //                   [num_jobs_per_epoch=10] [stop_rel_objv=1e-5] [stop_val_auc=1e-5]
 //                   [model_in=F] [model_out=F]
 //                   [load_epoch=-1] [has_aux=0] [task=0|2] [pred_out=F] [pred_prob=1]
-//                   [fused=1] [nthreads=8] [parse=host|device|auto|auto-sharded]
+//                   [fused=1] [nthreads=8] [parse=host|device|auto|auto-sharded] [parse_adfea=0]
 //                   [cache=none|device|auto]
 //                   [cache_mb=16384] [cache_loc=0] [epoch_shuffle=0] [shuffle_seed=0]
 //                   [epoch_resample=0] [pred_write=host|device]
@@ -28,6 +28,13 @@
 // are) and the run is the single-GPU fused path, else the host reader; one line at the start
 // says which and why, e.g. "parse: device (libsvm)" or "parse: host (exchange=split)".
 // parse=device keeps its contract: Criteo formats only, anything else is an error.
+//
+// parse_adfea=1 (with data_format=adfea and parse=auto or parse=auto-sharded; anything else is
+// an error, exit 2) makes adfea a format with a device parser (dfx_parse_adfea: binary rows of
+// any length, batches handed out unvalued as BatchReader's are), so the two values then treat
+// it as they treat libsvm and print "parse: device (adfea)" or "parse: device (adfea, <n>
+// shards)".  Default 0: adfea is read by the host reader and the lines say "parse: host
+// (data_format=adfea)".
 //
 // parse=auto-sharded is parse=auto that takes the device parser in the sharded runs too
 // (shards=N, shards=-1, WORLD_SIZE > 1; both exchanges; pipelined=0|1; training, data_val

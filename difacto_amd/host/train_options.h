@@ -31,6 +31,7 @@ struct Param {
   double stop_rel_objv = 1e-5;
   double stop_val_auc = 1e-5;  // sgd_param.h:73
   std::string parse = "host";  // host|device|auto|auto-sharded
+  bool parse_adfea = false;    // adfea has a device parser too (under auto, auto-sharded)
   std::string cache = "none";  // none|device|auto
   int64_t cache_mb = 16384;    // its budget (per shard)
   bool cache_loc = false;      // the Localizer's outputs kept with the cached batches too
@@ -75,6 +76,7 @@ inline int ParseArgs(int argc, const char* const* argv, Param* Pp, KWArgs* rest,
     else if (k == "exchange") P.exchange = v;
     else if (k == "model_in_parts") P.model_in_parts = std::stoi(v);
     else if (k == "parse") P.parse = v;
+    else if (k == "parse_adfea") P.parse_adfea = std::stoi(v) != 0;
     else if (k == "cache") P.cache = v;
     else if (k == "cache_mb") P.cache_mb = std::stoll(v);
     else if (k == "cache_loc") P.cache_loc = std::stoi(v) != 0;
@@ -126,11 +128,11 @@ struct RunPlan {
 };
 
 /** Every option rule of dfx_train, in the order that decides which refusal wins: the parse
- * value, auto-sharded, auto, device; the cache value, cache_loc, epoch_shuffle, epoch_resample,
- * cache=device, cache=auto; the pred_write value, pred_write=device; the prediction inputs;
- * exchange.  The
- * lines resolved before a refusal stay in out_lines (main prints them first).  0, or 2 with the
- * message in err.  Prints nothing and reads no environment. */
+ * value, parse_adfea (the format, then the parse value), auto-sharded, auto, device; the cache
+ * value, cache_loc, epoch_shuffle, epoch_resample, cache=device, cache=auto; the pred_write
+ * value, pred_write=device; the prediction inputs; exchange.  The lines resolved before a
+ * refusal stay in out_lines (main prints them first).  0, or 2 with the message in err.  Prints
+ * nothing and reads no environment. */
 inline int ResolveOptions(const Param& P, const KWArgs& rest, const LaunchEnv& env, RunPlan* plan,
                           std::vector<std::string>* out_lines, std::string* err) {
   RunPlan& R = *plan;
@@ -150,10 +152,17 @@ inline int ResolveOptions(const Param& P, const KWArgs& rest, const LaunchEnv& e
     return 2;
   };
   const bool criteo = P.data_format == "criteo" || P.data_format == "criteo_test";
-  const bool dev_parser = criteo || P.data_format == "libsvm";
+  const bool dev_parser = criteo || P.data_format == "libsvm" ||
+                          (P.parse_adfea && P.data_format == "adfea");
 
   if (P.parse != "host" && P.parse != "device" && P.parse != "auto" && P.parse != "auto-sharded")
     return refuse("parse must be host, device, auto or auto-sharded", "");
+  if (P.parse_adfea) {  // no silent run on the host reader
+    const char* const what = "parse_adfea=1 needs ";
+    if (P.data_format != "adfea") return refuse(what, "data_format=adfea");
+    if (P.parse != "auto" && P.parse != "auto-sharded")
+      return refuse(what, "parse=auto or parse=auto-sharded");
+  }
   if (P.parse == "auto-sharded" && sharded) {
     // the device parser in the sharded run too, where the format has one
     if (R.print_rank)

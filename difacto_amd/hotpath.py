@@ -612,6 +612,32 @@ def parse_libsvm(ctx, data):
             labels[:rows].cpu().numpy(), rowflag[:rows].cpu().numpy(), stat)
 
 
+def parse_adfea(ctx, data):
+    """adfea text (whole lines, bytes) parsed on the device (dfx_parse_adfea, replacing the host
+    reader's ParseAdfea) -> (offs, ids, labels, stat): numpy arrays (uint64 offsets and ids
+    (idx << 12) | (gid & 4095), float32 labels) and stat = {rows, nnz, needs_host}.  needs_host:
+    the chunk holds a form the device leaves to the host parser (include/difacto_amd.h lists
+    them); the arrays are then None."""
+    data = bytes(data)
+    max_rows = data.count(b"\n") + 1
+    max_nnz = data.count(b" ") + data.count(b"\t") + 1  # a feature follows a blank
+    dev = ctx.device
+    text = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev) if data else None
+    offs = torch.empty(max_rows + 1, dtype=torch.int64, device=dev)
+    ids = torch.empty(max_nnz, dtype=torch.int64, device=dev)
+    labels = torch.empty(max_rows, dtype=torch.float32, device=dev)
+    stat_dev = torch.empty(4, dtype=torch.int64, device=dev)
+    check(_lib.lib().dfx_parse_adfea(ctx.h, _p(text), len(data), max_rows, max_nnz, _p(offs),
+                                     _p(ids), _p(labels), _p(stat_dev)))
+    st = (ctypes.c_int64 * 4)()
+    check(_lib.lib().dfx_parse_criteo_wait(ctx.h, _p(stat_dev), st))
+    rows, nnz = st[0], st[1]
+    stat = {"rows": rows, "nnz": nnz, "needs_host": bool(st[2])}
+    if stat["needs_host"]:
+        return None, None, None, stat
+    return u64(offs[:rows + 1]), u64(ids[:nnz]), labels[:rows].cpu().numpy(), stat
+
+
 def gather_rows_valued(ctx, src, rows=None, begin=0, n=None, dst=None, r0=0):
     """dfx_gather_rows_valued (the host reader's GatherRows with values and row flags) on device
     tensors.  src / dst: dicts of offs, ids (int64 holding the uint64 bits), vals (float32 or

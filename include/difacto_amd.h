@@ -219,13 +219,43 @@ int dfx_gather_rows_valued(dfx_ctx* ctx, const uint64_t* src_offset, const uint6
                            int64_t n, uint64_t* dst_offset, uint64_t* dst_index, float* dst_value,
                            float* dst_label, uint8_t* dst_rowflag, int64_t r0);
 
+/* ---- adfea text on the device (difacto_amd/csrc/adfeaparse.hip) --------------------------
+ * dfx_parse_adfea replaces the adfea branch of TextReader::ParseChunk (the host reader's
+ * ParseAdfea, difacto_amd/host/reader.cc; the reference's CTR format,
+ * src/reader/adfea_parser.h:34-84) for a chunk of whole lines text_dev[0, nbytes) in device
+ * memory: offset[rows + 1] (offset[0] == 0), index[nnz], label[rows]; the rows are binary.
+ * Parsed on the device: lines
+ *   blank* digits blank+ digits blank+ digits (blank+ digits ':' digits)* blank* '\n'
+ * with blank = ' ' | '\t'.  A line's tokens 0 and 1 (lineid, count) are checked and dropped;
+ * token 2 is the label, 1.0f iff its first byte is '1' (the reference's rule: "10" is 1, "01"
+ * is 0); every later token idx:gid is a feature (idx << 12) | (gid & 4095), idx and gid any run
+ * of digits, saturating to 2^64 - 1 as strtoull does, the shift wrapping mod 2^64 as the
+ * host's.  rows = newlines, nnz = tokens - 3 * rows.  Inside this domain ParseAdfea's result
+ * does not depend on where ParseChunk cuts the chunk for its threads (it cuts at newlines and
+ * the parser's token counter is back at 0 after every such line).  The result equals
+ * ParseAdfea's byte for byte, or the chunk is flagged: stat_dev[4] (device) = {rows, nnz,
+ * needs_host, overflow}, as dfx_parse_criteo's.
+ * needs_host == 1: the outputs are undefined and the host parses the chunk.  Only these forms
+ * may raise it: an empty or blank-only line; a line with fewer than three tokens; one of a
+ * line's first three tokens that is not digits (an "idx:gid" there is the host's row continued
+ * on the next line, which the device leaves to it); a later token that is not digits ':'
+ * digits; a token longer than 64 bytes; a '\r' byte anywhere; a last byte that is not '\n'.
+ * overflow == 1: the chunk needs more than max_rows rows or max_nnz features; rows / nnz hold
+ * the needed counts and nothing was written.  No byte outside the text is read, nothing past
+ * the capacities is written.  nbytes >= 2^31 is DFX_ERR_ARG.  Asynchronous on the context's
+ * input stream; dfx_parse_criteo_wait serves as the wait. */
+int dfx_parse_adfea(dfx_ctx* ctx, const char* text_dev, int64_t nbytes, int64_t max_rows,
+                    int64_t max_nnz, uint64_t* offset, uint64_t* index, float* label,
+                    int64_t* stat_dev);
+
 /* The text feed (difacto_amd/csrc/textfeed.hip): raw text to device batches
  * (src/reader/reader.h:18-55 + batch_reader.cc with the parsing and the row copies on the
  * device).  nslots pinned text slots, a loader stream that becomes the context's input stream,
  * one parsed chunk (device CSR + pinned copies of its offsets and labels) per slot, a shuffle
  * buffer of shuf_rows rows and a ring of nring device batches of batch_rows rows.  The format
- * (DFX_TEXT_CRITEO, DFX_TEXT_LIBSVM) is fixed at creation and every call below takes its
- * behaviour from the feed.  A Criteo feed holds 39 ids a row at most: rows size everything.
+ * (DFX_TEXT_CRITEO, DFX_TEXT_LIBSVM, DFX_TEXT_ADFEA) is fixed at creation and every call below
+ * takes its behaviour from the feed.  A Criteo feed holds 39 ids a row at most: rows size
+ * everything.
  *   dfx_textfeed_text      the slot's pinned text buffer, at least `bytes` long; fill it
  *   dfx_textfeed_submit    upload + the format's parser + the copies back, asynchronous
  *   dfx_textfeed_wait      join: stat[4] as dfx_parse_criteo_wait, the pinned offsets / labels
@@ -246,9 +276,14 @@ int dfx_gather_rows_valued(dfx_ctx* ctx, const uint64_t* src_offset, const uint6
  * three pinned arrays.  _batch_end / _slot_batch with valued == 0 hand out value == NULL: the
  * caller found no flagged row in the batch (batch_reader.cc:71-73).  On a Criteo feed a value
  * array, a gather's nnz != 0 and valued != 0 are DFX_ERR_ARG, as is an _upload with features
- * and no value array on a libsvm feed; a rejected call queues nothing. */
+ * and no value array on a libsvm feed; a rejected call queues nothing.
+ * A DFX_TEXT_ADFEA feed (dfx_parse_adfea) is sized by nnz as a libsvm feed is (the submit's
+ * max_nnz: the ':' bytes of a chunk inside the parser's domain bound its features, and a chunk
+ * that needs more is outside it; the growth; the nnz a gather says it appends) and binary as a
+ * Criteo feed is: no value arrays, no row flags, the pinned row flag pointers NULL, _upload
+ * takes value == NULL; a value array and valued != 0 are DFX_ERR_ARG. */
 typedef struct dfx_textfeed dfx_textfeed;
-enum { DFX_TEXT_CRITEO = 0, DFX_TEXT_LIBSVM = 1 };
+enum { DFX_TEXT_CRITEO = 0, DFX_TEXT_LIBSVM = 1, DFX_TEXT_ADFEA = 2 };
 int dfx_textfeed_create(dfx_ctx* ctx, int nslots, int nring, int64_t batch_rows,
                         int64_t shuf_rows, int format, dfx_textfeed** out);
 int dfx_textfeed_destroy(dfx_textfeed* f);
