@@ -42,7 +42,8 @@ all: $(LIB) $(DISTLIB) oracle $(HOSTBIN) $(TRAINBIN) $(READERBIN) $(GENBIN) $(CO
   $(TPBIN) $(LSBIN) $(ADBIN) $(SEBIN) $(SDBIN) $(SPBIN) build/expf_check build/strtof_check \
   build/gen_libsvm build/locbench \
   build/reshuffle_check build/resample_check build/fmtg_check build/train_options_tests \
-  build/train_options_resample_tests build/train_options_adfea_tests build/gen_adfea
+  build/train_options_resample_tests build/train_options_adfea_tests build/gen_adfea \
+  build/modeltext_check build/train_options_model_tests
 
 $(RBENCH): difacto_amd/host/reader.cc tools/reader_bench.cc difacto_amd/host/reader.h $(CITYHDR)
 	@mkdir -p build
@@ -81,6 +82,12 @@ build/train_options_adfea_tests: tests/host/train_options_adfea_tests.cc \
   difacto_amd/host/train_options.h difacto_amd/host/iface.h
 	@mkdir -p build
 	g++ $(HOSTFLAGS) -o $@ tests/host/train_options_adfea_tests.cc
+
+# ... and model_write's and task=1's, behind every older rule
+build/train_options_model_tests: tests/host/train_options_model_tests.cc \
+  difacto_amd/host/train_options.h difacto_amd/host/iface.h
+	@mkdir -p build
+	g++ $(HOSTFLAGS) -o $@ tests/host/train_options_model_tests.cc
 
 # the device text parser, the row gather and DeviceBatchReader against the host reader
 # (dfx_parse_criteo / dfx_gather_rows vs ParseCriteo / GatherRows / BatchReader), plus the CPU
@@ -124,6 +131,12 @@ build/resample_check: tools/resample_check.cc $(CSRC)/reshuffle.h
 # test infrastructure: csrc/fmtg.h (the device prediction writer's rows) against the host's
 # snprintf("%g") and the driver's probability expression; also writes the GPU tests' expected text
 build/fmtg_check: tools/fmtg_check.cc $(CSRC)/fmtg.h $(CSRC)/expf.h
+	@mkdir -p build
+	g++ -std=c++17 -O2 -Wall -ffp-contract=off -o $@ $<
+
+# test infrastructure: csrc/modeltext.h (the device model dump's lines) against a std::ostream
+build/modeltext_check: tools/modeltext_check.cc $(CSRC)/modeltext.h $(CSRC)/fmtg.h \
+  $(CSRC)/revbytes.h $(CSRC)/expf.h
 	@mkdir -p build
 	g++ -std=c++17 -O2 -Wall -ffp-contract=off -o $@ $<
 
@@ -217,8 +230,12 @@ build/expf_check: tools/expf_check.hip $(CSRC)/expf.h
 	@mkdir -p build
 	$(HIPCC) --offload-arch=$(ARCH) -O2 -ffp-contract=off -o $@ $<
 
+# measurement: the model files' host writers against the device writers, A B B A (needs a GPU)
+model_write_ab: $(LIB)
+	python tools/model_write_ab.py
+
 clean:
 	rm -rf build $(LIB) $(DISTLIB)
 	$(MAKE) -s -C oracle clean
 
-.PHONY: all oracle clean
+.PHONY: all oracle clean model_write_ab

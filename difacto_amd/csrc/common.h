@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "revbytes.h"
+
 namespace dfx {
 
 constexpr int kWave = 64;
@@ -52,14 +54,12 @@ constexpr uint64_t kEmptyKey = ~0ull;  // never produced by the Localizer (see D
 // skips it — no update ever lands in another key's entry
 constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
 
-// include/difacto/base.h:39-51 — nibble reversal (involution).
-__host__ __device__ inline uint64_t reverse_bytes(uint64_t x) {
-  x = x << 32 | x >> 32;
-  x = (x & 0x0000FFFF0000FFFFull) << 16 | (x & 0xFFFF0000FFFF0000ull) >> 16;
-  x = (x & 0x00FF00FF00FF00FFull) << 8 | (x & 0xFF00FF00FF00FF00ull) >> 8;
-  x = (x & 0x0F0F0F0F0F0F0F0Full) << 4 | (x & 0xF0F0F0F0F0F0F0F0ull) >> 4;
-  return x;
-}
+// reverse_bytes (include/difacto/base.h:39-51): the nibble reversal that turns a feature id
+// into the key the store holds, and back (an involution).  It is revbytes.h's, included above:
+// the model dump prints keys through it under need_reverse, and the host tool that holds the
+// dump's text to a std::ostream (tools/modeltext_check.cc) is built by plain g++, which cannot
+// read this header (hip_runtime.h).  One text for the kernels and for such tools; every use
+// here is unchanged (localize.hip, locbucket.hip, fm.hip, split.hip, store.hip).
 
 __device__ inline int lane_id() { return threadIdx.x & (kWave - 1); }
 

@@ -29,6 +29,20 @@ int DevBuf::ensure(size_t n) {
   return DFX_OK;
 }
 
+void MfStaging::release() {
+  for (int k = 0; k < 2; ++k) {
+    if (dev[k]) (void)hipFree(dev[k]);
+    if (host[k]) (void)hipHostFree(host[k]);
+    if (ev[k]) (void)hipEventDestroy(ev[k]);
+    dev[k] = host[k] = nullptr;
+    ev[k] = nullptr;
+  }
+  if (stat_dev) (void)hipFree(stat_dev);
+  if (stat_host) (void)hipHostFree(stat_host);
+  stat_dev = stat_host = nullptr;
+  cap_bytes = 0;
+}
+
 void DevBuf::release() {
   if (p) (void)hipFree(p);
   p = nullptr;
@@ -378,8 +392,10 @@ int dfx_ctx_destroy(dfx_ctx* ctx) {
   release_ws(c->aws_alt);
   release_ws(c->uws);
   for (DevBuf* b : {&c->tp_tiles, &c->tp_cells, &c->tp_lines, &c->tp_pair, &c->tp_tot,
-                    &c->tp_stat, &c->tg_len, &c->tg_tot, &c->pt_rec, &c->pt_tot})
+                    &c->tp_stat, &c->tg_len, &c->tg_tot, &c->pt_rec, &c->pt_tot,
+                    &c->mf_tot})
     b->release();
+  c->mf_stage.release();
   for (auto h : c->dist_host)
     if (h) (void)hipHostFree(h);
   for (hipEvent_t e : {c->ev_in, c->ev_fwd, c->ev_auc, c->ev_auc_p[0], c->ev_auc_p[1]})

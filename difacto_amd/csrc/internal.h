@@ -153,6 +153,17 @@ struct Workspace {
 
 struct Context;
 
+// staging of dfx_store_save_dev / dfx_store_dump_dev (modelfile.hip); ctx.hip frees it
+struct MfStaging {
+  char* dev[2] = {nullptr, nullptr};
+  char* host[2] = {nullptr, nullptr};  // pinned
+  int64_t* stat_dev = nullptr;         // 2 x 4 status words
+  int64_t* stat_host = nullptr;        // pinned
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  int64_t cap_bytes = 0;               // of each of the four buffers
+  void release();
+};
+
 // Growth without a stall per step: every step records a D2H copy of {n_keys, n_vrows} and an
 // event; a new step's inserts are bounded by its nnz, so the host knows an upper bound of the
 // counts when it enqueues, from the latest completed record plus the bounds enqueued since.
@@ -226,6 +237,11 @@ struct Context {
   // scratch of the prediction formatter (predtext.hip), used in the context stream's order: a
   // 32-byte record per row, the tile totals
   DevBuf pt_rec, pt_tot;
+  // the model file writers (modelfile.hip), in the context stream's order: the tile totals of
+  // a chunk, and the two staging buffers with their pinned mirrors, status words and events,
+  // made by the first dfx_store_save_dev / _dump_dev call and kept for the next
+  DevBuf mf_tot;
+  MfStaging mf_stage;
   Workspace bws[kSlots];  // [0], [1]: also the fused step's Localizer parities
   DevState* bds[kSlots] = {};
   Workspace aws;
@@ -571,6 +587,12 @@ int cap_record_commit(Context* c, hipEvent_t* recorded = nullptr);
 void cap_release(Context* c);
 // at a sync point (the stream is idle): grow the table once its load passes 0.5
 int store_maybe_grow(Context* c);
+// dfx_store_dump's lines of the entries in slots [s0, s0 + ns), by the host loop itself, into
+// *out (store.hip; modelfile.hip's stand-in for a chunk the device did not format).  *pool: the
+// split layout's V pool on the host, copied while it is empty and kept for the caller's next
+// range; blocking copies
+int store_dump_range(Context* c, int64_t s0, int64_t ns, int dump_aux, int need_reverse,
+                     std::vector<float>* pool, std::string* out);
 
 // InitV ranked over all owners of a sharded model (initv.hip), for the raw 0 / 1 flags of any
 // owner step (per unique key, key order; nuniq: their device count, NULL: bound): count writes

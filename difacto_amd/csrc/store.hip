@@ -637,23 +637,24 @@ __global__ void k_probe_stats(Table T, int64_t cap, unsigned long long* out) {
   }
 }
 
-// Every stored entry with its V and Vaux rows (null without V), in slot order, for save /
-// dump.  Fat slots stream the table in chunks of kHostChunk slots (a key's V and Vaux rows are
-// its slot's, so a chunk carries them); the split layout copies the entries and the used V pool
-// rows once (V rows are in allocation order, not slot order).
+// Every stored entry of slots [s0, s0 + ns) with its V and Vaux rows (null without V), in slot
+// order, for save / dump.  Fat slots stream the range in chunks of kHostChunk slots (a key's V
+// and Vaux rows are its slot's, so a chunk carries them); the split layout copies the range's
+// entries and the used V pool rows (V rows are in allocation order, not slot order) - into
+// *pool when the caller keeps one across calls (it is copied while it is empty: at most once).
 constexpr int64_t kHostChunk = 1 << 20;
 
 template <typename F>
-static int for_each_entry(Context* c, F fn) {
+static int for_each_entry(Context* c, int64_t s0, int64_t ns, std::vector<float>* pool, F fn) {
   const Table& T = c->T;
   const int d = T.d;
   HostCounters hc;
   DFX_TRY(read_counters(c, &hc));
   if (T.es) {
-    std::vector<Entry> raw((size_t)std::min<int64_t>(c->cap, kHostChunk) << T.es);
-    std::vector<float> aux((size_t)std::min<int64_t>(c->cap, kHostChunk) * d);
-    for (int64_t i0 = 0; i0 < c->cap; i0 += kHostChunk) {
-      const int64_t n = std::min<int64_t>(kHostChunk, c->cap - i0);
+    std::vector<Entry> raw((size_t)std::min<int64_t>(ns, kHostChunk) << T.es);
+    std::vector<float> aux((size_t)std::min<int64_t>(ns, kHostChunk) * d);
+    for (int64_t i0 = s0; i0 < s0 + ns; i0 += kHostChunk) {
+      const int64_t n = std::min<int64_t>(kHostChunk, s0 + ns - i0);
       DFX_HIP(hipMemcpy(raw.data(), ent_at(T, i0), ((size_t)n << T.es) * sizeof(Entry),
                         hipMemcpyDeviceToHost));
       if (d > 0)
@@ -668,16 +669,49 @@ static int for_each_entry(Context* c, F fn) {
     }
     return DFX_OK;
   }
-  std::vector<Entry> ent((size_t)c->cap);
-  std::vector<float> VV((size_t)hc.n_vrows * 2 * d);  // [V(d) | Vaux(d)] per V row
-  DFX_HIP(hipMemcpy(ent.data(), T.ent, c->cap * sizeof(Entry), hipMemcpyDeviceToHost));
-  if (!VV.empty()) DFX_HIP(hipMemcpy(VV.data(), T.V, VV.size() * 4, hipMemcpyDeviceToHost));
+  std::vector<Entry> ent((size_t)ns);
+  std::vector<float> own;
+  std::vector<float>& VV = pool ? *pool : own;  // [V(d) | Vaux(d)] per V row
+  if (ns > 0)
+    DFX_HIP(hipMemcpy(ent.data(), T.ent + s0, ns * sizeof(Entry), hipMemcpyDeviceToHost));
+  if (VV.empty()) {
+    VV.resize((size_t)hc.n_vrows * 2 * d);
+    if (!VV.empty()) DFX_HIP(hipMemcpy(VV.data(), T.V, VV.size() * 4, hipMemcpyDeviceToHost));
+  }
   for (const Entry& e : ent) {
     if (e.key == kEmptyKey) continue;
     const bool v = e.vrow >= 0;
     fn(e, v ? VV.data() + (size_t)e.vrow * 2 * d : nullptr,
        v ? VV.data() + (size_t)e.vrow * 2 * d + d : nullptr);
   }
+  return DFX_OK;
+}
+
+// SGDUpdater::Dump's lines (sgd_updater.h:108-139) of the entries in slots [s0, s0 + ns)
+template <typename OS>
+static int dump_entries(Context* c, int64_t s0, int64_t ns, int dump_aux, int need_reverse,
+                        std::vector<float>* pool, OS& os) {
+  const int d = c->T.d;
+  return for_each_entry(c, s0, ns, pool, [&](const Entry& e, const float* V, const float* C) {
+    const int size = V ? 1 + d : 1;
+    if (e.w == 0.f && size == 1) return;
+    os << (need_reverse ? reverse_bytes(e.key) : (uint64_t)e.key);
+    os << '\t' << size << '\t' << e.w;
+    if (dump_aux) os << '\t' << e.sqrt_g << '\t' << e.z;
+    if (size > 1) {
+      for (int k = 0; k < d; ++k) os << '\t' << V[k];
+      if (dump_aux)
+        for (int k = 0; k < d; ++k) os << '\t' << C[k];
+    }
+    os << '\n';
+  });
+}
+
+int store_dump_range(Context* c, int64_t s0, int64_t ns, int dump_aux, int need_reverse,
+                     std::vector<float>* pool, std::string* out) {
+  std::ostringstream os;
+  DFX_TRY(dump_entries(c, s0, ns, dump_aux, need_reverse, pool, os));
+  *out = os.str();
   return DFX_OK;
 }
 
@@ -867,7 +901,8 @@ int dfx_store_save(dfx_ctx* ctx, const char* path, int save_aux) {
   if (!f) { set_error(std::string("cannot open ") + path); return DFX_ERR_IO; }
   bool aux = save_aux != 0;
   fwrite(&aux, sizeof(bool), 1, f);
-  const int rc = for_each_entry(c, [&](const Entry& e, const float* V, const float* C) {
+  const int rc = for_each_entry(c, 0, c->cap, nullptr, [&](const Entry& e, const float* V,
+                                                           const float* C) {
     const int size = V ? 1 + d : 1;
     if (e.w == 0.f && size == 1) return;  // SGDEntry::empty()
     const uint64_t key = e.key;
@@ -991,22 +1026,9 @@ int dfx_store_load_part(dfx_ctx* ctx, const char* path, int rank, int nranks) {
 int dfx_store_dump(dfx_ctx* ctx, const char* path, int dump_aux, int need_reverse) {
   DFX_CHECK_ARG(ctx && path, "null argument");
   Context* c = &ctx->c;
-  const int d = c->T.d;
   std::ofstream os(path);
   if (!os) { set_error(std::string("cannot open ") + path); return DFX_ERR_IO; }
-  return for_each_entry(c, [&](const Entry& e, const float* V, const float* C) {
-    const int size = V ? 1 + d : 1;
-    if (e.w == 0.f && size == 1) return;
-    os << (need_reverse ? reverse_bytes(e.key) : (uint64_t)e.key);
-    os << '\t' << size << '\t' << e.w;
-    if (dump_aux) os << '\t' << e.sqrt_g << '\t' << e.z;
-    if (size > 1) {
-      for (int k = 0; k < d; ++k) os << '\t' << V[k];
-      if (dump_aux)
-        for (int k = 0; k < d; ++k) os << '\t' << C[k];
-    }
-    os << '\n';
-  });
+  return dump_entries(c, 0, c->cap, dump_aux, need_reverse, nullptr, os);
 }
 
 }  // extern "C"

@@ -23,7 +23,7 @@ import torch
 
 from . import _lib
 from ._lib import check
-from .hotpath import MAX_INDEX, kTraining, kValidation, _p  # noqa: F401
+from .hotpath import MAX_INDEX, Store, kTraining, kValidation, _p  # noqa: F401
 
 
 def owner_of(keys_u64, nranks):
@@ -242,9 +242,12 @@ class Shard:
                                               self.nranks))
 
     # model files (SGDLearner::SaveLoadModel, sgd_learner.cc:180-196) ---------------------------
-    def save(self, prefix, rank, save_aux=False, it=-1):
-        """this server's part, in SGDUpdater::Save's format (flush a pipeline first)"""
+    def save(self, prefix, rank, save_aux=False, it=-1, device=False):
+        """this server's part, in SGDUpdater::Save's format (flush a pipeline first).  device:
+        packed on the device (dfx_store_save_dev), the same bytes -> its stats"""
         self.ctx.sync()
+        if device:
+            return Store(self.ctx).save(model_name(prefix, rank, it), save_aux, device=True)
         check(_lib.lib().dfx_store_save(self.ctx.h, model_name(prefix, rank, it).encode(),
                                         int(save_aux)))
 

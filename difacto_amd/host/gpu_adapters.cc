@@ -3,12 +3,14 @@
 
 #include <chrono>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 
 #include <iterator>
 
 #include "reader.h"
 
+#include <sys/stat.h>
 #include <unistd.h>
 
 #include <algorithm>
@@ -324,6 +326,80 @@ void GpuSGDUpdater::Dump(bool dump_aux, bool need_reverse, Stream* fo) const {
   std::vector<char> buf((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
   if (!buf.empty()) fo->Write(buf.data(), buf.size());
   unlink(path);
+}
+
+namespace {
+double WallNow() {
+  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch())
+      .count();
+}
+
+// a written file's size
+int64_t FileBytes(const std::string& path) {
+  struct stat sb;
+  DFX_HOST_CHECK(stat(path.c_str(), &sb) == 0, "cannot stat the model file");
+  return (int64_t)sb.st_size;
+}
+
+// a written text's lines (outside the writer's timed span)
+int64_t FileLines(const std::string& path) {
+  FILE* f = std::fopen(path.c_str(), "rb");
+  DFX_HOST_CHECK(f != nullptr, "cannot reopen the model file");
+  std::vector<char> buf(1 << 20);
+  int64_t nl = 0;
+  size_t n;
+  while ((n = std::fread(buf.data(), 1, buf.size(), f)) > 0)
+    for (size_t i = 0; i < n; ++i) nl += buf[i] == '\n';
+  std::fclose(f);
+  return nl;
+}
+
+ModelWriteStats DeviceWriteStats(const int64_t* s, const double* t, double seconds) {
+  ModelWriteStats st;
+  st.entries = s[0];
+  st.bytes = s[1];
+  st.chunks = s[2];
+  st.host_chunks = s[3];
+  st.wait_s = t[0];
+  st.write_s = t[1];
+  st.seconds = seconds;
+  return st;
+}
+}  // namespace
+
+ModelWriteStats GpuSGDUpdater::SaveFile(const std::string& path, bool save_aux,
+                                        bool device) const {
+  const double t0 = WallNow();
+  if (device) {
+    int64_t s[4];
+    double t[2];
+    DfxCheck(dfx_store_save_dev(ctx_->h(), path.c_str(), save_aux, 0, s, t),
+             "dfx_store_save_dev");
+    return DeviceWriteStats(s, t, WallNow() - t0);
+  }
+  ModelWriteStats st;
+  DfxCheck(dfx_store_save(ctx_->h(), path.c_str(), save_aux), "dfx_store_save");
+  st.seconds = WallNow() - t0;
+  st.bytes = FileBytes(path);
+  return st;
+}
+
+ModelWriteStats GpuSGDUpdater::DumpFile(const std::string& path, bool dump_aux,
+                                        bool need_reverse, bool device) const {
+  const double t0 = WallNow();
+  if (device) {
+    int64_t s[4];
+    double t[2];
+    DfxCheck(dfx_store_dump_dev(ctx_->h(), path.c_str(), dump_aux, need_reverse, 0, s, t),
+             "dfx_store_dump_dev");
+    return DeviceWriteStats(s, t, WallNow() - t0);
+  }
+  ModelWriteStats st;
+  DfxCheck(dfx_store_dump(ctx_->h(), path.c_str(), dump_aux, need_reverse), "dfx_store_dump");
+  st.seconds = WallNow() - t0;
+  st.bytes = FileBytes(path);
+  st.entries = FileLines(path);  // (the host writer does not count: read back, untimed)
+  return st;
 }
 
 // ---- Store -------------------------------------------------------------------------------

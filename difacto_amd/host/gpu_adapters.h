@@ -116,6 +116,15 @@ class GpuFMLoss : public Loss {
   std::shared_ptr<Dev> dev_;
 };
 
+/** what SaveFile / DumpFile wrote.  The device writers count everything; the host writers give
+ * the file's bytes (its size), DumpFile its lines too (SaveFile: entries = -1, not counted).
+ * seconds: the writer's call alone, not the counting */
+struct ModelWriteStats {
+  int64_t entries = -1, bytes = 0, chunks = 0, host_chunks = 0;
+  double wait_s = 0, write_s = 0;  // host seconds waiting for a chunk, and writing
+  double seconds = 0;
+};
+
 /** SGDUpdater (FTRL w, AdaGrad V, V_threshold InitV) with its model in HBM */
 class GpuSGDUpdater : public Updater {
  public:
@@ -124,6 +133,12 @@ class GpuSGDUpdater : public Updater {
   void Load(Stream* fi) override;
   void Save(bool save_aux, Stream* fo) const override;
   void Dump(bool dump_aux, bool need_reverse, Stream* fo) const override;
+  /** Save and Dump straight to a path, with no Stream and no temporary file between: by the
+   * device writers (dfx_store_save_dev / dfx_store_dump_dev) or, device = false, by the host
+   * writers (dfx_store_save / dfx_store_dump).  The same bytes either way. */
+  ModelWriteStats SaveFile(const std::string& path, bool save_aux, bool device) const;
+  ModelWriteStats DumpFile(const std::string& path, bool dump_aux, bool need_reverse,
+                           bool device) const;
   void Get(const SArray<feaid_t>& fea_ids, int data_type, SArray<real_t>* data,
            SArray<int>* data_offset) override;
   void Update(const SArray<feaid_t>& fea_ids, int data_type, const SArray<real_t>& data,

@@ -5,11 +5,12 @@
 //                   [batch_size=100] [shuffle=10] [neg_sampling=1] [max_num_epochs=20]
 //                   [num_jobs_per_epoch=10] [stop_rel_objv=1e-5] [stop_val_auc=1e-5]
 //                   [model_in=F] [model_out=F]
-//                   [load_epoch=-1] [has_aux=0] [task=0|2] [pred_out=F] [pred_prob=1]
+//                   [load_epoch=-1] [has_aux=0] [task=0|1|2] [pred_out=F] [pred_prob=1]
 //                   [fused=1] [nthreads=8] [parse=host|device|auto|auto-sharded] [parse_adfea=0]
 //                   [cache=none|device|auto]
 //                   [cache_mb=16384] [cache_loc=0] [epoch_shuffle=0] [shuffle_seed=0]
-//                   [epoch_resample=0] [pred_write=host|device]
+//                   [epoch_resample=0] [pred_write=host|device] [model_write=host|device]
+//                   [name_dump=dump.txt] [need_reverse=0] [dump_aux=0]
 //                   [V_dim=..] [lr=..] [l1=..] ... (SGDUpdaterParam)
 //
 // What each option does is described below.  The rules themselves — which combinations are
@@ -136,6 +137,31 @@
 // an error (exit 2, before any context exists); without task=2 it is accepted and does
 // nothing.  Default host: the run as without it.
 //
+// model_write=device (with model_out; the single-GPU run with either fused value, and the
+// sharded runs with both exchanges): every <model_out>_part-<rank> is packed on the device
+// (GpuSGDUpdater::SaveFile, dfx_store_save_dev; csrc/modelfile.hip) instead of the host's walk
+// over a copy of the whole table with a few fwrite calls of 4 to 8 bytes per entry: the table is
+// read in chunks of slots where it lies, a chunk's records come down in one copy and are written
+// with one fwrite while the next chunk is packed, and in the single-GPU run the file is written
+// straight to its path (the default goes through a temporary file and a copy of it in memory).
+// The file is the host writer's byte for byte.  One line after the save gives the entries, the
+// MB, the seconds and the seconds the host waited for chunks.  A value other than host or device
+// is an error (exit 2); without model_out it is accepted and does nothing.  Default host: the
+// run as without it.
+//
+// task=1 (src/main.cc:81-87 with src/reader/dump.h) dumps a model as text: model_in, the literal
+// file (not a prefix: dump.h:55-56 opens it as it is named), is loaded (V_dim as for task=2; a
+// mismatch is the loader's error) and written to name_dump (default dump.txt) in
+// SGDUpdater::Dump's lines, key \t size \t w [\t sqrt_g \t z] [\t V..] [\t Vaux..], the
+// bracketed state under dump_aux=1 and the key nibble-reversed back to the feature id under
+// need_reverse=1.  data_in is not needed.  model_write names the writer: host is dfx_store_dump's
+// loop, device formats the lines on the device (dfx_store_dump_dev; csrc/modeltext.h prints a
+// float as operator<< does through csrc/fmtg.h) - the same bytes: a chunk of slots holding a
+// float the device does not format (not finite, a float subnormal, outside 1e-14 <= |x| < 1e12)
+// is written by the host loop in its place, and the count of such chunks is printed when it is
+// not zero.  It prints "Dump: <entries> entries, <bytes> bytes in <s> s".  Without model_in
+// ("dump needs model_in") or in a sharded invocation it is an error (exit 2).
+//
 // Sharded store (KVStoreDist over GPUs, dist_host.h): `shards=N` holds N shards on this GPU
 // (loopback exchange, for tests); `shards=-1` or a launch with WORLD_SIZE > 1 (RANK / LOCAL_RANK as
 // torchrun sets them; DFX_COMM_ID_FILE or /tmp/dfx_comm_<MASTER_PORT> as the node-local
@@ -219,6 +245,14 @@ void PrintPredWriteLine(const DevicePredWriter::Stats& st, double pass_s) {
     std::printf("pred_write=device: %lld batch%s written by the host (a row outside the device "
                 "formatter's domain)\n",
                 (long long)st.host_batches, st.host_batches == 1 ? "" : "es");
+}
+
+// model_write=device, after the save: what the device writer did (a sharded run: this process's
+// shards)
+void PrintModelWriteLine(const ModelWriteStats& st, double seconds) {
+  std::printf("model_write=device: %lld entries, %.1f MB in %.3f s, the host waited %.3f s for "
+              "chunks\n",
+              (long long)st.entries, (double)st.bytes / (1 << 20), seconds, st.wait_s);
 }
 
 // the batch cache's list of a part: one per (job kind, part)
@@ -1095,13 +1129,44 @@ int RunSharded(const Param& P, const KWArgs& rest, const LaunchEnv& env, const R
     if (ShouldStop(tr, va, &pre_loss, &pre_val_auc, P, false)) break;
   }
   run->Flush();
-  if (!P.model_out.empty())
+  if (!P.model_out.empty()) {
+    ModelWriteStats sum;  // model_write=device: this process's shards
+    sum.entries = 0;
+    const double t0 = Now();
     for (int l = 0; l < nlocal; ++l) {
+      const std::string name = ModelNamePart(P.model_out, -1, run->rank(l));
       DfxCheck(dfx_sync(run->ctx(l)), "dfx_sync");
-      DfxCheck(dfx_store_save(run->ctx(l), ModelNamePart(P.model_out, -1, run->rank(l)).c_str(),
-                              P.has_aux ? 1 : 0),
-               "dfx_store_save");
+      if (plan.model_write_device) {
+        int64_t st[4];
+        double tm[2];
+        DfxCheck(dfx_store_save_dev(run->ctx(l), name.c_str(), P.has_aux ? 1 : 0, 0, st, tm),
+                 "dfx_store_save_dev");
+        sum.entries += st[0];
+        sum.bytes += st[1];
+        sum.wait_s += tm[0];
+      } else {
+        DfxCheck(dfx_store_save(run->ctx(l), name.c_str(), P.has_aux ? 1 : 0), "dfx_store_save");
+      }
     }
+    if (plan.model_write_device) PrintModelWriteLine(sum, Now() - t0);
+  }
+  return 0;
+}
+
+// task=1 (src/main.cc:81-87 with src/reader/dump.h): model_in, the literal file (dump.h:55-56
+// opens it as it is named), into name_dump as SGDUpdater::Dump's text
+int RunDump(const Param& P, KWArgs rest, const RunPlan& plan) {
+  if (!plan.fused_given) rest.push_back({"fused", "1"});
+  GpuSGDLearner learner(rest);  // (the context and its updater; nothing is trained)
+  DfxCheck(dfx_store_load(learner.context(), P.model_in.c_str()), "dfx_store_load");
+  const ModelWriteStats st = learner.updater()->DumpFile(P.name_dump, P.dump_aux, P.need_reverse,
+                                                         plan.model_write_device);
+  std::printf("Dump: %lld entries, %lld bytes in %.3f s\n", (long long)st.entries,
+              (long long)st.bytes, st.seconds);
+  if (plan.model_write_device && st.host_chunks)
+    std::printf("model_write=device: %lld of %lld chunk%s written by the host (a float outside "
+                "the device formatter's domain)\n",
+                (long long)st.host_chunks, (long long)st.chunks, st.chunks == 1 ? "" : "s");
   return 0;
 }
 
@@ -1249,7 +1314,13 @@ int RunSingle(const Param& P, KWArgs rest, const RunPlan& plan) {
     std::fflush(stdout);
     if (ShouldStop(tr, va, &pre_loss, &pre_val_auc, P, true)) break;
   }
-  if (!P.model_out.empty()) {  // sgd_learner.cc:116-120
+  if (!P.model_out.empty() && plan.model_write_device) {
+    // the same file with no Stream, temporary file or copy of it between (either fused value:
+    // the updater's own context holds the model)
+    const ModelWriteStats st =
+        learner.updater()->SaveFile(ModelName(P.model_out, -1), P.has_aux, true);
+    PrintModelWriteLine(st, st.seconds);
+  } else if (!P.model_out.empty()) {  // sgd_learner.cc:116-120
     FileStream fo(ModelName(P.model_out, -1).c_str(), "wb");
     learner.updater()->Save(P.has_aux, &fo);
   }
@@ -1274,5 +1345,6 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "%s\n", err.c_str());
     return rc;
   }
+  if (plan.dump) return RunDump(P, rest, plan);
   return plan.sharded ? RunSharded(P, rest, env, plan) : RunSingle(P, rest, plan);
 }

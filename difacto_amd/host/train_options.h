@@ -39,6 +39,10 @@ struct Param {
   uint64_t shuffle_seed = 0;   // ... keyed by (shuffle_seed, epoch, list)
   bool epoch_resample = false;  // ... and negatives are down-sampled afresh per epoch there
   std::string pred_write = "host";  // host|device
+  std::string model_write = "host";  // host|device: who lays down model_out / name_dump
+  // task=1 (src/reader/dump.h): model_in, the literal file, as text into name_dump
+  std::string name_dump = "dump.txt";
+  bool need_reverse = false, dump_aux = false;
 };
 
 /** argv into P; a key Param does not know goes to rest (the context's and the updater's).
@@ -84,9 +88,13 @@ inline int ParseArgs(int argc, const char* const* argv, Param* Pp, KWArgs* rest,
     else if (k == "shuffle_seed") P.shuffle_seed = std::stoull(v);
     else if (k == "epoch_resample") P.epoch_resample = std::stoi(v) != 0;
     else if (k == "pred_write") P.pred_write = v;
+    else if (k == "model_write") P.model_write = v;
+    else if (k == "name_dump") P.name_dump = v;
+    else if (k == "need_reverse") P.need_reverse = std::stoi(v) != 0;
+    else if (k == "dump_aux") P.dump_aux = std::stoi(v) != 0;
     else rest->push_back({k, v});
   }
-  if (P.data_in.empty() && P.task != 2) {
+  if (P.data_in.empty() && P.task != 2 && P.task != 1) {
     *err = std::string("usage: ") + argv[0] + " data_in=FILE [key=value ...]";
     return 2;
   }
@@ -124,13 +132,16 @@ struct RunPlan {
   bool cache_loc = false, epoch_shuffle = false;
   bool epoch_resample = false;  // every training epoch draws its negatives out of the full cache
   bool pred_write_device = false;
+  bool model_write_device = false;  // model_out / name_dump through the device writers
+  bool dump = false;                // task=1: load model_in, write name_dump, nothing else
   bool print_rank = true;  // rank 0, or an unsharded run: prints the run's lines
 };
 
 /** Every option rule of dfx_train, in the order that decides which refusal wins: the parse
  * value, parse_adfea (the format, then the parse value), auto-sharded, auto, device; the cache
  * value, cache_loc, epoch_shuffle, epoch_resample, cache=device, cache=auto; the pred_write
- * value, pred_write=device; the prediction inputs; exchange.  The lines resolved before a
+ * value, pred_write=device; the prediction inputs; exchange; the model_write value; task=1's
+ * inputs.  The lines resolved before a
  * refusal stay in out_lines (main prints them first).  0, or 2 with the message in err.  Prints
  * nothing and reads no environment. */
 inline int ResolveOptions(const Param& P, const KWArgs& rest, const LaunchEnv& env, RunPlan* plan,
@@ -253,6 +264,14 @@ inline int ResolveOptions(const Param& P, const KWArgs& rest, const LaunchEnv& e
     return refuse("prediction needs model_in and data_val", "");
   if (sharded && P.exchange != "a2a" && P.exchange != "split")
     return refuse("exchange must be a2a or split", "");
+  if (P.model_write != "host" && P.model_write != "device")
+    return refuse("model_write must be host or device", "");
+  R.model_write_device = P.model_write == "device";  // (without model_out: nothing to write)
+  R.dump = P.task == 1;
+  if (R.dump) {
+    if (P.model_in.empty()) return refuse("dump needs model_in", "");
+    if (sharded) return refuse("task=1 needs ", "the single-GPU run (shards=0)");
+  }
   return 0;
 }
 

@@ -261,15 +261,36 @@ class Store:
         check(_lib.lib().dfx_store_push(self.ctx.h, _p(keys), keys.numel(), int(val_type),
                                         _p(vals), vals.numel(), _p(lens)))
 
-    def save(self, path, save_aux=True):
+    def save(self, path, save_aux=True, device=False, chunk_slots=0):
+        """SGDUpdater::Save's file.  device: packed on the device (dfx_store_save_dev), the same
+        bytes -> its stats (model_write_stats)"""
+        if device:
+            st, tm = (ctypes.c_int64 * 4)(), (ctypes.c_double * 2)()
+            check(_lib.lib().dfx_store_save_dev(self.ctx.h, str(path).encode(), int(save_aux),
+                                                int(chunk_slots), st, tm))
+            return model_write_stats(st, tm)
         check(_lib.lib().dfx_store_save(self.ctx.h, str(path).encode(), int(save_aux)))
 
     def load(self, path):
         check(_lib.lib().dfx_store_load(self.ctx.h, str(path).encode()))
 
-    def dump(self, path, dump_aux=False, need_reverse=False):
+    def dump(self, path, dump_aux=False, need_reverse=False, device=False, chunk_slots=0):
+        """SGDUpdater::Dump's text.  device: formatted on the device (dfx_store_dump_dev), the
+        same bytes -> its stats; host_chunks counts the chunks the host loop wrote in the
+        device's place (an entry with a float outside csrc/fmtg.h's domain)"""
+        if device:
+            st, tm = (ctypes.c_int64 * 4)(), (ctypes.c_double * 2)()
+            check(_lib.lib().dfx_store_dump_dev(self.ctx.h, str(path).encode(), int(dump_aux),
+                                                int(need_reverse), int(chunk_slots), st, tm))
+            return model_write_stats(st, tm)
         check(_lib.lib().dfx_store_dump(self.ctx.h, str(path).encode(), int(dump_aux),
                                         int(need_reverse)))
+
+    def capacity(self):
+        """the table's slots (the range of model_pack / model_format and of chunk_slots)"""
+        cap = ctypes.c_int64(0)
+        check(_lib.lib().dfx_store_probe_stats(self.ctx.h, None, None, ctypes.byref(cap)))
+        return cap.value
 
     def stats(self):
         nk, nv, nw = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_double(0)
@@ -653,6 +674,38 @@ def gather_rows_valued(ctx, src, rows=None, begin=0, n=None, dst=None, r0=0):
     stat_dev = torch.zeros(4, dtype=torch.int64, device=ctx.device)
     st = (ctypes.c_int64 * 4)()
     check(_lib.lib().dfx_parse_criteo_wait(ctx.h, _p(stat_dev), st))
+
+
+def model_write_stats(st, tm):
+    """the four counts and the two host times of dfx_store_save_dev / _dump_dev"""
+    return {"entries": st[0], "bytes": st[1], "chunks": st[2], "host_chunks": st[3],
+            "wait_s": tm[0], "write_s": tm[1]}
+
+
+def _model_chunk(ctx, text, slot0, nslots, aux, need_reverse, out, cap_bytes):
+    stat_dev = torch.empty(4, dtype=torch.int64, device=ctx.device)
+    L = _lib.lib()
+    if text:
+        check(L.dfx_model_format(ctx.h, int(slot0), int(nslots), int(bool(aux)),
+                                 int(bool(need_reverse)), _p(out), int(cap_bytes), _p(stat_dev)))
+    else:
+        check(L.dfx_model_pack(ctx.h, int(slot0), int(nslots), int(bool(aux)), _p(out),
+                               int(cap_bytes), _p(stat_dev)))
+    ctx.sync()
+    return [int(x) for x in stat_dev.cpu().tolist()]
+
+
+def model_pack(ctx, slot0, nslots, save_aux, out, cap_bytes):
+    """dfx_model_pack: SGDUpdater::Save's records of table slots [slot0, slot0 + nslots) into
+    the uint8 device tensor out, no byte at or past cap_bytes -> [bytes needed, bytes written,
+    entries, 0]; joins the context stream"""
+    return _model_chunk(ctx, False, slot0, nslots, save_aux, False, out, cap_bytes)
+
+
+def model_format(ctx, slot0, nslots, dump_aux, need_reverse, out, cap_bytes):
+    """dfx_model_format: SGDUpdater::Dump's lines of those slots -> [bytes needed, bytes
+    written, entries, entries the device did not format (then the text is not to be used)]"""
+    return _model_chunk(ctx, True, slot0, nslots, dump_aux, need_reverse, out, cap_bytes)
 
 
 PRED_ROW_BYTES = 26  # a formatted prediction row at most (csrc/fmtg.h kMaxRow)

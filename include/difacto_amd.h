@@ -626,6 +626,50 @@ int dfx_store_load(dfx_ctx* ctx, const char* path);
  * loading every part */
 int dfx_store_load_part(dfx_ctx* ctx, const char* path, int rank, int nranks);
 int dfx_store_dump(dfx_ctx* ctx, const char* path, int dump_aux, int need_reverse);
+
+/* ---- model files written from the device (difacto_amd/csrc/modelfile.hip) ------------------
+ * The same two files as dfx_store_save and dfx_store_dump above, byte for byte, without the
+ * table crossing to the host slot by slot:
+ *   SGDUpdater::Save  src/sgd/sgd_updater.h:96-106 with SGDEntry::SaveEntry :35-48: per entry
+ *                     key(8) int size(4) w(4) [sqrt_g z] [V(d)] [Vaux(d)], an entry with
+ *                     w == 0.f and no V (SGDEntry::empty()) left out; one bool in front
+ *   SGDUpdater::Dump  src/sgd/sgd_updater.h:108-139: per entry the line
+ *                     key \t size \t w [\t sqrt_g \t z] [\t V..] [\t Vaux..] \n through
+ *                     operator<<, the key nibble-reversed first under need_reverse
+ * in the table's slot order, the host writers' order.  Floats print through csrc/fmtg.h, which
+ * is glibc's %g at precision 6 for +-0 and 1e-12 <= |x| < 1e12 (and answers for 1e-14 <= |x|);
+ * anything else - non-finite values, float subnormals, magnitudes outside - the device does
+ * not print: it flags the entry, and the chunk is written by the host loop in its place.
+ *
+ * dfx_model_pack / dfx_model_format run one chunk, slots [slot0, slot0 + nslots) of the table
+ * (dfx_store_probe_stats gives its capacity), into caller memory on the context stream.
+ * out_dev: device memory, dword aligned; no byte at or past cap_bytes is written.  stat_dev:
+ * four device words, final once the stream has passed the call:
+ *   [0] bytes the chunk needs   [1] bytes written (min of need and cap_bytes)
+ *   [2] entries in the chunk    [3] entries with a field the device did not format (format
+ *                                   only; when not 0 the text is not to be used)
+ * DFX_ERR_ARG: slots outside the table, cap_bytes < 0, out_dev not aligned, or nslots times
+ * the longest record / line for this V_dim beyond 32-bit offsets; a rejected call queues
+ * nothing.
+ *
+ * dfx_store_save_dev / dfx_store_dump_dev write the whole file: two staging buffers with pinned
+ * mirrors, chunk t + 1's kernels and chunk t's copy running while the host hands chunk t - 1
+ * to one fwrite.  chunk_slots = 0 takes the default, a fixed staging budget (64 MB a buffer)
+ * divided by the longest record or line for this V_dim; a larger request is cut to that, so
+ * device and pinned memory do not depend on the table's size.  The buffers are made by the
+ * context's first such call and kept for its next (freed with the context).  stats (may be
+ * NULL): [0] entries written, [1] the file's bytes, [2] chunks, [3] chunks written by the host
+ * loop (always 0 for save).  times (may be NULL): the host seconds this call [0] waited for a
+ * chunk and [1] spent writing (fwrite, a host-written chunk's loop, fclose).  They return with
+ * the file closed and the stream idle. */
+int dfx_model_pack(dfx_ctx* ctx, int64_t slot0, int64_t nslots, int save_aux, char* out_dev,
+                   int64_t cap_bytes, int64_t* stat_dev);
+int dfx_model_format(dfx_ctx* ctx, int64_t slot0, int64_t nslots, int dump_aux, int need_reverse,
+                     char* out_dev, int64_t cap_bytes, int64_t* stat_dev);
+int dfx_store_save_dev(dfx_ctx* ctx, const char* path, int save_aux, int64_t chunk_slots,
+                       int64_t* stats, double* times);
+int dfx_store_dump_dev(dfx_ctx* ctx, const char* path, int dump_aux, int need_reverse,
+                       int64_t chunk_slots, int64_t* stats, double* times);
 int dfx_store_stats(dfx_ctx* ctx, int64_t* n_keys, int64_t* n_vrows, double* new_w,
                     uint32_t* seed);
 /* table health: mean and longest distance of a stored key from its home slot; capacity in
