@@ -4,7 +4,10 @@
 // (from ARM's optimized-routines: x * 32 / ln2 = k + r, 2^(k/32) from a 32-entry table, a cubic
 // in r, all in double), in the form the x86-64 build dispatches to on FMA hardware (e_expf-fma:
 // the compiler contracts its multiply-adds, kd and r included).  tools/expf_check.hip compares
-// it with the host's expf on every float: identical on all 2^32 inputs.
+// the host compilation of this template with the host's expf on every float: identical on all
+// 2^32 inputs.  The device compilation (its own contraction, double -> float rounding into
+// subnormals, the constant-memory table, the early-out branches) is checked through CalcGrad's p
+// by tests/test_gpu_loss_edges.py::test_p_sweep, on both sides of every cut below.
 #pragma once
 #include <stdint.h>
 

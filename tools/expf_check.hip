@@ -1,5 +1,8 @@
 // Host check of difacto_amd/csrc/expf.h against the host's glibc expf on every float bit
-// pattern (the device evaluates the same template with the same table).  Test infrastructure:
+// pattern.  It runs the host compilation only: the device compiles the same template with the
+// same table, and tests/test_gpu_loss_edges.py::test_p_sweep is the check of that compilation
+// (every exponent, both sides of each early-out cut, subnormal results, +-inf, NaN, through
+// CalcGrad's p).  Test infrastructure:
 // build and run with  hipcc -O2 -ffp-contract=off tools/expf_check.hip -o build/expf_check
 #include <math.h>
 #include <stdio.h>
