@@ -234,8 +234,12 @@ build/expf_check: tools/expf_check.hip $(CSRC)/expf.h
 model_write_ab: $(LIB)
 	python tools/model_write_ab.py
 
+# measurement: the model file's host loader against the device loader, A B B A (needs a GPU)
+model_load_ab: $(LIB)
+	python tools/model_load_ab.py
+
 clean:
 	rm -rf build $(LIB) $(DISTLIB)
 	$(MAKE) -s -C oracle clean
 
-.PHONY: all oracle clean model_write_ab
+.PHONY: all oracle clean model_write_ab model_load_ab

@@ -89,6 +89,8 @@ _SIGS = {
     "dfx_store_save": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_int]),
     "dfx_store_load": (ctypes.c_int, [vp, ctypes.c_char_p]),
     "dfx_store_load_part": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_int, ctypes.c_int]),
+    "dfx_store_load_dev": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, c_i64,
+                                          i64p, f64p]),
     "dfx_store_dump": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_int, ctypes.c_int]),
     "dfx_model_pack": (ctypes.c_int, [vp, c_i64, c_i64, ctypes.c_int, vp, c_i64, vp]),
     "dfx_model_format": (ctypes.c_int, [vp, c_i64, c_i64, ctypes.c_int, ctypes.c_int, vp, c_i64,

@@ -99,6 +99,22 @@ __device__ inline uint32_t block_excl_scan(uint32_t v, uint32_t* lds, uint32_t* 
   return r;
 }
 
+// a block of kCountNT threads adds its lanes' v to *dst with one atomic (the store's insert
+// counts: store.hip's pushes and k_load, modelload.hip's insert pass)
+constexpr int kCountNT = 256;
+__device__ inline void block_count_add(int v, unsigned long long* dst) {
+  __shared__ int red[kCountNT / kWave];
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
+  if (lane_id() == 0) red[threadIdx.x / kWave] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int s = 0;
+    for (int i = 0; i < kCountNT / kWave; ++i) s += red[i];
+    if (s) atomicAdd(dst, (unsigned long long)(long long)s);
+  }
+  __syncthreads();
+}
+
 // ---- glibc rand_r (stdlib/rand_r.c): three LCG steps per call ------------------------
 constexpr uint32_t kLcgA = 1103515245u, kLcgC = 12345u;
 

@@ -43,6 +43,18 @@ void MfStaging::release() {
   cap_bytes = 0;
 }
 
+void MlStaging::release() {
+  for (int k = 0; k < 2; ++k) {
+    if (host[k]) (void)hipHostFree(host[k]);
+    if (ev[k]) (void)hipEventDestroy(ev[k]);
+    host[k] = nullptr;
+    ev[k] = nullptr;
+  }
+  if (res) (void)hipHostFree(res);
+  res = nullptr;
+  cap_bytes = 0;
+}
+
 void DevBuf::release() {
   if (p) (void)hipFree(p);
   p = nullptr;
@@ -396,6 +408,7 @@ int dfx_ctx_destroy(dfx_ctx* ctx) {
                     &c->mf_tot})
     b->release();
   c->mf_stage.release();
+  c->ml_stage.release();
   for (auto h : c->dist_host)
     if (h) (void)hipHostFree(h);
   for (hipEvent_t e : {c->ev_in, c->ev_fwd, c->ev_auc, c->ev_auc_p[0], c->ev_auc_p[1]})

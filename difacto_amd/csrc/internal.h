@@ -164,6 +164,16 @@ struct MfStaging {
   void release();
 };
 
+// staging of dfx_store_load_dev (modelload.hip): the two pinned buffers the file is read into,
+// their copies' events and the pinned verdict words; ctx.hip frees it
+struct MlStaging {
+  char* host[2] = {nullptr, nullptr};
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  unsigned long long* res = nullptr;
+  int64_t cap_bytes = 0;  // of each buffer
+  void release();
+};
+
 // Growth without a stall per step: every step records a D2H copy of {n_keys, n_vrows} and an
 // event; a new step's inserts are bounded by its nnz, so the host knows an upper bound of the
 // counts when it enqueues, from the latest completed record plus the bounds enqueued since.
@@ -242,6 +252,7 @@ struct Context {
   // made by the first dfx_store_save_dev / _dump_dev call and kept for the next
   DevBuf mf_tot;
   MfStaging mf_stage;
+  MlStaging ml_stage;  // the model file loader (modelload.hip), made by its first call
   Workspace bws[kSlots];  // [0], [1]: also the fused step's Localizer parities
   DevState* bds[kSlots] = {};
   Workspace aws;
@@ -575,6 +586,8 @@ __device__ inline void step_finalize_body(const FinArgs& f, uint32_t initv_n, do
 int push_cnt_seg_run(Context* c, int64_t n_bound, const uint32_t* segstart,
                      const uint32_t* segslot, uint32_t* flags, const DevState* nds);
 int store_reserve(Context* c, int64_t n_keys, int64_t n_vrows);
+// the device bytes that call would allocate, beside what the store holds now (0: nothing grows)
+int64_t store_reserve_bytes(const Context* c, int64_t n_keys, int64_t n_vrows);
 // before enqueueing work that inserts at most `add` keys (and draws at most `add` V rows):
 // make sure the table stays below 0.9 load and the V pool cannot overflow, growing at a sync
 // point when needed (kwarg autogrow=0: no-op).  cap_record after that work is enqueued.

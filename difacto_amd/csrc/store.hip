@@ -26,20 +26,7 @@
 
 namespace dfx {
 
-constexpr int kStNT = 256;
-
-__device__ inline void block_count_add(int v, unsigned long long* dst) {
-  __shared__ int red[kStNT / kWave];
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  if (lane_id() == 0) red[threadIdx.x / kWave] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int s = 0;
-    for (int i = 0; i < kStNT / kWave; ++i) s += red[i];
-    if (s) atomicAdd(dst, (unsigned long long)(long long)s);
-  }
-  __syncthreads();
-}
+constexpr int kStNT = kCountNT;  // (block_count_add: common.h)
 
 // ---- Update(kFeaCount) (sgd_updater.cc:64-75) ---------------------------------------------
 __device__ inline uint32_t feacnt_apply(const Table& T, const Params& P, int64_t s, float c) {
@@ -382,16 +369,38 @@ static int read_counters(Context* c, HostCounters* h) {
   return DFX_OK;
 }
 
+// what store_reserve(n_keys, n_vrows) builds: the table's capacity afterwards (the present one:
+// no rebuild), whether the split layout's V pool is replaced, and the device bytes the two
+// allocate (table_alloc_entries' slots and, with fat slots, their Vaux rows; the pool's rows) -
+// beside the old table and pool, which live until the new ones are filled
+struct ReservePlan {
+  int64_t cap;
+  bool pool;
+  int64_t bytes;
+};
+static ReservePlan reserve_plan(const Context* c, int64_t n_keys, int64_t n_vrows) {
+  const Table& T = c->T;
+  ReservePlan p{c->cap, false, 0};
+  while (p.cap < 2 * n_keys) p.cap <<= 1;
+  if (p.cap > c->cap)
+    p.bytes += p.cap * (int64_t)(sizeof(Entry) << T.es) +
+               (T.es ? p.cap * (int64_t)T.d * (int64_t)sizeof(float) : 0);
+  p.pool = T.d > 0 && !T.es && n_vrows > T.vcap;  // fat slots: V grows with the slots
+  if (p.pool) p.bytes += n_vrows * 2 * T.d * (int64_t)sizeof(float);
+  return p;
+}
+
+int64_t store_reserve_bytes(const Context* c, int64_t n_keys, int64_t n_vrows) {
+  return reserve_plan(c, n_keys, n_vrows).bytes;
+}
+
 int store_reserve(Context* c, int64_t n_keys, int64_t n_vrows) {
   DFX_HIP(hipStreamSynchronize(c->stream));
   Table& T = c->T;
   DFX_TRY(table_unclump(c));
-  if (2 * n_keys > c->cap) {
-    int64_t cap = c->cap;
-    while (cap < 2 * n_keys) cap <<= 1;
-    DFX_TRY(table_rebuild(c, T, cap));
-  }
-  if (T.d > 0 && !T.es && n_vrows > T.vcap) {  // fat slots: V grows with the slots
+  const ReservePlan plan = reserve_plan(c, n_keys, n_vrows);
+  if (plan.cap > c->cap) DFX_TRY(table_rebuild(c, T, plan.cap));
+  if (plan.pool) {
     HostCounters h;
     DFX_TRY(read_counters(c, &h));
     float* nV;

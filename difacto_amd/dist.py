@@ -251,10 +251,18 @@ class Shard:
         check(_lib.lib().dfx_store_save(self.ctx.h, model_name(prefix, rank, it).encode(),
                                         int(save_aux)))
 
-    def load(self, prefix, rank, it=-1, saved_ranks=None):
+    def load(self, prefix, rank, it=-1, saved_ranks=None, device=False):
         """this server's part.  saved_ranks (the number of servers that saved the model, when
-        it differs from this run's): read every part and keep the keys this rank owns"""
-        if saved_ranks is None or saved_ranks == self.nranks:
+        it differs from this run's): read every part and keep the keys this rank owns.  device:
+        the files are taken apart on the device (dfx_store_load_dev) -> a list of their stats"""
+        same = saved_ranks is None or saved_ranks == self.nranks
+        if device:
+            store = Store(self.ctx)
+            if same:
+                return [store.load(model_name(prefix, rank, it), device=True)]
+            return [store.load(model_name(prefix, r, it), device=True, rank=rank,
+                               nranks=self.nranks) for r in range(int(saved_ranks))]
+        if same:
             check(_lib.lib().dfx_store_load(self.ctx.h, model_name(prefix, rank, it).encode()))
             return
         for r in range(int(saved_ranks)):

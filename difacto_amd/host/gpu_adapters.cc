@@ -367,6 +367,33 @@ ModelWriteStats DeviceWriteStats(const int64_t* s, const double* t, double secon
 }
 }  // namespace
 
+ModelLoadStats LoadModelFile(dfx_ctx* ctx, const std::string& path, int rank, int nranks,
+                             bool device) {
+  ModelLoadStats st;
+  const double t0 = WallNow();
+  if (device) {
+    int64_t s[6];
+    double t[2];
+    DfxCheck(dfx_store_load_dev(ctx, path.c_str(), rank, nranks, 0, s, t), "dfx_store_load_dev");
+    st.records = s[0];
+    st.owned = s[1];
+    st.owned_v = s[2];
+    st.tiles = s[3];
+    st.tile_dwords = s[4];
+    st.host_loaded = s[5];
+    st.read_s = t[0];
+    st.wait_s = t[1];
+  } else {
+    DfxCheck(dfx_store_load_part(ctx, path.c_str(), rank, nranks), "dfx_store_load_part");
+  }
+  st.seconds = WallNow() - t0;
+  return st;
+}
+
+ModelLoadStats GpuSGDUpdater::Load(const std::string& path, bool device) {
+  return LoadModelFile(ctx_->h(), path, 0, 1, device);
+}
+
 ModelWriteStats GpuSGDUpdater::SaveFile(const std::string& path, bool save_aux,
                                         bool device) const {
   const double t0 = WallNow();

@@ -125,12 +125,35 @@ struct ModelWriteStats {
   double seconds = 0;
 };
 
+/** what LoadModelFile / GpuSGDUpdater::Load(path, device) read.  The device loader counts
+ * everything (dfx_store_load_dev's stats and times); the host loader gives the seconds alone
+ * (records = -1, not counted).  Add sums several files' counts and seconds; tiles and
+ * tile_dwords belong to one file (files of one run may differ in both) and stay out of it. */
+struct ModelLoadStats {
+  int64_t records = -1, owned = 0, owned_v = 0, tiles = 0, tile_dwords = 0, host_loaded = 0;
+  double read_s = 0, wait_s = 0;  // host seconds in fread, and waiting for the device
+  double seconds = 0;
+  void Add(const ModelLoadStats& o) {
+    records = (records < 0 ? 0 : records) + (o.records < 0 ? 0 : o.records);
+    owned += o.owned, owned_v += o.owned_v, host_loaded += o.host_loaded;
+    read_s += o.read_s, wait_s += o.wait_s, seconds += o.seconds;
+  }
+};
+/** one model file into a context's store, the keys rank of nranks owns: by the device loader
+ * (dfx_store_load_dev) or, device = false, the host loader (dfx_store_load_part).  The same
+ * store either way. */
+ModelLoadStats LoadModelFile(dfx_ctx* ctx, const std::string& path, int rank, int nranks,
+                             bool device);
+
 /** SGDUpdater (FTRL w, AdaGrad V, V_threshold InitV) with its model in HBM */
 class GpuSGDUpdater : public Updater {
  public:
   GpuSGDUpdater() {}
   KWArgs Init(const KWArgs& kwargs) override;
   void Load(Stream* fi) override;
+  /** Load straight from a path, with no Stream and no temporary file between: taken apart on
+   * the device or, device = false, by the host loader */
+  ModelLoadStats Load(const std::string& path, bool device);
   void Save(bool save_aux, Stream* fo) const override;
   void Dump(bool dump_aux, bool need_reverse, Stream* fo) const override;
   /** Save and Dump straight to a path, with no Stream and no temporary file between: by the

@@ -10,6 +10,7 @@
 //                   [cache=none|device|auto]
 //                   [cache_mb=16384] [cache_loc=0] [epoch_shuffle=0] [shuffle_seed=0]
 //                   [epoch_resample=0] [pred_write=host|device] [model_write=host|device]
+//                   [model_read=host|device]
 //                   [name_dump=dump.txt] [need_reverse=0] [dump_aux=0]
 //                   [V_dim=..] [lr=..] [l1=..] ... (SGDUpdaterParam)
 //
@@ -149,6 +150,18 @@
 // is an error (exit 2); without model_out it is accepted and does nothing.  Default host: the
 // run as without it.
 //
+// model_read=device (with model_in; the single-GPU run, the sharded runs with both exchanges
+// and model_in_parts, load_epoch, task=1 and task=2): every model file is taken apart on the
+// device (dfx_store_load_dev; csrc/modelload.hip) instead of the host's five to seven fread
+// calls of 4 or 8 bytes per record: the file is read once in large pieces into one device buffer,
+// cut into records by kernels, validated as a whole and then inserted - the store the host loader
+// leaves, with its errors.  In the single-GPU run the file is read straight from its path (the
+// default goes through a Stream and a temporary copy).  One line after the load gives the files,
+// the records, how many this process's stores kept, the seconds, the seconds in fread and the
+// seconds the host waited for the device; a file that did not fit beside its table was loaded by
+// the host and the line counts it.  A value other than host or device is an error (exit 2);
+// without model_in it is accepted and does nothing.  Default host: the run as without it.
+//
 // task=1 (src/main.cc:81-87 with src/reader/dump.h) dumps a model as text: model_in, the literal
 // file (not a prefix: dump.h:55-56 opens it as it is named), is loaded (V_dim as for task=2; a
 // mismatch is the loader's error) and written to name_dump (default dump.txt) in
@@ -253,6 +266,19 @@ void PrintModelWriteLine(const ModelWriteStats& st, double seconds) {
   std::printf("model_write=device: %lld entries, %.1f MB in %.3f s, the host waited %.3f s for "
               "chunks\n",
               (long long)st.entries, (double)st.bytes / (1 << 20), seconds, st.wait_s);
+}
+
+// model_read=device, after the load: what the device loader did with `files` files (a sharded
+// run: this process's shards)
+void PrintModelReadLine(const ModelLoadStats& st, int files) {
+  std::printf("model_read=device: %d file%s, %lld records, %lld kept, %.3f s (fread %.3f s, the "
+              "host waited %.3f s for the device)\n",
+              files, files == 1 ? "" : "s", (long long)st.records, (long long)st.owned,
+              st.seconds, st.read_s, st.wait_s);
+  if (st.host_loaded)
+    std::printf("model_read=device: %lld file%s loaded by the host (no room on the device beside "
+                "the table)\n",
+                (long long)st.host_loaded, st.host_loaded == 1 ? "" : "s");
 }
 
 // the batch cache's list of a part: one per (job kind, part)
@@ -1008,17 +1034,20 @@ int RunSharded(const Param& P, const KWArgs& rest, const LaunchEnv& env, const R
   const int nlocal = run->nlocal(), nshards = run->nranks(), rank = run->rank(0);
   if (!P.model_in.empty()) {
     const int it = P.load_epoch > 0 ? P.load_epoch : -1;
+    const bool dev = plan.model_read_device;
+    ModelLoadStats sum;  // model_read=device: this process's shards
+    int files = 0;
     for (int l = 0; l < nlocal; ++l) {
       if (P.model_in_parts <= 0 || P.model_in_parts == nshards) {
-        DfxCheck(dfx_store_load(run->ctx(l), ModelNamePart(P.model_in, it, run->rank(l)).c_str()),
-                 "dfx_store_load");
+        sum.Add(LoadModelFile(run->ctx(l), ModelNamePart(P.model_in, it, run->rank(l)), 0, 1, dev));
+        ++files;
       } else {  // saved by a different number of servers: keep the keys this shard owns
-        for (int r = 0; r < P.model_in_parts; ++r)
-          DfxCheck(dfx_store_load_part(run->ctx(l), ModelNamePart(P.model_in, it, r).c_str(),
-                                       run->rank(l), nshards),
-                   "dfx_store_load_part");
+        for (int r = 0; r < P.model_in_parts; ++r, ++files)
+          sum.Add(LoadModelFile(run->ctx(l), ModelNamePart(P.model_in, it, r), run->rank(l),
+                                nshards, dev));
       }
     }
+    if (dev) PrintModelReadLine(sum, files);
   }
   // parse=auto-sharded: one text feed per local shard on the shard's context, for the whole run.
   // Its loader stream is the context's input stream while it lives.  The feeds go before the
@@ -1158,7 +1187,9 @@ int RunSharded(const Param& P, const KWArgs& rest, const LaunchEnv& env, const R
 int RunDump(const Param& P, KWArgs rest, const RunPlan& plan) {
   if (!plan.fused_given) rest.push_back({"fused", "1"});
   GpuSGDLearner learner(rest);  // (the context and its updater; nothing is trained)
-  DfxCheck(dfx_store_load(learner.context(), P.model_in.c_str()), "dfx_store_load");
+  const ModelLoadStats ld = LoadModelFile(learner.context(), P.model_in, 0, 1,
+                                          plan.model_read_device);
+  if (plan.model_read_device) PrintModelReadLine(ld, 1);
   const ModelWriteStats st = learner.updater()->DumpFile(P.name_dump, P.dump_aux, P.need_reverse,
                                                          plan.model_write_device);
   std::printf("Dump: %lld entries, %lld bytes in %.3f s\n", (long long)st.entries,
@@ -1186,8 +1217,13 @@ int RunSingle(const Param& P, KWArgs rest, const RunPlan& plan) {
   std::vector<std::unique_ptr<DeviceReshuffler>> resh;
   int k0 = 0;
   if (!P.model_in.empty()) {  // sgd_learner.cc:58-67
-    FileStream fi(ModelName(P.model_in, P.load_epoch > 0 ? P.load_epoch : -1).c_str(), "rb");
-    learner.updater()->Load(&fi);
+    const std::string name = ModelName(P.model_in, P.load_epoch > 0 ? P.load_epoch : -1);
+    if (plan.model_read_device) {
+      PrintModelReadLine(learner.updater()->Load(name, true), 1);
+    } else {
+      FileStream fi(name.c_str(), "rb");
+      learner.updater()->Load(&fi);
+    }
     if (P.load_epoch > 0) k0 = P.load_epoch + 1;
   }
   if (P.task == 2) {  // prediction, sgd_learner.cc:69-77

@@ -40,6 +40,7 @@ struct Param {
   bool epoch_resample = false;  // ... and negatives are down-sampled afresh per epoch there
   std::string pred_write = "host";  // host|device
   std::string model_write = "host";  // host|device: who lays down model_out / name_dump
+  std::string model_read = "host";   // host|device: who takes model_in's files apart
   // task=1 (src/reader/dump.h): model_in, the literal file, as text into name_dump
   std::string name_dump = "dump.txt";
   bool need_reverse = false, dump_aux = false;
@@ -89,6 +90,7 @@ inline int ParseArgs(int argc, const char* const* argv, Param* Pp, KWArgs* rest,
     else if (k == "epoch_resample") P.epoch_resample = std::stoi(v) != 0;
     else if (k == "pred_write") P.pred_write = v;
     else if (k == "model_write") P.model_write = v;
+    else if (k == "model_read") P.model_read = v;
     else if (k == "name_dump") P.name_dump = v;
     else if (k == "need_reverse") P.need_reverse = std::stoi(v) != 0;
     else if (k == "dump_aux") P.dump_aux = std::stoi(v) != 0;
@@ -133,6 +135,7 @@ struct RunPlan {
   bool epoch_resample = false;  // every training epoch draws its negatives out of the full cache
   bool pred_write_device = false;
   bool model_write_device = false;  // model_out / name_dump through the device writers
+  bool model_read_device = false;   // model_in's files through the device loader
   bool dump = false;                // task=1: load model_in, write name_dump, nothing else
   bool print_rank = true;  // rank 0, or an unsharded run: prints the run's lines
 };
@@ -267,6 +270,9 @@ inline int ResolveOptions(const Param& P, const KWArgs& rest, const LaunchEnv& e
   if (P.model_write != "host" && P.model_write != "device")
     return refuse("model_write must be host or device", "");
   R.model_write_device = P.model_write == "device";  // (without model_out: nothing to write)
+  if (P.model_read != "host" && P.model_read != "device")
+    return refuse("model_read must be host or device", "");
+  R.model_read_device = P.model_read == "device";  // (without model_in: nothing to read)
   R.dump = P.task == 1;
   if (R.dump) {
     if (P.model_in.empty()) return refuse("dump needs model_in", "");

@@ -271,8 +271,20 @@ class Store:
             return model_write_stats(st, tm)
         check(_lib.lib().dfx_store_save(self.ctx.h, str(path).encode(), int(save_aux)))
 
-    def load(self, path):
-        check(_lib.lib().dfx_store_load(self.ctx.h, str(path).encode()))
+    def load(self, path, device=False, tile_dwords=0, rank=0, nranks=1):
+        """SGDUpdater::Load; rank of nranks: only the keys that rank owns (dfx_store_load_part).
+        device: the file is cut into records and inserted by kernels (dfx_store_load_dev), the
+        same store -> its stats (model_load_stats)"""
+        if device:
+            st, tm = (ctypes.c_int64 * 6)(), (ctypes.c_double * 2)()
+            check(_lib.lib().dfx_store_load_dev(self.ctx.h, str(path).encode(), int(rank),
+                                                int(nranks), int(tile_dwords), st, tm))
+            return model_load_stats(st, tm)
+        if (int(rank), int(nranks)) == (0, 1):
+            check(_lib.lib().dfx_store_load(self.ctx.h, str(path).encode()))
+        else:
+            check(_lib.lib().dfx_store_load_part(self.ctx.h, str(path).encode(), int(rank),
+                                                 int(nranks)))
 
     def dump(self, path, dump_aux=False, need_reverse=False, device=False, chunk_slots=0):
         """SGDUpdater::Dump's text.  device: formatted on the device (dfx_store_dump_dev), the
@@ -680,6 +692,12 @@ def model_write_stats(st, tm):
     """the four counts and the two host times of dfx_store_save_dev / _dump_dev"""
     return {"entries": st[0], "bytes": st[1], "chunks": st[2], "host_chunks": st[3],
             "wait_s": tm[0], "write_s": tm[1]}
+
+
+def model_load_stats(st, tm):
+    """the six counts and the two host times of dfx_store_load_dev"""
+    return {"records": st[0], "owned": st[1], "owned_v": st[2], "tiles": st[3],
+            "tile_dwords": st[4], "host_loaded": st[5], "read_s": tm[0], "wait_s": tm[1]}
 
 
 def _model_chunk(ctx, text, slot0, nslots, aux, need_reverse, out, cap_bytes):

@@ -625,6 +625,24 @@ int dfx_store_load(dfx_ctx* ctx, const char* path);
  * a model saved by N servers (<prefix>_part-<r>, r < N) loads into M servers by every server
  * loading every part */
 int dfx_store_load_part(dfx_ctx* ctx, const char* path, int rank, int nranks);
+/* dfx_store_load_part with the file taken apart on the device (difacto_amd/csrc/modelload.hip):
+ * the file is read once, in large freads through two pinned buffers, into one device buffer; its
+ * tiles of tile_dwords dwords are cut into records in parallel (every entry phase of a tile
+ * walked, the tiles' maps composed by a two-level scan), validated as a whole, and only then
+ * inserted - the same store as the host loader leaves: the owner rule, table_set_ranges,
+ * LoadEntry's rule (fea_cnt kept; sqrt_g and z kept when the file has no aux), n_keys, n_vrows
+ * and new_w, the table's capacity, fat slots and the split pool, and its error codes with the
+ * store untouched.  The keys of a file are distinct, as Save writes them; with duplicates the
+ * inserts race here as they do in the host loader's kernel, and no order is promised.
+ * tile_dwords: 0 for the default (4096; 8192 for records over 128 dwords), else a multiple of 16
+ * in [32, 8192]; anything else is DFX_ERR_ARG.  A file that does not fit in free device memory
+ * beside the table it needs (or whose records pass the maps' 16-bit phases, V_dim near 32000) is
+ * loaded by dfx_store_load_part in the device's place, and stats[5] says so.
+ * stats (6, may be NULL): [0] records in the file, [1] records this rank owns, [2] of those with
+ * V, [3] tiles, [4] tile_dwords used, [5] 1 when the host loader took the file.  times (2, may be
+ * NULL): host seconds [0] in fread, [1] waiting for the device. */
+int dfx_store_load_dev(dfx_ctx* ctx, const char* path, int rank, int nranks, int64_t tile_dwords,
+                       int64_t* stats, double* times);
 int dfx_store_dump(dfx_ctx* ctx, const char* path, int dump_aux, int need_reverse);
 
 /* ---- model files written from the device (difacto_amd/csrc/modelfile.hip) ------------------
