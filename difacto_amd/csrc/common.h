@@ -194,7 +194,8 @@ struct Table {
   Entry* ent;       // cap slots of 32 << es bytes, the entry first
   float* V;         // split layout (es == 0): vcap rows of [V(d) | Vaux(d)] — a key's embedding
                     // and its AdaGrad accumulators share one 2*d*4-byte row (one 128-byte line
-                    // at d = 16); fat slots (es > 0): cap rows of Vaux(d), row = slot
+                    // at d = 16); fat slots (es > 0): cap rows of Vaux(d), row = slot; line
+                    // slots: null (no pool, vcap 0)
   uint64_t mask;    // cap - 1
   int logcap;
   int d;
@@ -211,6 +212,10 @@ struct Table {
   // stays in the pool, one d-float row per slot; a key's vrow is its own slot (InitV sets it,
   // a rehash moves the row with the slot)
   int es;
+  // line slots (kwarg slot_layout=line, d = 4 / 8 / 12): Vaux lives in the slot too, behind V —
+  // [Entry 32 B | V 4d B | Vaux 4d B | pad] in 64 bytes (d = 4) or 128 (d = 8, 12), a key's whole
+  // state in one 128-byte line; es as with fat slots (d = 8: 2, not 1), vrow = slot, no pool
+  int line;
 };
 
 __host__ __device__ inline Entry* ent_at(const Table& t, int64_t s) { return t.ent + (s << t.es); }
@@ -218,8 +223,17 @@ __host__ __device__ inline Entry* ent_at(const Table& t, int64_t s) { return t.e
 __host__ __device__ inline float* row_V(const Table& t, int64_t vr) {
   return t.es ? reinterpret_cast<float*>(t.ent + (vr << t.es) + 1) : t.V + vr * 2 * (int64_t)t.d;
 }
-__host__ __device__ inline float* row_C(const Table& t, int64_t vr) {
+// Vaux of V row vr where the table has a pool (the split layout and fat slots): what the
+// kernels that never run on a line table call, so that they compile to what they were
+__host__ __device__ inline float* row_C_pool(const Table& t, int64_t vr) {
   return t.es ? t.V + vr * (int64_t)t.d : t.V + vr * 2 * (int64_t)t.d + t.d;
+}
+__host__ __device__ inline float* row_C(const Table& t, int64_t vr) {
+  return t.line ? row_V(t, vr) + t.d : row_C_pool(t, vr);
+}
+// the V rows the table has room for: the pool's, or with line slots one per slot
+__host__ __device__ inline int64_t vrow_cap(const Table& t) {
+  return t.line ? (int64_t)t.mask + 1 : t.vcap;
 }
 
 // the V row InitV gives a key: the q-th new row of this Update in the split layout (rows are
@@ -233,6 +247,13 @@ __host__ __device__ inline int64_t initv_row(const Table& t, uint64_t n_vrows, i
 __host__ __device__ inline int fat_es(int d) {
   if (d < 4 || d % 4 != 0 || 32 + 4 * d > 128) return 0;
   return 32 + 4 * d <= 64 ? 1 : 2;
+}
+
+// line slot stride for V_dim d (0: d has no line layout): the entry, V and Vaux in 64 or 128
+// bytes — d = 4: 64; d = 8 (96 bytes of state, which would straddle lines at that stride) and
+// d = 12: 128
+__host__ __device__ inline int line_es(int d) {
+  return d == 4 ? 1 : (d == 8 || d == 12) ? 2 : 0;
 }
 
 __device__ inline float4 ent_state(const Entry* e) {

@@ -83,7 +83,9 @@ struct Kw {
   // rounds (round 4's bucket AUC, a shorter lane but a slower step, is gone: DESIGN.md (d))
   int auc_sort = 1;
   // slot_layout=auto (default): fat slots (entry + V in one 64/128-byte slot, common.h Table)
-  // when V_dim allows them (4 <= d <= 24, d % 4 == 0), else the split layout; split | fat force
+  // when V_dim allows them (4 <= d <= 24, d % 4 == 0), else the split layout; split | fat force;
+  // line (2): the entry, V and Vaux in one 128-byte line, no pool (V_dim 4, 8 or 12; the
+  // single-GPU context only)
   int slot_layout = -1;
   int fat_fwd = 1;  // fat_fwd=0: with fat slots, the split forward walk (A/B of the one-trip read)
   // diag=noauc|noloc|noauc_noloc: MEASUREMENT ONLY (the headroom of the side lanes): no AUC
@@ -205,7 +207,8 @@ static int parse_kwargs(const char* kwargs, Kw* kw) {
       if (v == "auto") kw->slot_layout = -1;
       else if (v == "split") kw->slot_layout = 0;
       else if (v == "fat") kw->slot_layout = 1;
-      else { set_error("unknown slot_layout: " + v + " (auto|split|fat)"); return DFX_ERR_ARG; }
+      else if (v == "line") kw->slot_layout = 2;
+      else { set_error("unknown slot_layout: " + v + " (auto|split|fat|line)"); return DFX_ERR_ARG; }
     }
     else if (k == "auc_sort") {
       if (v == "radix") kw->auc_sort = 1;
@@ -246,6 +249,10 @@ static int parse_kwargs(const char* kwargs, Kw* kw) {
   if (!kw->loss_fm) kw->P.V_dim = 0;  // LogitLoss ignores V (logit_loss.h)
   if (kw->slot_layout == 1 && fat_es(kw->P.V_dim) == 0) {
     set_error("slot_layout=fat needs 4 <= V_dim <= 24 with V_dim % 4 == 0");
+    return DFX_ERR_ARG;
+  }
+  if (kw->slot_layout == 2 && line_es(kw->P.V_dim) == 0) {
+    set_error("slot_layout=line needs V_dim 4, 8 or 12 (the entry, V and Vaux in one 128-byte line)");
     return DFX_ERR_ARG;
   }
   return DFX_OK;
@@ -335,7 +342,8 @@ int dfx_ctx_create(int device, const char* kwargs, dfx_ctx** out) {
   c->dist_sum = kw.dist_sum;
   c->sort_pack = kw.sort_pack;
   c->auc_sort = kw.auc_sort;
-  c->slot_es = kw.slot_layout == 0 ? 0 : fat_es(c->P.V_dim);
+  c->slot_line = kw.slot_layout == 2;
+  c->slot_es = c->slot_line ? line_es(c->P.V_dim) : kw.slot_layout == 0 ? 0 : fat_es(c->P.V_dim);
   c->fat_fwd = kw.fat_fwd;
   c->nt_mask = kw.nt;
   c->bwd_two_pass = kw.bwd_two_pass;

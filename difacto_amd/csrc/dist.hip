@@ -241,7 +241,7 @@ __global__ void k_dist_push(const uint32_t* segstart, const uint32_t* segslot,
     const int vr = en->vrow;
     bool has_v = vr >= 0;
     float* V = has_v ? row_V(T, vr) : nullptr;
-    float* C = has_v ? row_C(T, vr) : nullptr;
+    float* C = has_v ? row_C_pool(T, vr) : nullptr;
     uint32_t f = 0, fr = 0;
     for (uint32_t i = segstart[u]; i < segstart[u + 1]; ++i) {
       const uint32_t src = sorted_idx[i];
@@ -346,7 +346,7 @@ __global__ __launch_bounds__(kDNT) void k_dist_push_vec(const uint32_t* __restri
     const float* g0 = g + (int64_t)src0 * S;
     const float2 gwp0 = *reinterpret_cast<const float2*>(g0 + d);  // {gw, pulled}
     float4* V4 = reinterpret_cast<float4*>(row_V(T, vr >= 0 ? vr : 0));
-    float4* C4 = reinterpret_cast<float4*>(row_C(T, vr >= 0 ? vr : 0));
+    float4* C4 = reinterpret_cast<float4*>(row_C_pool(T, vr >= 0 ? vr : 0));
     const bool mine = vr >= 0 && l < nc;
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
     float4 v = mine ? V4[l] : z4, cg = mine ? C4[l] : z4;
@@ -440,7 +440,7 @@ __global__ __launch_bounds__(kDNT) void k_dist_push_sum_vec(
     const float2 gwp0 = *reinterpret_cast<const float2*>(g0 + d);  // {gw, pulled}
     const int vr = __float_as_int(h.y);
     float4* V4 = reinterpret_cast<float4*>(row_V(T, vr >= 0 ? vr : 0));
-    float4* C4 = reinterpret_cast<float4*>(row_C(T, vr >= 0 ? vr : 0));
+    float4* C4 = reinterpret_cast<float4*>(row_C_pool(T, vr >= 0 ? vr : 0));
     const bool upd_v = vr >= 0 && gwp0.y != 0.f;
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
     float4 v = upd_v && l < nc ? V4[l] : z4, cg = upd_v && l < nc ? C4[l] : z4;
@@ -511,7 +511,7 @@ __global__ void k_dist_push_sum(const uint32_t* segstart, const uint32_t* segslo
     ent_set_state(en, e);
     if (vr >= 0 && g0[d + 1] != 0.f) {
       float* V = row_V(T, vr);
-      float* C = row_C(T, vr);
+      float* C = row_C_pool(T, vr);
       for (int k = 0; k < d; ++k) {
         float gk = g0[k];
         for (uint32_t i = s0 + 1; i < s1; ++i) gk += g[(int64_t)sorted_idx[i] * S + k];
@@ -633,6 +633,7 @@ int dfx_dist_record_floats(dfx_ctx* ctx) { return ctx ? rec_floats(ctx->c.P.V_di
 int dfx_dist_localize(dfx_ctx* ctx, const dfx_batch* b, uint64_t max_index, int nranks,
                       int slot, uint64_t* keys_out, float* cnt_out) {
   DFX_CHECK_ARG(ctx && b, "null argument");
+  DFX_NO_LINE(ctx);
   DFX_CHECK_SLOT(slot);
   DFX_CHECK_ARG(nranks >= 1 && nranks <= kMaxRanks, "dist: 1 <= nranks <= 64");
   DFX_CHECK_ARG(b->size >= 0 && b->nnz >= 0, "dist_localize: negative sizes");
@@ -675,6 +676,7 @@ int dfx_dist_localize(dfx_ctx* ctx, const dfx_batch* b, uint64_t max_index, int 
 int dfx_dist_localize_wait(dfx_ctx* ctx, int slot, int nranks, int64_t* split_counts,
                            int64_t* n_uniq) {
   DFX_CHECK_ARG(ctx && split_counts && n_uniq, "null argument");
+  DFX_NO_LINE(ctx);
   DFX_CHECK_SLOT(slot);
   DFX_CHECK_ARG(nranks >= 1 && nranks <= kMaxRanks, "dist: 1 <= nranks <= 64");
   Context* c = &ctx->c;
@@ -690,6 +692,7 @@ int dfx_dist_localize_wait(dfx_ctx* ctx, int slot, int nranks, int64_t* split_co
 int dfx_dist_fwd_bwd(dfx_ctx* ctx, int slot, const dfx_batch* b, const float* pulled,
                      int job_type, float* grads_out, float* pred_out) {
   DFX_CHECK_ARG(ctx && b, "null argument");
+  DFX_NO_LINE(ctx);
   DFX_CHECK_SLOT(slot);
   DFX_CHECK_ARG(job_type == DFX_JOB_TRAINING || job_type == DFX_JOB_VALIDATION ||
                     job_type == DFX_JOB_PREDICTION,
@@ -754,6 +757,7 @@ int dfx_dist_fwd_bwd(dfx_ctx* ctx, int slot, const dfx_batch* b, const float* pu
 int dfx_dist_owner_begin(dfx_ctx* ctx, int slot, const uint64_t* recv_keys,
                          const int64_t* recv_offsets, int nranks, const float* recv_cnt) {
   DFX_CHECK_ARG(ctx && recv_offsets, "null argument");
+  DFX_NO_LINE(ctx);
   DFX_CHECK_SLOT(slot);
   DFX_CHECK_ARG(nranks >= 1 && nranks <= kMaxRanks, "dist: 1 <= nranks <= 64");
   Context* c = &ctx->c;
@@ -824,6 +828,7 @@ int dfx_dist_owner_begin(dfx_ctx* ctx, int slot, const uint64_t* recv_keys,
 
 int dfx_dist_owner_pull(dfx_ctx* ctx, int slot, float* vals_out) {
   DFX_CHECK_ARG(ctx, "null ctx");
+  DFX_NO_LINE(ctx);
   DFX_CHECK_SLOT(slot);
   Context* c = &ctx->c;
   DFX_CHECK_ARG(!c->dist_initv_pending[slot],
@@ -870,6 +875,7 @@ int dfx_dist_owner_pull(dfx_ctx* ctx, int slot, float* vals_out) {
 
 int dfx_dist_owner_push(dfx_ctx* ctx, int slot, const float* recv_grads) {
   DFX_CHECK_ARG(ctx, "null ctx");
+  DFX_NO_LINE(ctx);
   DFX_CHECK_SLOT(slot);
   Context* c = &ctx->c;
   DFX_CHECK_ARG(!any_pending(c->dist_initv_pending),
@@ -948,6 +954,7 @@ int dfx_dist_owner_push(dfx_ctx* ctx, int slot, const float* recv_grads) {
 // owner's, advancing the shared seed by the total (sgd_updater.cc:144-152 in global key order)
 int dfx_dist_initv_local(dfx_ctx* ctx, int slot, int64_t* count_dev) {
   DFX_CHECK_ARG(ctx && count_dev, "null argument");
+  DFX_NO_LINE(ctx);
   DFX_CHECK_SLOT(slot);
   Context* c = &ctx->c;
   DFX_CHECK_ARG(c->dist_sum, "dist_initv_local: only with push_agg=sum");
@@ -961,6 +968,7 @@ int dfx_dist_initv_local(dfx_ctx* ctx, int slot, int64_t* count_dev) {
 int dfx_dist_initv_draw(dfx_ctx* ctx, int slot, const int64_t* counts_all_dev, int rank,
                         int nranks) {
   DFX_CHECK_ARG(ctx && counts_all_dev, "null argument");
+  DFX_NO_LINE(ctx);
   DFX_CHECK_SLOT(slot);
   DFX_CHECK_ARG(nranks >= 1 && nranks <= kMaxRanks && rank >= 0 && rank < nranks,
                 "dist_initv_draw: bad rank");
@@ -988,6 +996,7 @@ int dfx_dist_union(dfx_ctx* ctx, const uint64_t* runs, const int64_t* run_offs, 
                    int nranks, uint64_t* union_out, uint32_t* upos_out, int64_t* bounds_out,
                    int64_t* n_union) {
   DFX_CHECK_ARG(ctx && run_offs && bounds_out && n_union, "null argument");
+  DFX_NO_LINE(ctx);
   DFX_CHECK_ARG(nruns >= 1 && nruns <= kMaxRanks && nranks >= 1 && nranks <= kMaxRanks,
                 "dist_union: 1 <= nruns, nranks <= 64");
   Context* c = &ctx->c;
@@ -1040,6 +1049,7 @@ int dfx_dist_union_rows(dfx_ctx* ctx, const uint64_t* keys, const uint32_t* upos
                         const int64_t* bounds, int nranks, int64_t M, int width, int to_union,
                         const float* src, float* dst) {
   DFX_CHECK_ARG(ctx && bounds, "null argument");
+  DFX_NO_LINE(ctx);
   DFX_CHECK_ARG(nranks >= 1 && nranks <= kMaxRanks && width >= 1, "dist_union_rows: bad sizes");
   if (U == 0) return DFX_OK;
   DFX_CHECK_ARG(keys && upos && src && dst, "dist_union_rows: null buffer");

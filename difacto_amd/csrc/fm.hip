@@ -20,55 +20,14 @@
 // round trip through HBM).
 #include <cstdlib>
 
-#include "fm_args.h"
+#include "fm_lanes.h"
 
 namespace dfx {
 
-constexpr int kFmNT = 256;
 
 // kFusedProbe: kFused whose nnz find their keys in the table (FwdArgs::index)
 enum FwdMode { kPredict = 0, kGradPrep = 1, kFused = 2, kFusedProbe = 3 };
 
-
-// Coordinates [l*CPL, l*CPL+CPL) of a length-d row.  VEC: d is a multiple of the vector
-// width and the row 16-byte aligned, so a lane's chunk is wholly inside or wholly outside
-// the row (outside chunks read chunk 0 and are ignored).
-template <int CPL, bool VEC>
-__device__ inline void load_coords(const float* row, int l, int d, float (&v)[CPL],
-                                   bool nt = false) {
-  const int base = l * CPL;
-  if constexpr (VEC && CPL % 4 == 0) {
-    const int b = base < d ? base : 0;
-#pragma unroll
-    for (int m = 0; m < CPL / 4; ++m) {
-      const float4 f = ld4(row + b + 4 * m, nt);
-      v[4 * m] = f.x; v[4 * m + 1] = f.y; v[4 * m + 2] = f.z; v[4 * m + 3] = f.w;
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < CPL; ++k) {
-      const int cd = base + k;
-      v[k] = ldnt(row + (cd < d ? cd : 0), nt);
-    }
-  }
-}
-
-template <int CPL, bool VEC>
-__device__ inline void store_coords(float* row, int l, int d, const float (&v)[CPL],
-                                    bool nt = false) {
-  const int base = l * CPL;
-  if (base >= d) return;
-  if constexpr (VEC && CPL % 4 == 0) {
-#pragma unroll
-    for (int m = 0; m < CPL / 4; ++m)
-      st4(row + base + 4 * m, make_float4(v[4 * m], v[4 * m + 1], v[4 * m + 2], v[4 * m + 3]),
-          nt);
-  } else {
-#pragma unroll
-    for (int k = 0; k < CPL; ++k)
-      if (base + k < d) stnt(row + base + k, v[k], nt);
-  }
-}
 
 template <int G, int CPL, int MODE, bool PACKED, bool VEC>
 __global__ __launch_bounds__(kFmNT) void k_fm_fwd(FwdArgs a) {
@@ -810,14 +769,7 @@ int launch_fwd_records(const FwdArgs& a, hipStream_t st, int* nblk) {
 }
 
 // ---- backward: sorted-key segmented reduction --------------------------------------------
-// p of row r for a backward that also reads the row's XV*p: from the XV*p row when p shares
-// its last line (4d % 128 != 0: d = 16's 68 bytes in one 128-byte line), else from the
-// compact per-row array (d = 64 / 128: p would be a line of its own in a 384 / 640-byte row,
-// where the 400-KB array stays in the L2); the split owner has only the rows (p == nullptr)
-__device__ inline float row_p(const BwdArgs& a, uint32_t r, int d, int64_t xs) {
-  if (a.p && (xs <= d || (4 * d) % 128 == 0)) return a.p[r];
-  return a.XVp[(int64_t)r * xs + d];
-}
+// (row_p: fm_lanes.h)
 template <int G, int CPL, bool FUSED, bool VEC>
 __global__ __launch_bounds__(kFmNT) void k_fm_bwd(BwdArgs a) {
   constexpr int SPB = kFmNT / G;
@@ -862,7 +814,7 @@ __global__ __launch_bounds__(kFmNT) void k_fm_bwd(BwdArgs a) {
         const float4 h0 = ld4(eh, ntb), h1 = ld4(eh + 4, ntb);
         if (a.T.es && !a.no_fat_spec) {  // a key at home has V there: one trip for the key
           load_coords<CPL, VEC>(row_V(a.T, (int64_t)hh), l, d, vcur, ntb);
-          load_coords<CPL, VEC>(row_C(a.T, (int64_t)hh), l, d, ccur, ntb);
+          load_coords<CPL, VEC>(row_C_pool(a.T, (int64_t)hh), l, d, ccur, ntb);
           spec = true;
         }
         const uint64_t ek =
@@ -921,7 +873,7 @@ __global__ __launch_bounds__(kFmNT) void k_fm_bwd(BwdArgs a) {
       vq = (vrow >= 0 && !(a.Pm.l1_shrk && e.x == 0.f)) ? vrow : -1;
       if (!(spec && home && vq >= 0)) {  // (fat slots: at home, vrow == the home slot)
         load_coords<CPL, VEC>(vq >= 0 ? row_V(a.T, vq) : zp, l, d, vcur, ntb);
-        load_coords<CPL, VEC>(vq >= 0 ? row_C(a.T, vq) : zp, l, d, ccur, ntb);
+        load_coords<CPL, VEC>(vq >= 0 ? row_C_pool(a.T, vq) : zp, l, d, ccur, ntb);
       }
 #pragma unroll
       for (int k = 0; k < CPL; ++k) g0[k] = 0.f;
@@ -1179,7 +1131,7 @@ __global__ __launch_bounds__(kFmNT) void k_fm_bwd(BwdArgs a) {
 #pragma unroll
         for (int k = 0; k < CPL; ++k) adagrad_update(a.Pm, acc[k], &vcur[k], &ccur[k]);
         store_coords<CPL, VEC>(row_V(a.T, vq), l, d, vcur, ntb);
-        store_coords<CPL, VEC>(row_C(a.T, vq), l, d, ccur, ntb);
+        store_coords<CPL, VEC>(row_C_pool(a.T, vq), l, d, ccur, ntb);
       }
       if (l == 0) {
         if (!dead) ent_store_hot(ent_at(a.T, sl), e, vrow, ntb);
@@ -1495,7 +1447,7 @@ __global__ __launch_bounds__(kFmNT) void k_fm_bwd_v(BwdArgs a) {
     const uint32_t s0 = it.x, s1 = s0 + len;  // (it.x is the first chunk of a chunked key)
     float vcur[CPL], ccur[CPL], acc[CPL];
     load_coords<CPL, true>(row_V(a.T, vq), l, d, vcur);
-    load_coords<CPL, true>(row_C(a.T, vq), l, d, ccur);
+    load_coords<CPL, true>(row_C_pool(a.T, vq), l, d, ccur);
     // grad_u = (g0 - V*XXp) + sum (XV_ p) x, g0 = 0 (fm_loss.h:185-202, spmm.h:127-159)
     if (a.choff && len > (uint32_t)kChunkOcc) {
       const uint32_t c0 = it.x;
@@ -1549,7 +1501,7 @@ __global__ __launch_bounds__(kFmNT) void k_fm_bwd_v(BwdArgs a) {
 #pragma unroll
     for (int k = 0; k < CPL; ++k) adagrad_update(a.Pm, acc[k], &vcur[k], &ccur[k]);
     store_coords<CPL, true>(row_V(a.T, vq), l, d, vcur);
-    store_coords<CPL, true>(row_C(a.T, vq), l, d, ccur);
+    store_coords<CPL, true>(row_C_pool(a.T, vq), l, d, ccur);
   }
 }
 
@@ -1876,6 +1828,7 @@ bool bwd_two_pass(int d) {
 
 int launch_bwd_fused(const BwdArgs& a, int64_t nseg_bound, hipStream_t st, long lds) {
   DFX_TRY(check_row_p(a));
+  if (a.T.line) return launch_bwd_line(a, nseg_bound, st, lds, kBwdLdsCapFused);
   if (!a.vlist) return launch_bwd<true>(a, nseg_bound, st, true, lds);
   if (nseg_bound <= 0) return DFX_OK;
   int G, CPL;

@@ -179,6 +179,10 @@ bool bwd_two_pass(int d);
 int bwd_two_pass_reserve(Context* c, Workspace& ws, int64_t nseg_bound, BwdArgs* g);
 int sum_live(const uint2* part, int64_t n, DevState* ds, hipStream_t st);
 int launch_bwd_fused(const BwdArgs& a, int64_t nseg_bound, hipStream_t st, long lds = -1);
+// ... of a line table (fm_line.hip; launch_bwd_fused goes there when the table says so).
+// lds_default: the fused backward's LDS reservation when lds < 0
+int launch_bwd_line(const BwdArgs& a, int64_t nseg_bound, hipStream_t st, long lds,
+                    size_t lds_default);
 // the chunk partials of long segments (before the backward reads them)
 int launch_bwd_chunks(const BwdArgs& a, int64_t chunk_bound, hipStream_t st, bool aligned);
 

@@ -1,0 +1,416 @@
+// The fused backward over line slots (kwarg slot_layout=line): k_fm_bwd_line and its launcher.
+// A translation unit of its own, built without packed fp32 arithmetic (Makefile).
+#include "fm_lanes.h"
+
+namespace dfx {
+
+// One key's sums over its occurrences [s0, s1) for the line backward (k_fm_bwd_line): g_w into
+// gw and, when the key's V takes part (vq >= 0), grad_u of lane l's CPL coordinates into acc.
+// row / x / pr / xr: the first UNR occurrences' rows, values, p and XV*p, loaded by the caller
+// beside the key's state; u: the key's segment (its chunks' partials); vcur, g0: V and the
+// gradient so far.  The terms, their order and the three forms (a short segment from registers,
+// a chunked one from its partials, the walk) are k_fm_bwd's for groups under 8 lanes, restated
+// here, not called from there: k_fm_bwd inlines its own text, so that what it compiles to for
+// the split and fat layouts stays what it was (taking these sums through this function changed
+// its register allocation).  A change to either text belongs in both; tests/
+// test_gpu_line_slots.py holds the two to the same bits.
+template <int G, int CPL, bool VEC, int UNR>
+__device__ __forceinline__ void bwd_key_sums(const BwdArgs& a, int l, int64_t u, uint32_t s0,
+                                             uint32_t s1, bool valued, int d, int64_t xs, int vq,
+                                             const uint32_t (&row)[UNR], const float (&x)[UNR],
+                                             const float (&pr)[UNR], const float (&xr)[UNR][CPL],
+                                             const float (&vcur)[CPL], const float (&g0)[CPL],
+                                             float& gw, float (&acc)[CPL]) {
+  static_assert(G < 8, "wide groups walk G occurrences per trip (k_fm_bwd)");
+  const uint32_t len = s1 - s0;
+  float xxp = 0.f;
+  // ---- pass 1: g_w and XXp (SpMV::TransTimes, spmv.h:139-171: skip p == 0)
+  // ---- pass 2: grad_u = (g0 - V*XXp) + sum (XV_ p) x (fm_loss.h:185-202, spmm.h:127-159)
+  // Both sums run in occurrence order; a segment of <= UNR occurrences (the common case)
+  // is computed from the registers loaded above.
+  if (len <= (uint32_t)UNR) {
+#pragma unroll
+    for (int t = 0; t < UNR; ++t) {
+      if ((uint32_t)t < len && pr[t] != 0.f) {
+        if (valued) {
+          gw += pr[t] * x[t];
+          xxp += pr[t] * (x[t] * x[t]);
+        } else {
+          gw += pr[t];
+          xxp += pr[t];
+        }
+      }
+    }
+    if (vq >= 0) {
+#pragma unroll
+      for (int k = 0; k < CPL; ++k) acc[k] = g0[k] - vcur[k] * xxp;
+#pragma unroll
+      for (int t = 0; t < UNR; ++t) {
+        if ((uint32_t)t < len) {
+#pragma unroll
+          for (int k = 0; k < CPL; ++k)
+            acc[k] = valued ? acc[k] + xr[t][k] * x[t] : acc[k] + xr[t][k];
+        }
+      }
+    }
+  } else if (a.choff && len > (uint32_t)kChunkOcc) {
+    // a long segment (a skewed key): its chunks' partial sums (k_fm_bwd_chunks), combined in
+    // chunk order, all in double and rounded once — the sums differ from the reference's
+    // sequential float sums only by that float rounding (reordering error)
+    const uint32_t c0 = a.choff[u];
+    const uint32_t nc = hot_chunks_read((len + kChunkOcc - 1) / kChunkOcc);
+    const int P = d + 2;
+    double gwd = 0, xxpd = 0, accp[CPL];
+#pragma unroll
+    for (int k = 0; k < CPL; ++k) accp[k] = 0;
+    for (uint32_t c = 0; c < nc; ++c) {
+      const double* pc = a.part + (int64_t)(c0 + c) * P;
+      gwd += pc[0];
+      xxpd += pc[1];
+      if (vq >= 0) {
+#pragma unroll
+        for (int k = 0; k < CPL; ++k) {
+          const int cd = l * CPL + k;
+          accp[k] += cd < d ? pc[2 + cd] : 0.0;
+        }
+      }
+    }
+    gw = (float)gwd;
+    xxp = (float)xxpd;
+    if (vq >= 0) {
+#pragma unroll
+      for (int k = 0; k < CPL; ++k) acc[k] = (float)((double)(g0[k] - vcur[k] * xxp) + accp[k]);
+    }
+  } else {
+    // Both walks keep the next trip's rows in flight beside this trip's row reads (the
+    // segment's occ_row / occ_x are contiguous; the p / XV*p reads are the random ones), so a
+    // trip costs one memory round trip instead of two.  Same terms, same order.
+    uint32_t rw[UNR];
+    float xw[UNR];
+#pragma unroll
+    for (int t = 0; t < UNR; ++t) {  // the first trip's rows: already loaded (level 2)
+      rw[t] = row[t];
+      xw[t] = x[t];
+    }
+    for (uint32_t i0 = s0; i0 < s1; i0 += UNR) {
+      float pw[UNR];
+#pragma unroll
+      for (int t = 0; t < UNR; ++t)
+        pw[t] = row_p(a, rw[t], d, xs);
+      const uint32_t in = i0 + UNR;
+      uint32_t rn[UNR];
+      float xn[UNR];
+#pragma unroll
+      for (int t = 0; t < UNR; ++t) {
+        const uint32_t i = in + t < s1 ? in + t : s1 - 1;
+        xn[t] = 1.f;
+        rn[t] = in < s1 ? occ_get(a, i, valued, false, &xn[t]) : 0u;
+      }
+#pragma unroll
+      for (int t = 0; t < UNR; ++t) {
+        if (i0 + t < s1 && pw[t] != 0.f) {
+          if (valued) {
+            gw += pw[t] * xw[t];
+            xxp += pw[t] * (xw[t] * xw[t]);
+          } else {
+            gw += pw[t];
+            xxp += pw[t];
+          }
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < UNR; ++t) {
+        rw[t] = rn[t];
+        xw[t] = xn[t];
+      }
+    }
+    if (vq >= 0) {
+#pragma unroll
+      for (int k = 0; k < CPL; ++k) acc[k] = g0[k] - vcur[k] * xxp;
+#pragma unroll
+      for (int t = 0; t < UNR; ++t) {
+        rw[t] = row[t];
+        xw[t] = x[t];
+      }
+      for (uint32_t i0 = s0; i0 < s1; i0 += UNR) {
+        float xrw[UNR][CPL];
+#pragma unroll
+        for (int t = 0; t < UNR; ++t)
+          load_coords<CPL, VEC>(a.XVp + (int64_t)rw[t] * xs, l, d, xrw[t]);
+        // the next trip's rows, in flight beside this trip's XV*p rows
+        const uint32_t in = i0 + UNR;
+        uint32_t rn[UNR];
+        float xn[UNR];
+#pragma unroll
+        for (int t = 0; t < UNR; ++t) {
+          const uint32_t i = in + t < s1 ? in + t : s1 - 1;
+          xn[t] = 1.f;
+          rn[t] = in < s1 ? occ_get(a, i, valued, false, &xn[t]) : 0u;
+        }
+#pragma unroll
+        for (int t = 0; t < UNR; ++t) {
+          if (i0 + t < s1) {
+#pragma unroll
+            for (int k = 0; k < CPL; ++k)
+              acc[k] = valued ? acc[k] + xrw[t][k] * xw[t] : acc[k] + xrw[t][k];
+          }
+        }
+#pragma unroll
+        for (int t = 0; t < UNR; ++t) {
+          rw[t] = rn[t];
+          xw[t] = xn[t];
+        }
+      }
+    }
+  }
+}
+
+// The line backward's block epilogue, k_fm_bwd's restated (see bwd_key_sums): the lanes' new_w,
+// InitV-request, insert and live-V counts summed over the block and added to the step's counters
+// (every thread of the block calls it)
+__device__ __forceinline__ void bwd_block_stats(const BwdArgs& a, int dnew, int ninit, int nins,
+                                                unsigned nlive, unsigned nlocc) {
+  __shared__ int red[kFmNT / kWave];
+  __shared__ int redn[kFmNT / kWave];
+  __shared__ int redi[kFmNT / kWave];
+  __shared__ unsigned redl[kFmNT / kWave], redo[kFmNT / kWave];
+  // new_w, and the InitV requests (dsw->n_init gates the InitV pass on the device)
+  for (int off = 32; off > 0; off >>= 1) {
+    dnew += __shfl_xor(dnew, off, kWave);
+    ninit += __shfl_xor(ninit, off, kWave);
+    nins += __shfl_xor(nins, off, kWave);
+    nlive += __shfl_xor(nlive, off, kWave);
+    nlocc += __shfl_xor(nlocc, off, kWave);
+  }
+  if (lane_id() == 0) {
+    red[threadIdx.x / kWave] = dnew;
+    redn[threadIdx.x / kWave] = ninit;
+    redi[threadIdx.x / kWave] = nins;
+    redl[threadIdx.x / kWave] = nlive;
+    redo[threadIdx.x / kWave] = nlocc;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int s = 0, q = 0, i2 = 0;
+    unsigned long long lv = 0, lo = 0;
+    for (int i = 0; i < kFmNT / kWave; ++i) {
+      s += red[i];
+      q += redn[i];
+      i2 += redi[i];
+      lv += redl[i];
+      lo += redo[i];
+    }
+    // one-word atomics serialise (~88 per us) and a cold model has a new w in
+    // nearly every block: the counts go to a stripe of their own line; n_init is a gate only
+    unsigned long long* nw = (unsigned long long*)&a.dsw->new_w;
+    unsigned long long* nk = &a.dsw->n_keys;
+    if (a.stripes) {
+      nw = a.stripes + (blockIdx.x % kBwStripes) * 16;
+      nk = nw + 1;
+    }
+    if (s) atomicAdd(nw, (unsigned long long)(long long)s);
+    if (q && __hip_atomic_load(&a.dsw->n_init, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
+      atomicOr(&a.dsw->n_init, 1u);
+    if (i2) atomicAdd(nk, (unsigned long long)i2);
+    if (a.live_part) a.live_part[blockIdx.x] = make_uint2((unsigned)lv, (unsigned)lo);
+  }
+}
+
+// ---- the fused backward over line slots (kwarg slot_layout=line, V_dim 4 / 8 / 12) ----------
+// A line slot [Entry 32 B | V | Vaux | pad] holds a key's whole state in one 128-byte line, as
+// 4 + d / 2 pieces of 16 bytes (common.h Table::line).  k_fm_bwd's lanes each load both entry
+// halves, V and Vaux — four loads per lane, and Vaux from a second random line in the pool.
+// Here the group's G = d / 4 (rounded up to a power of two) lanes request every piece once, in
+// one issue to that one line, and the entry's halves reach the other lanes by shuffles:
+//   d = 4   G = 1   the lane: both halves, V, Vaux (no shuffle; one line instead of two)
+//   d = 8   G = 2   lane l: entry half l, V piece l, Vaux piece l
+//   d = 12  G = 4   lanes 0..2: V piece l, Vaux piece l; lane 3 (no coordinates): both halves —
+//                   two loads per lane, the eight pieces of the line
+// So V and Vaux arrive in the lane that owns their coordinates, the lane layout is k_fm_bwd's
+// (lane l: coordinates 4l..4l+3) and the sums are bwd_key_sums': same terms, same order.  The
+// key is checked after the trip: away from home (or absent) lane 0 walks the chain / inserts
+// (tbl_insert) and the group loads the found slot's line the same way.  The write-back is one
+// issue to the line again — the hot entry half from the lane that loaded it (every lane holds
+// the same FTRL state), V from its lanes — and Vaux behind it.
+template <int G>
+__device__ __forceinline__ float4 line_bcast(float4 v, int src) {
+  if constexpr (G == 1) return v;
+  return make_float4(__shfl(v.x, src, kWave), __shfl(v.y, src, kWave), __shfl(v.z, src, kWave),
+                     __shfl(v.w, src, kWave));
+}
+
+// the group's trip to slot s: h0 = {w, vrow, sqrt_g, z} and h1 = {fea_cnt, pad, key} in every
+// lane, v / c = the lane's V / Vaux coordinates (junk in d = 12's lane 3, which owns none)
+template <int G>
+__device__ __forceinline__ void line_load(const Table& T, int64_t s, int l, int gb, bool nt,
+                                          float4* h0, float4* h1, float (&v)[4], float (&c)[4]) {
+  const float* sp = reinterpret_cast<const float*>(ent_at(T, s));
+  const int d = T.d;
+  float4 fv, fc;
+  if constexpr (G == 1) {
+    *h0 = ld4(sp, nt);
+    *h1 = ld4(sp + 4, nt);
+    fv = ld4(sp + 8, nt);
+    fc = ld4(sp + 8 + d, nt);
+  } else if constexpr (G == 2) {
+    const float4 eh = ld4(sp + 4 * l, nt);
+    fv = ld4(sp + 8 + 4 * l, nt);
+    fc = ld4(sp + 8 + d + 4 * l, nt);
+    *h0 = line_bcast<G>(eh, gb);
+    *h1 = line_bcast<G>(eh, gb + 1);
+  } else {
+    static_assert(G == 4, "line slots: 1, 2 or 4 lanes per key");
+    const bool el = l == G - 1;  // the entry's lane
+    fv = ld4(sp + (el ? 0 : 8 + 4 * l), nt);
+    fc = ld4(sp + (el ? 4 : 8 + d + 4 * l), nt);
+    *h0 = line_bcast<G>(fv, gb + G - 1);
+    *h1 = line_bcast<G>(fc, gb + G - 1);
+  }
+  v[0] = fv.x; v[1] = fv.y; v[2] = fv.z; v[3] = fv.w;
+  c[0] = fc.x; c[1] = fc.y; c[2] = fc.z; c[3] = fc.w;
+}
+
+// the write-back to slot s: the hot entry half (unless the key is dead), and V and Vaux when the
+// key's V was updated (live)
+template <int G>
+__device__ __forceinline__ void line_store(const Table& T, int64_t s, int l, bool nt, bool dead,
+                                           bool live, float4 e, int vrow, const float (&v)[4],
+                                           const float (&c)[4]) {
+  float* sp = reinterpret_cast<float*>(ent_at(T, s));
+  const int d = T.d;
+  const float4 hot = make_float4(e.x, __int_as_float(vrow), e.y, e.z);
+  const float4 fv = make_float4(v[0], v[1], v[2], v[3]), fc = make_float4(c[0], c[1], c[2], c[3]);
+  if constexpr (G == 4) {
+    const bool el = l == G - 1;
+    if (el ? !dead : live) st4(el ? sp : sp + 8 + 4 * l, el ? hot : fv, nt);
+    if (!el && live) st4(sp + 8 + d + 4 * l, fc, nt);
+  } else {
+    if (l == 0 && !dead) st4(sp, hot, nt);
+    if (live) {
+      st4(sp + 8 + 4 * l, fv, nt);
+      st4(sp + 8 + d + 4 * l, fc, nt);
+    }
+  }
+}
+
+template <int G>
+__global__ __launch_bounds__(kFmNT) void k_fm_bwd_line(BwdArgs a) {
+  constexpr int CPL = 4, UNR = 4, SPB = kFmNT / G;
+  const int g = threadIdx.x / G;
+  const int l = threadIdx.x % G;
+  const int gb = (int)(threadIdx.x % kWave) - l;
+  const int64_t u = (int64_t)blockIdx.x * SPB + g;
+  const int64_t nseg = a.nseg_host >= 0 ? a.nseg_host : (int64_t)a.ds->u_count;
+  int dnew = 0, ninit = 0, nins = 0;
+  unsigned nlive = 0, nlocc = 0;
+  if (u < nseg) {
+    const bool ntb = (a.nt & kNtBwdTable) != 0, nto = (a.nt & kNtBwdOcc) != 0;
+    const uint32_t s0 = ldnt(a.segstart + u, nto), s1 = ldnt(a.segstart + u + 1, nto);
+    const uint32_t cidx = a.segcol ? a.segcol[u] : (uint32_t)u;
+    const bool valued = a.occ_x != nullptr;
+    const int d = a.d;
+    const int64_t xs = a.xs > d ? a.xs : d;
+    const uint32_t len = s1 - s0;
+    // ---- the key's line (its home slot, or the slot the Get pass found) and the first UNR
+    // occurrences of its segment, mutually independent
+    uint64_t key = 0;
+    uint32_t sl = a.insert_keys ? 0u : a.slot[cidx];
+    bool dead = !a.insert_keys && sl == kNoSlot;
+    if (a.insert_keys) {
+      key = ldnt(a.uniq + cidx, nto);
+      sl = (uint32_t)tbl_hash(key, a.T);
+    }
+    float4 h0, h1;
+    float vcur[CPL], ccur[CPL];
+    line_load<G>(a.T, dead ? 0 : (int64_t)sl, l, gb, ntb, &h0, &h1, vcur, ccur);
+    uint32_t row[UNR];
+    float x[UNR];
+#pragma unroll
+    for (int t = 0; t < UNR; ++t) {
+      const uint32_t i = s0 + ((uint32_t)t < len ? (uint32_t)t : 0u);
+      row[t] = occ_get(a, i, valued, nto, &x[t]);
+    }
+    // ---- the key check: Get's find-or-insert (model_[key]) for a key away from home
+    if (a.insert_keys) {
+      const uint64_t ek =
+          ((uint64_t)__float_as_uint(h1.w) << 32) | (uint64_t)__float_as_uint(h1.z);
+      if (ek != key) {  // group-uniform
+        int sf = 0;
+        if (l == 0) {
+          bool inserted;
+          const int64_t r = tbl_insert(a.T, key, &inserted);
+          if (r < 0) atomicOr(&a.dsw->err, insert_error(r));
+          sf = r < 0 ? (int)kNoSlot : (int)r;
+          nins = inserted ? 1 : 0;
+        }
+        sl = (uint32_t)__shfl(sf, gb, kWave);
+        dead = sl == kNoSlot;
+        if (!dead) line_load<G>(a.T, (int64_t)sl, l, gb, ntb, &h0, &h1, vcur, ccur);
+      }
+    }
+    if (dead) {  // not in the table (the error word says why): read as absent, no update
+      h0 = make_float4(0.f, __int_as_float(-1), 0.f, 0.f);
+      h1.x = 0.f;
+    }
+    float4 e = make_float4(h0.x, h0.z, h0.w, h1.x);  // {w, sqrt_g, z, fea_cnt}
+    const int vrow = __float_as_int(h0.y);           // (the key's own slot, or -1)
+    // V was pulled iff present and not (l1_shrk && w == 0) (SGDUpdater::Get, :40-43)
+    const int vq = (vrow >= 0 && !(a.Pm.l1_shrk && e.x == 0.f)) ? vrow : -1;
+    // ---- p and XV*p of the first occurrences' rows (XV*p only for a key whose V takes part)
+    const float* zp = a.zpad + ((cidx & 255u) << 4);
+    float g0[CPL], pr[UNR], xr[UNR][CPL];
+#pragma unroll
+    for (int k = 0; k < CPL; ++k) g0[k] = 0.f;
+#pragma unroll
+    for (int t = 0; t < UNR; ++t) {
+      pr[t] = xs > d ? a.XVp[(int64_t)row[t] * xs + d] : a.p[row[t]];
+      load_coords<CPL, true>(vq >= 0 ? a.XVp + (int64_t)row[t] * xs : zp, l, d, xr[t]);
+    }
+    float gw = 0.f, acc[CPL];
+    bwd_key_sums<G, CPL, true, UNR>(a, l, u, s0, s1, valued, d, xs, vq, row, x, pr, xr, vcur, g0, gw,
+                                    acc);
+    // Update(kGradient): UpdateW (FTRL), then UpdateV (AdaGrad) if V was pulled
+    bool tr;
+    const int dw = ftrl_update(a.Pm, gw, &e, &tr);
+    if (vq >= 0) {
+#pragma unroll
+      for (int k = 0; k < CPL; ++k) adagrad_update(a.Pm, acc[k], &vcur[k], &ccur[k]);
+    }
+    line_store<G>(a.T, dead ? 0 : (int64_t)sl, l, ntb, dead, vq >= 0 && 4 * l < d, e, vrow, vcur,
+                  ccur);
+    if (l == 0) {
+      dnew = dead ? 0 : dw;
+      // InitV on a 0 -> nonzero transition (sgd_updater.cc:118-121); e.w is fea_cnt
+      const bool need = !dead && tr && vrow < 0 && e.w > (float)a.Pm.V_threshold;
+      a.flags[u] = need ? 1u : 0u;
+      // InitV's slot: it reads the slots of flagged keys only (in the steady state none)
+      if (need && a.insert_keys) a.slot[cidx] = sl;
+      ninit = need ? 1 : 0;
+      nlive = vq >= 0 ? 1u : 0u;
+      nlocc = vq >= 0 ? len : 0u;
+    }
+  }
+  bwd_block_stats(a, dnew, ninit, nins, nlive, nlocc);
+}
+
+// the fused backward of a line table: G = the lanes of d / 4 float4 (bwd_lanes' layout, so
+// bwd_fused_blocks counts its blocks too)
+int launch_bwd_line(const BwdArgs& a, int64_t nseg_bound, hipStream_t st, long lds,
+                    size_t lds_default) {
+  const size_t lds_bytes = lds >= 0 ? (size_t)lds : lds_default;
+  if (nseg_bound <= 0) return DFX_OK;
+  if (line_es(a.d) == 0 || a.T.d != a.d || a.vlist) {
+    set_error("line slots: the fused backward needs V_dim 4, 8 or 12");
+    return DFX_ERR_ARG;
+  }
+  const int G = a.d == 4 ? 1 : a.d == 8 ? 2 : 4;
+  const int64_t spb = kFmNT / G;
+  const dim3 grid((unsigned)((nseg_bound + spb - 1) / spb));
+  if (G == 1) hipLaunchKernelGGL(k_fm_bwd_line<1>, grid, dim3(kFmNT), lds_bytes, st, a);
+  else if (G == 2) hipLaunchKernelGGL(k_fm_bwd_line<2>, grid, dim3(kFmNT), lds_bytes, st, a);
+  else hipLaunchKernelGGL(k_fm_bwd_line<4>, grid, dim3(kFmNT), lds_bytes, st, a);
+  DFX_HIP(hipGetLastError());
+  return DFX_OK;
+}
+
+}  // namespace dfx

@@ -35,14 +35,18 @@ constexpr int kIvNT = 256;  // threads of every InitV block
 static_assert(kIvNT == kFinNT, "the fused InitV's blocks run the step's finalize");
 
 // One key's place: its V row (the own-th new row of this owner in the split layout, its slot
-// with fat slots) written to its entry, and the rand_r state at its first draw, 3 * d * all steps
+// with fat or line slots) written to its entry, and the rand_r state at its first draw, 3 * d * all steps
 // past the seed (all: its rank over every owner's draws of this Update).  seed and nv0 are the
 // store's as of the kernel's start.  A full pool: kErrPoolFull, no row, 0xFFFFFFFF returned.
+// LINE (here and below): the table has line slots — Vaux behind V in the slot, a V row per slot
+// and no pool.  A template parameter, not a test of Table::line, so that the kernels of the
+// split and fat layouts are the code they were
+template <bool LINE = false>
 __device__ inline uint32_t initv_place(const Table& T, uint32_t seed, uint64_t nv0, uint32_t own,
                                        uint64_t all, uint32_t slot, int* err, uint32_t* state) {
   *state = lcg_advance(seed, 3ull * (uint64_t)T.d * all);
   const int64_t vr = initv_row(T, nv0, own, slot);
-  if (vr >= T.vcap) {
+  if (vr >= (LINE ? (int64_t)T.mask + 1 : T.vcap)) {
     atomicOr(err, kErrPoolFull);
     return 0xFFFFFFFFu;
   }
@@ -57,20 +61,26 @@ __device__ inline void initv_jumps(int d, uint32_t* A, uint32_t* C) {
 
 // The block's n placed keys drawn (st, vrow: initv_place's, in LDS; the caller's barriers around
 // it): a coordinate per thread, or a whole row per thread where V is wider than kIvMaxD
+template <bool LINE = false>
 __device__ inline void initv_draw(const Table& T, uint32_t n, const uint32_t* st,
                                   const uint32_t* vrow, float scale, const uint32_t* A,
                                   const uint32_t* C) {
   const int d = T.d;
+  if constexpr (LINE) {  // (d <= 12)
+    initv_draw_list<kIvNT>(n, st, vrow, d, scale, A, C, [&](uint32_t r) { return row_V(T, r); },
+                           [&](uint32_t r) { return row_V(T, r) + d; });
+    return;
+  }
   if (d <= kIvMaxD) {
     initv_draw_list<kIvNT>(n, st, vrow, d, scale, A, C, [&](uint32_t r) { return row_V(T, r); },
-                           [&](uint32_t r) { return row_C(T, r); });
+                           [&](uint32_t r) { return row_C_pool(T, r); });
     return;
   }
   for (uint32_t i = threadIdx.x; i < n; i += kIvNT) {
     if (vrow[i] == 0xFFFFFFFFu) continue;
     uint32_t s = st[i];
     float* V = row_V(T, vrow[i]);
-    float* Cg = row_C(T, vrow[i]);
+    float* Cg = row_C_pool(T, vrow[i]);
     for (int k = 0; k < d; ++k) {
       V[k] = initv_value(rand_r_dev(&s), scale);
       Cg[k] = 0.f;
@@ -108,10 +118,12 @@ __device__ inline bool initv_arrive(unsigned long long* word, uint32_t v, uint32
 constexpr int kIvItems = 32, kIvTile = kIvNT * kIvItems, kIvList = 4096;
 
 // -> the request count of the step if this block took the last tile, else 0
+template <bool LINE>
 __device__ uint32_t initv_onepass_body(const uint32_t* flags, const uint32_t* slot, const Table& T,
                                        float scale, DevState* ds, unsigned long long* status,
                                        int64_t n, uint32_t need);
 
+template <bool LINE>
 __global__ __launch_bounds__(kIvNT) void k_initv_onepass(const uint32_t* flags,
                                                          const uint32_t* slot, Table T,
                                                          float scale, DevState* ds,
@@ -126,11 +138,12 @@ __global__ __launch_bounds__(kIvNT) void k_initv_onepass(const uint32_t* flags,
     return;
   }
   if (blockIdx.x >= need) return;
-  const uint32_t part = initv_onepass_body(flags, slot, T, scale, ds, status, n, need);
+  const uint32_t part = initv_onepass_body<LINE>(flags, slot, T, scale, ds, status, n, need);
   uint32_t total;
   if (initv_arrive(&ds->iv_done, part, need, &total)) step_finalize_body<kFinNT>(fin, total, s_red);
 }
 
+template <bool LINE>
 __device__ uint32_t initv_onepass_body(const uint32_t* flags, const uint32_t* slot, const Table& T,
                                        float scale, DevState* ds, unsigned long long* status,
                                        int64_t n, uint32_t need) {
@@ -193,12 +206,13 @@ __device__ uint32_t initv_onepass_body(const uint32_t* flags, const uint32_t* sl
         if (idx >= q0 + kIvList) break;
         const int64_t u = i0 + (__ffs(m) - 1);
         const uint32_t e = pre + idx;
-        s_vr[idx - q0] = initv_place(T, seed, nv0, e, e, slot[u], &ds->err, &s_st[idx - q0]);
+        s_vr[idx - q0] =
+            initv_place<LINE>(T, seed, nv0, e, e, slot[u], &ds->err, &s_st[idx - q0]);
       }
     }
     __syncthreads();
-    initv_draw(T, tot - q0 < (uint32_t)kIvList ? tot - q0 : (uint32_t)kIvList, s_st, s_vr, scale,
-               s_A, s_C);
+    initv_draw<LINE>(T, tot - q0 < (uint32_t)kIvList ? tot - q0 : (uint32_t)kIvList, s_st, s_vr,
+                     scale, s_A, s_C);
     __syncthreads();
   }
   return part;
@@ -253,6 +267,7 @@ __global__ __launch_bounds__(kIvNT) void k_initv_rank_count(const uint32_t* flag
   *count_out = (int64_t)F;
 }
 
+template <bool LINE>
 __global__ __launch_bounds__(kIvNT) void k_initv_rank_draw(
     const uint32_t* flags, int64_t bound, const uint32_t* nuniq, const uint32_t* ftotal,
     const uint32_t* ts, const uint32_t* segslot, const int64_t* Fall, int rank, int nranks,
@@ -295,10 +310,10 @@ __global__ __launch_bounds__(kIvNT) void k_initv_rank_draw(
         uint32_t cnt;
         const uint32_t at = block_excl_scan<kIvNT>(f ? 1u : 0u, lds, &cnt);
         if (f)
-          s_vr[at] = initv_place(T, seed, nv0, base + at, (uint64_t)off + base + at, segslot[u],
-                                 &ds->err, &s_st[at]);
+          s_vr[at] = initv_place<LINE>(T, seed, nv0, base + at, (uint64_t)off + base + at,
+                                       segslot[u], &ds->err, &s_st[at]);
         __syncthreads();
-        initv_draw(T, cnt, s_st, s_vr, scale, s_A, s_C);
+        initv_draw<LINE>(T, cnt, s_st, s_vr, scale, s_A, s_C);
         base += cnt;
         __syncthreads();
       }
@@ -310,7 +325,7 @@ __global__ __launch_bounds__(kIvNT) void k_initv_rank_draw(
   uint32_t none;
   if (!initv_arrive(ticket, 0u, gridDim.x, &none) || threadIdx.x != 0) return;
   if (fcount) *fcount = 0u;
-  initv_advance(ds, T.d, (uint64_t)tot, F, T.vcap);
+  initv_advance(ds, T.d, (uint64_t)tot, F, LINE ? (int64_t)T.mask + 1 : T.vcap);
   if (cap_host) {
     cap_host[0] = ds->n_keys;
     cap_host[1] = ds->n_vrows;
@@ -335,9 +350,14 @@ int initv_rank_draw(Context* c, const Lane& L, const uint32_t* flags, const uint
   const int64_t ntiles = std::max<int64_t>(1, (bound + kIvrTile - 1) / kIvrTile);
   DFX_TRY(L.ws->tiles.ensure(sizeof(uint32_t) * (ntiles + 1)));
   const dim3 g((unsigned)std::min<int64_t>(ntiles, kIvrGrid));
-  hipLaunchKernelGGL(k_initv_rank_draw, g, dim3(kIvNT), 0, L.stream, flags, bound, nuniq, ftotal,
-                     L.ws->tiles.as<uint32_t>(), segslot, counts_all, rank, nranks, c->T,
-                     c->P.V_init_scale, c->ds, fcount, &L.ds->ivr_ticket[1], cap_host);
+  if (c->T.line)
+    hipLaunchKernelGGL(k_initv_rank_draw<true>, g, dim3(kIvNT), 0, L.stream, flags, bound, nuniq,
+                       ftotal, L.ws->tiles.as<uint32_t>(), segslot, counts_all, rank, nranks, c->T,
+                       c->P.V_init_scale, c->ds, fcount, &L.ds->ivr_ticket[1], cap_host);
+  else
+    hipLaunchKernelGGL(k_initv_rank_draw<false>, g, dim3(kIvNT), 0, L.stream, flags, bound, nuniq,
+                       ftotal, L.ws->tiles.as<uint32_t>(), segslot, counts_all, rank, nranks, c->T,
+                       c->P.V_init_scale, c->ds, fcount, &L.ds->ivr_ticket[1], cap_host);
   DFX_HIP(hipGetLastError());
   return DFX_OK;
 }
@@ -352,9 +372,14 @@ int run_initv(Context* c, int64_t n_bound, const uint32_t* flags, const uint32_t
     DFX_TRY(ws.ivstat.ensure((size_t)ntiles * 8));
     if (ws.ivstat.p != before)  // fresh words read as unpublished (tag 0, flag 0)
       DFX_HIP(hipMemsetAsync(ws.ivstat.p, 0, ws.ivstat.bytes, c->stream));
-    hipLaunchKernelGGL(k_initv_onepass, dim3((unsigned)ntiles), dim3(kIvNT), 0, c->stream, flags,
-                       slot, c->T, c->P.V_init_scale, c->ds, nds, &c->ds->n_init,
-                       ws.ivstat.as<unsigned long long>(), *fin);
+    if (c->T.line)
+      hipLaunchKernelGGL(k_initv_onepass<true>, dim3((unsigned)ntiles), dim3(kIvNT), 0, c->stream,
+                         flags, slot, c->T, c->P.V_init_scale, c->ds, nds, &c->ds->n_init,
+                         ws.ivstat.as<unsigned long long>(), *fin);
+    else
+      hipLaunchKernelGGL(k_initv_onepass<false>, dim3((unsigned)ntiles), dim3(kIvNT), 0, c->stream,
+                         flags, slot, c->T, c->P.V_init_scale, c->ds, nds, &c->ds->n_init,
+                         ws.ivstat.as<unsigned long long>(), *fin);
     DFX_HIP(hipGetLastError());
     return DFX_OK;
   }

@@ -30,6 +30,12 @@ void set_error(const std::string& msg);
     }                                         \
   } while (0)
 
+// the sharded stores (dfx_dist_*, dfx_split_*) run over a pool: not on line slots
+#define DFX_NO_LINE(ctx)                                                                      \
+  DFX_CHECK_ARG(!(ctx)->c.slot_line,                                                          \
+                "slot_layout=line is the single-GPU context only: the sharded stores "        \
+                "(dfx_dist_*, dfx_split_*) need slot_layout=auto, split or fat")
+
 #define DFX_TRY(expr)             \
   do {                            \
     int _rc = (expr);             \
@@ -278,6 +284,7 @@ struct Context {
   long bwd_lds = -1;  // LDS bytes reserved per fused-backward block (kwarg bwd_lds; -1 default)
   int autogrow = 1;   // grow the table / V pool before a step could overflow them (kwarg)
   int slot_es = 0;    // Table::es of this context's store (kwarg slot_layout)
+  int slot_line = 0;  // Table::line: slot_layout=line
   int fat_fwd = 1;    // kwarg fat_fwd
   int fwd_cpl = 8;        // kwarg fwd_cpl: V coordinates per lane of the probe forward
   int nt_mask = 0;        // kwarg nt (common.h kNt*)

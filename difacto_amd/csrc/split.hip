@@ -362,6 +362,7 @@ int dfx_split_pxv_floats(dfx_ctx* ctx) {
 int dfx_split_partition(dfx_ctx* ctx, int slot, const dfx_batch* b, uint64_t max_index,
                         int nranks, uint64_t* keys_out, float* x_out, uint32_t* row_cnt_out) {
   DFX_CHECK_ARG(ctx && b, "null argument");
+  DFX_NO_LINE(ctx);
   DFX_SPLIT_SLOT(slot);
   DFX_CHECK_ARG(nranks >= 1 && nranks <= kMaxDistRanks, "split: 1 <= nranks <= 64");
   DFX_CHECK_ARG(b->size >= 0 && b->nnz >= 0, "split_partition: negative sizes");
@@ -411,6 +412,7 @@ int dfx_split_partition(dfx_ctx* ctx, int slot, const dfx_batch* b, uint64_t max
 
 int dfx_split_partition_wait(dfx_ctx* ctx, int slot, int nranks, int64_t* split_counts) {
   DFX_CHECK_ARG(ctx && split_counts, "null argument");
+  DFX_NO_LINE(ctx);
   DFX_SPLIT_SLOT(slot);
   DFX_CHECK_ARG(nranks >= 1 && nranks <= kMaxDistRanks, "split: 1 <= nranks <= 64");
   Context* c = &ctx->c;
@@ -425,6 +427,7 @@ int dfx_split_owner_begin(dfx_ctx* ctx, int slot, const uint64_t* keys, const fl
                           const int64_t* keys_per_rank, int nranks, int job_type,
                           int push_cnt, int lane) {
   DFX_CHECK_ARG(ctx && rows_per_rank && keys_per_rank, "null argument");
+  DFX_NO_LINE(ctx);
   DFX_SPLIT_SLOT(slot);
   DFX_CHECK_ARG(nranks >= 1 && nranks <= kMaxDistRanks, "split: 1 <= nranks <= 64");
   Context* c = &ctx->c;
@@ -526,6 +529,7 @@ int dfx_split_owner_begin(dfx_ctx* ctx, int slot, const uint64_t* keys, const fl
 int dfx_split_owner_forward_rows(dfx_ctx* ctx, int slot, float* part_out, int nranks, int64_t M,
                                  int64_t lo, int64_t len) {
   DFX_CHECK_ARG(ctx, "null ctx");
+  DFX_NO_LINE(ctx);
   DFX_SPLIT_SLOT(slot);
   Context* c = &ctx->c;
   DFX_CHECK_ARG(!c->split_initv_pending[slot],
@@ -579,6 +583,7 @@ int dfx_split_combine_rows(dfx_ctx* ctx, int slot, const dfx_batch* b, const flo
                            int64_t part_rows, int nranks, float* pxv_out, float* pred_out,
                            int64_t lo, int64_t len) {
   DFX_CHECK_ARG(ctx && b, "null argument");
+  DFX_NO_LINE(ctx);
   DFX_SPLIT_SLOT(slot);
   DFX_CHECK_ARG(nranks >= 1 && nranks <= kMaxDistRanks, "split: 1 <= nranks <= 64");
   DFX_CHECK_ARG(lo >= 0 && len >= 1 && lo % 256 == 0,
@@ -664,6 +669,7 @@ int dfx_split_combine(dfx_ctx* ctx, int slot, const dfx_batch* b, const float* p
 
 int dfx_split_owner_backward(dfx_ctx* ctx, int slot, const float* pxv) {
   DFX_CHECK_ARG(ctx, "null ctx");
+  DFX_NO_LINE(ctx);
   DFX_SPLIT_SLOT(slot);
   Context* c = &ctx->c;
   DFX_CHECK_ARG(!any_pending(c->split_initv_pending),
@@ -715,6 +721,7 @@ int dfx_split_owner_backward(dfx_ctx* ctx, int slot, const float* pxv) {
 int dfx_split_owner_stats(dfx_ctx* ctx, int slot, int64_t* rows, int64_t* nnz,
                           int64_t* n_uniq) {
   DFX_CHECK_ARG(ctx && rows && nnz && n_uniq, "null argument");
+  DFX_NO_LINE(ctx);
   DFX_SPLIT_SLOT(slot);
   Context* c = &ctx->c;
   *rows = c->split_rows[slot];
@@ -731,6 +738,7 @@ int dfx_split_owner_stats(dfx_ctx* ctx, int slot, int64_t* rows, int64_t* nnz,
 
 int dfx_split_initv_local(dfx_ctx* ctx, int slot, int64_t* count_dev) {
   DFX_CHECK_ARG(ctx && count_dev, "null argument");
+  DFX_NO_LINE(ctx);
   DFX_SPLIT_SLOT(slot);
   Context* c = &ctx->c;
   const Lane OL = split_owner_lane(c, slot);
@@ -749,6 +757,7 @@ int dfx_split_initv_local(dfx_ctx* ctx, int slot, int64_t* count_dev) {
 int dfx_split_initv_draw(dfx_ctx* ctx, int slot, const int64_t* counts_all_dev, int rank,
                          int nranks) {
   DFX_CHECK_ARG(ctx && counts_all_dev, "null argument");
+  DFX_NO_LINE(ctx);
   DFX_SPLIT_SLOT(slot);
   DFX_CHECK_ARG(nranks >= 1 && nranks <= kMaxDistRanks && rank >= 0 && rank < nranks,
                 "split_initv_draw: bad rank");

@@ -403,7 +403,7 @@ int train_step(Context* c, const dfx_batch* b, int job_type, int push_cnt, uint6
   // kernel of its own
   FinArgs fin;
   fin.ds = c->ds; fin.bds = bds; fin.B = B; fin.initv = initv;
-  fin.d = d; fin.vcap = c->T.vcap; fin.loss_part = a.loss_part; fin.nparts = nblk;
+  fin.d = d; fin.vcap = vrow_cap(c->T); fin.loss_part = a.loss_part; fin.nparts = nblk;
   if (bwd_runs) {
     BwdArgs g{};
     g.segstart = segstart; g.ds = bds; g.nseg_host = -1; g.segcol = nullptr;

@@ -222,10 +222,42 @@ __global__ void k_rehash(Table O, int64_t ocap, Table T, DevState* ds, uint32_t*
   *ent_at(T, s) = e;
 }
 
-// slots (and, with fat slots, the Vaux pool: one row per slot) for capacity cap
+// k_rehash for line slots: a slot moves whole.  PL = the slot's 16-byte pieces (4 or 8)
+// consecutive lanes take old slot i, lane q its piece q, one coalesced read of the slot; the
+// key rides in piece 1 ({fea_cnt, pad, key}), lane 0 inserts it into T and the lanes write their
+// pieces to the new slot, piece 0 with vrow turned to the new slot when the key has V
+template <int PL>
+__global__ __launch_bounds__(256) void k_rehash_line(Table O, int64_t ocap, Table T, DevState* ds,
+                                                     uint32_t* map) {
+  const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / PL;
+  const int q = threadIdx.x % PL;
+  const int gb = (int)(threadIdx.x % kWave) - q;
+  if (i >= ocap) return;  // (whole groups: 256 % PL == 0)
+  float4 pc = reinterpret_cast<const float4*>(ent_at(O, i))[q];
+  const uint64_t key = ((uint64_t)__float_as_uint(__shfl(pc.w, gb + 1, kWave)) << 32) |
+                       (uint64_t)__float_as_uint(__shfl(pc.z, gb + 1, kWave));
+  if (key == kEmptyKey) {
+    if (map && q == 0) map[i] = kNoSlot;
+    return;
+  }
+  long long s0 = 0;
+  if (q == 0) {
+    bool ins;
+    s0 = tbl_insert(T, key, &ins);
+    if (map) map[i] = s0 < 0 ? kNoSlot : (uint32_t)s0;
+    if (s0 < 0) atomicOr(&ds->err, kErrTableFull);
+  }
+  const int64_t s = __shfl(s0, gb, kWave);
+  if (s < 0) return;
+  if (q == 0 && __float_as_int(pc.y) >= 0) pc.y = __int_as_float((int32_t)s);  // vrow = the slot
+  reinterpret_cast<float4*>(ent_at(T, s))[q] = pc;
+}
+
+// slots (and, with fat slots, the Vaux pool: one row per slot; line slots have none) for
+// capacity cap
 static int table_alloc_entries(Table* T, int64_t cap, hipStream_t st) {
   DFX_HIP(hipMalloc(&T->ent, cap * (sizeof(Entry) << T->es)));
-  if (T->es) {
+  if (T->es && !T->line) {
     DFX_HIP(hipMalloc(&T->V, cap * (int64_t)T->d * sizeof(float)));
     T->vcap = cap;
   }
@@ -263,14 +295,21 @@ static int table_rebuild(Context* c, Table NT, int64_t new_cap) {
     remap = remap || (c->dist_live[s] && !c->dist_segs_pending[s] && c->dist_R[s] > 0);
   uint32_t* map = nullptr;
   if (remap) DFX_HIP(hipMalloc(&map, (size_t)c->cap * sizeof(uint32_t)));
-  hipLaunchKernelGGL(k_rehash, dim3((c->cap + 255) / 256), dim3(256), 0, c->stream, T,
-                     c->cap, NT, c->ds, map);
+  if (T.line && T.es == 1)
+    hipLaunchKernelGGL(k_rehash_line<4>, dim3((c->cap * 4 + 255) / 256), dim3(256), 0, c->stream,
+                       T, c->cap, NT, c->ds, map);
+  else if (T.line)
+    hipLaunchKernelGGL(k_rehash_line<8>, dim3((c->cap * 8 + 255) / 256), dim3(256), 0, c->stream,
+                       T, c->cap, NT, c->ds, map);
+  else
+    hipLaunchKernelGGL(k_rehash, dim3((c->cap + 255) / 256), dim3(256), 0, c->stream, T,
+                       c->cap, NT, c->ds, map);
   DFX_HIP(hipGetLastError());
   DFX_HIP(hipMemcpyAsync(&err1, &c->ds->err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   DFX_HIP(hipStreamSynchronize(c->stream));
   if ((err1 & ~err0) & kErrTableFull) {
     (void)hipFree(NT.ent);
-    if (NT.es) (void)hipFree(NT.V);
+    if (NT.es && NT.V) (void)hipFree(NT.V);
     if (map) (void)hipFree(map);
     DFX_HIP(hipMemcpy(&c->ds->err, &err0, sizeof(int), hipMemcpyHostToDevice));
     set_error("table rebuild: the new table cannot hold every key; the old table is kept");
@@ -289,7 +328,7 @@ static int table_rebuild(Context* c, Table NT, int64_t new_cap) {
     (void)hipFree(map);
   }
   (void)hipFree(T.ent);
-  if (T.es) (void)hipFree(T.V);
+  if (T.es && T.V) (void)hipFree(T.V);
   T = NT;
   c->cap = new_cap;
   return DFX_OK;
@@ -336,10 +375,11 @@ int table_alloc(Context* c, int64_t n_keys, int64_t n_vrows) {
   Table& T = c->T;
   T.d = c->P.V_dim;
   T.es = c->slot_es;
+  T.line = c->slot_line;
   DFX_TRY(table_alloc_entries(&T, cap, c->stream));
   DFX_HIP(hipStreamSynchronize(c->stream));
   c->cap = cap;
-  if (T.es) return DFX_OK;  // the Vaux pool came with the slots
+  if (T.es) return DFX_OK;  // the Vaux pool came with the slots (line slots: Vaux itself)
   T.vcap = T.d > 0 ? (n_vrows > 0 ? n_vrows : 1) : 0;
   if (T.d > 0) DFX_HIP(hipMalloc(&T.V, T.vcap * 2 * T.d * sizeof(float)));
   return DFX_OK;
@@ -384,7 +424,7 @@ static ReservePlan reserve_plan(const Context* c, int64_t n_keys, int64_t n_vrow
   while (p.cap < 2 * n_keys) p.cap <<= 1;
   if (p.cap > c->cap)
     p.bytes += p.cap * (int64_t)(sizeof(Entry) << T.es) +
-               (T.es ? p.cap * (int64_t)T.d * (int64_t)sizeof(float) : 0);
+               (T.es && !T.line ? p.cap * (int64_t)T.d * (int64_t)sizeof(float) : 0);
   p.pool = T.d > 0 && !T.es && n_vrows > T.vcap;  // fat slots: V grows with the slots
   if (p.pool) p.bytes += n_vrows * 2 * T.d * (int64_t)sizeof(float);
   return p;
@@ -489,10 +529,11 @@ void cap_release(Context* c) {
 static int grow_to(Context* c, int64_t need_keys, int64_t need_vrows, bool exact = false) {
   const Table& T = c->T;
   const bool gk = 2 * need_keys > c->cap;
-  const bool gv = T.d > 0 && need_vrows > T.vcap;
+  const bool gv = T.d > 0 && need_vrows > vrow_cap(T);
   if (!gk && !gv) return DFX_OK;
   return store_reserve(c, gk ? need_keys : 0,
-                       gv ? (exact ? need_vrows : std::max<int64_t>(2 * T.vcap, need_vrows)) : 0);
+                       gv ? (exact ? need_vrows : std::max<int64_t>(2 * vrow_cap(T), need_vrows))
+                          : 0);
 }
 
 int cap_check(Context* c, int64_t add) {
@@ -509,11 +550,11 @@ int cap_check(Context* c, int64_t add) {
   for (;;) {
     const int64_t pend = g.enq_total - g.known_enq + add;
     const bool keys_ok = 10 * (g.known_keys + pend) <= 9 * c->cap;
-    const bool vrows_ok = !has_v || g.known_vrows + pend <= c->T.vcap;
+    const bool vrows_ok = !has_v || g.known_vrows + pend <= vrow_cap(c->T);
     if (keys_ok && vrows_ok) break;
     const auto t0 = std::chrono::steady_clock::now();
     const bool room_ahead = 10 * (g.known_keys + kCapRunAhead * add) <= 9 * c->cap &&
-                            (!has_v || g.known_vrows + kCapRunAhead * add <= c->T.vcap);
+                            (!has_v || g.known_vrows + kCapRunAhead * add <= vrow_cap(c->T));
     if (g.count > 0 && room_ahead) {  // an older step's counts may show room: wait for it
       DFX_TRY(cap_pop_oldest(c, true, &popped));
       c->host_wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -661,19 +702,20 @@ static int for_each_entry(Context* c, int64_t s0, int64_t ns, std::vector<float>
   DFX_TRY(read_counters(c, &hc));
   if (T.es) {
     std::vector<Entry> raw((size_t)std::min<int64_t>(ns, kHostChunk) << T.es);
-    std::vector<float> aux((size_t)std::min<int64_t>(ns, kHostChunk) * d);
+    std::vector<float> aux(T.line ? 0 : (size_t)std::min<int64_t>(ns, kHostChunk) * d);
     for (int64_t i0 = s0; i0 < s0 + ns; i0 += kHostChunk) {
       const int64_t n = std::min<int64_t>(kHostChunk, s0 + ns - i0);
       DFX_HIP(hipMemcpy(raw.data(), ent_at(T, i0), ((size_t)n << T.es) * sizeof(Entry),
                         hipMemcpyDeviceToHost));
-      if (d > 0)
+      if (d > 0 && !T.line)
         DFX_HIP(hipMemcpy(aux.data(), T.V + i0 * d, (size_t)n * d * 4, hipMemcpyDeviceToHost));
       for (int64_t i = 0; i < n; ++i) {
         const Entry& e = raw[(size_t)i << T.es];
         if (e.key == kEmptyKey) continue;
         const bool v = e.vrow >= 0;
-        fn(e, v ? reinterpret_cast<const float*>(&raw[(size_t)i << T.es] + 1) : nullptr,
-           v ? aux.data() + (size_t)i * d : nullptr);
+        const float* V = reinterpret_cast<const float*>(&raw[(size_t)i << T.es] + 1);
+        // (line slots: Vaux came with the slot, behind V)
+        fn(e, v ? V : nullptr, v ? (T.line ? V + d : aux.data() + (size_t)i * d) : nullptr);
       }
     }
     return DFX_OK;
@@ -835,6 +877,18 @@ int dfx_store_stats(dfx_ctx* ctx, int64_t* n_keys, int64_t* n_vrows, double* new
   if (new_w) *new_w = (double)h.new_w;
   if (seed) *seed = h.seed;
   return dfx_sync(ctx);
+}
+
+// device bytes of the model: the slots, and the pool (the split layout's [V | Vaux] rows, fat
+// slots' Vaux rows; line slots have none: 0)
+int dfx_store_bytes(dfx_ctx* ctx, int64_t* table_bytes, int64_t* pool_bytes) {
+  DFX_CHECK_ARG(ctx, "null ctx");
+  const Context* c = &ctx->c;
+  const Table& T = c->T;
+  if (table_bytes) *table_bytes = T.ent ? c->cap * (int64_t)(sizeof(Entry) << T.es) : 0;
+  if (pool_bytes)
+    *pool_bytes = !T.V ? 0 : T.vcap * (int64_t)T.d * (int64_t)sizeof(float) * (T.es ? 1 : 2);
+  return DFX_OK;
 }
 
 // table health: the mean and the longest distance of a stored key from its home slot, and the

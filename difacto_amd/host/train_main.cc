@@ -1376,6 +1376,17 @@ int main(int argc, char** argv) {
   int rc = ParseArgs(argc, argv, &P, &rest, &err);
   if (rc == 0) rc = ResolveOptions(P, rest, env, &plan, &lines, &err);
   for (const std::string& line : lines) std::printf("%s\n", line.c_str());
+  // the store's slot layout, a context kwarg passed through (include/difacto_amd.h): said with
+  // the plan; line slots are the single context's (the sharded stores refuse them)
+  for (const auto& kv : rest) {
+    if (kv.first != "slot_layout") continue;
+    std::printf("slot_layout: %s\n", kv.second.c_str());
+    if (rc == 0 && plan.sharded && kv.second == "line") {
+      err = "slot_layout=line is the single-GPU context only: a sharded run needs "
+            "slot_layout=auto, split or fat";
+      rc = 1;
+    }
+  }
   std::fflush(stdout);
   if (rc != 0) {
     std::fprintf(stderr, "%s\n", err.c_str());

@@ -316,6 +316,12 @@ class Store:
         check(_lib.lib().dfx_store_evaluate(self.ctx.h, ctypes.byref(pen), ctypes.byref(nnz)))
         return pen.value, nnz.value
 
+    def bytes(self):
+        """-> (bytes of the table's slots, bytes of the V pool: 0 with slot_layout=line)"""
+        tb, pb = ctypes.c_int64(0), ctypes.c_int64(0)
+        check(_lib.lib().dfx_store_bytes(self.ctx.h, ctypes.byref(tb), ctypes.byref(pb)))
+        return tb.value, pb.value
+
     def probe_stats(self):
         """-> (mean probe distance, longest probe distance, table capacity)"""
         m, mx, cap = ctypes.c_double(0), ctypes.c_int64(0), ctypes.c_int64(0)

@@ -81,8 +81,11 @@ typedef struct dfx_progress {
  *   V_threshold, l1_shrk, seed          (sgd_param.h:79-123, fm_loss.h:19-27)
  * plus device-store sizing: max_keys (hash table keys, default 1<<22; the table grows by
  * itself at sync points, autogrow=0 turns that off), max_vrows (V pool rows of the split
- * layout, default max_keys); the store's slot layout: slot_layout=auto|split|fat (auto: a key's
- * entry and V share one 64/128-byte slot when 4 <= V_dim <= 24 and V_dim % 4 == 0); the
+ * layout, default max_keys); the store's slot layout: slot_layout=auto|split|fat|line (auto: a
+ * key's entry and V share one 64/128-byte slot when 4 <= V_dim <= 24 and V_dim % 4 == 0; line:
+ * V_dim 4, 8 or 12 only, else DFX_ERR_ARG — the entry, V and Vaux in one slot of 64 bytes
+ * (V_dim 4) or 128, a key's whole state in one 128-byte line and no V pool; same results bit for
+ * bit; the single-GPU context only: dfx_dist_* and dfx_split_* calls return DFX_ERR_ARG); the
  * sharded store's push_agg=sum|ranks and hash=ordered|mixed; and execution choices that do
  * not change results (A/B switches, measured in DESIGN.md): fwd_probe, xvp_row, bwd_lds,
  * sort_pack, sort_items, sort_lookback, auc_sort=radix|merge|bucket|wbucket, fat_fwd, fat_bwd,
@@ -690,6 +693,9 @@ int dfx_store_dump_dev(dfx_ctx* ctx, const char* path, int dump_aux, int need_re
                        int64_t chunk_slots, int64_t* stats, double* times);
 int dfx_store_stats(dfx_ctx* ctx, int64_t* n_keys, int64_t* n_vrows, double* new_w,
                     uint32_t* seed);
+/* device bytes of the model: the table's slots, and the V pool beside them (the split layout's
+ * [V | Vaux] rows, fat slots' Vaux rows; 0 with slot_layout=line, which has none) */
+int dfx_store_bytes(dfx_ctx* ctx, int64_t* table_bytes, int64_t* pool_bytes);
 /* table health: mean and longest distance of a stored key from its home slot; capacity in
  * slots (a test / diagnostics hook) */
 int dfx_store_probe_stats(dfx_ctx* ctx, double* mean_probe, int64_t* max_probe,
