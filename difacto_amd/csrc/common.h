@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "revbytes.h"
+#include "vaux16.h"
 
 namespace dfx {
 
@@ -29,6 +30,14 @@ __device__ inline float2 ld2(const float* p, bool nt) {
     return make_float2(v.x, v.y);
   }
   return *reinterpret_cast<const float2*>(p);
+}
+__device__ inline void st2(float* p, float2 v, bool nt) {
+  if (nt) {
+    const dfx_f2v x = {v.x, v.y};
+    __builtin_nontemporal_store(x, reinterpret_cast<dfx_f2v*>(p));
+  } else {
+    *reinterpret_cast<float2*>(p) = v;
+  }
 }
 __device__ inline void st4(float* p, float4 v, bool nt) {
   if (nt) {
@@ -214,7 +223,9 @@ struct Table {
   int es;
   // line slots (kwarg slot_layout=line, d = 4 / 8 / 12): Vaux lives in the slot too, behind V —
   // [Entry 32 B | V 4d B | Vaux 4d B | pad] in 64 bytes (d = 4) or 128 (d = 8, 12), a key's whole
-  // state in one 128-byte line; es as with fat slots (d = 8: 2, not 1), vrow = slot, no pool
+  // state in one 128-byte line; es as with fat slots (d = 8: 2, not 1), vrow = slot, no pool.
+  // line == 2 (kwarg vaux=f16, d = 16 only): Vaux is d fp16 — [Entry 32 B | V 64 B | Vaux 32 B],
+  // 128 bytes; stored through vaux16_round (vaux16.h), read back widened
   int line;
 };
 
@@ -228,8 +239,17 @@ __host__ __device__ inline float* row_V(const Table& t, int64_t vr) {
 __host__ __device__ inline float* row_C_pool(const Table& t, int64_t vr) {
   return t.es ? t.V + vr * (int64_t)t.d : t.V + vr * 2 * (int64_t)t.d + t.d;
 }
-__host__ __device__ inline float* row_C(const Table& t, int64_t vr) {
-  return t.line ? row_V(t, vr) + t.d : row_C_pool(t, vr);
+// Vaux coordinate k of V row vr in any layout, read and written: what every caller that can meet
+// a line table goes through.  With fp16 Vaux the read widens exactly and the write narrows to
+// the nearest fp16 — exact for what such a slot held (a rebuild, a load of its own file) and for
+// InitV's 0; an Update narrows by vaux16_round and hands the result here
+__host__ __device__ inline float vaux_get(const Table& t, int64_t vr, int k) {
+  if (t.line == 2) return f16_widen(reinterpret_cast<const uint16_t*>(row_V(t, vr) + t.d)[k]);
+  return (t.line ? row_V(t, vr) + t.d : row_C_pool(t, vr))[k];
+}
+__host__ __device__ inline void vaux_put(const Table& t, int64_t vr, int k, float c) {
+  if (t.line == 2) reinterpret_cast<uint16_t*>(row_V(t, vr) + t.d)[k] = (uint16_t)f16_nearest(c);
+  else (t.line ? row_V(t, vr) + t.d : row_C_pool(t, vr))[k] = c;
 }
 // the V rows the table has room for: the pool's, or with line slots one per slot
 __host__ __device__ inline int64_t vrow_cap(const Table& t) {
@@ -251,8 +271,9 @@ __host__ __device__ inline int fat_es(int d) {
 
 // line slot stride for V_dim d (0: d has no line layout): the entry, V and Vaux in 64 or 128
 // bytes — d = 4: 64; d = 8 (96 bytes of state, which would straddle lines at that stride) and
-// d = 12: 128
-__host__ __device__ inline int line_es(int d) {
+// d = 12: 128; d = 16 only with fp16 Vaux (h16; 32 + 64 + 32 bytes): 128
+__host__ __device__ inline int line_es(int d, bool h16 = false) {
+  if (h16) return d == 16 ? 2 : 0;
   return d == 4 ? 1 : (d == 8 || d == 12) ? 2 : 0;
 }
 

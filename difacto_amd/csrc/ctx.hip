@@ -87,6 +87,9 @@ struct Kw {
   // line (2): the entry, V and Vaux in one 128-byte line, no pool (V_dim 4, 8 or 12; the
   // single-GPU context only)
   int slot_layout = -1;
+  // vaux=f16 (with slot_layout=line at V_dim 16 only): Vaux stored as fp16, rounded by
+  // vaux16_round — an opt-in approximation of the reference's AdaGrad state, not its arithmetic
+  int vaux16 = 0;
   int fat_fwd = 1;  // fat_fwd=0: with fat slots, the split forward walk (A/B of the one-trip read)
   // diag=noauc|noloc|noauc_noloc: MEASUREMENT ONLY (the headroom of the side lanes): no AUC
   // lane, or each Localizer parity run once and its output reused (results are then wrong
@@ -210,6 +213,11 @@ static int parse_kwargs(const char* kwargs, Kw* kw) {
       else if (v == "line") kw->slot_layout = 2;
       else { set_error("unknown slot_layout: " + v + " (auto|split|fat|line)"); return DFX_ERR_ARG; }
     }
+    else if (k == "vaux") {
+      if (v == "f32") kw->vaux16 = 0;
+      else if (v == "f16") kw->vaux16 = 1;
+      else { set_error("unknown vaux: " + v + " (f32|f16)"); return DFX_ERR_ARG; }
+    }
     else if (k == "auc_sort") {
       if (v == "radix") kw->auc_sort = 1;
       else if (v == "merge") kw->auc_sort = 0;
@@ -251,8 +259,14 @@ static int parse_kwargs(const char* kwargs, Kw* kw) {
     set_error("slot_layout=fat needs 4 <= V_dim <= 24 with V_dim % 4 == 0");
     return DFX_ERR_ARG;
   }
-  if (kw->slot_layout == 2 && line_es(kw->P.V_dim) == 0) {
-    set_error("slot_layout=line needs V_dim 4, 8 or 12 (the entry, V and Vaux in one 128-byte line)");
+  if (kw->vaux16 && (kw->slot_layout != 2 || line_es(kw->P.V_dim, true) == 0)) {
+    set_error("vaux=f16 needs slot_layout=line and V_dim=16 (fp16 Vaux is what lets a V_dim 16 "
+              "key fit one 128-byte line; no other layout or V_dim has it)");
+    return DFX_ERR_ARG;
+  }
+  if (kw->slot_layout == 2 && !kw->vaux16 && line_es(kw->P.V_dim) == 0) {
+    set_error("slot_layout=line needs V_dim 4, 8 or 12 (the entry, V and Vaux in one 128-byte "
+              "line), or V_dim 16 with vaux=f16");
     return DFX_ERR_ARG;
   }
   return DFX_OK;
@@ -342,8 +356,8 @@ int dfx_ctx_create(int device, const char* kwargs, dfx_ctx** out) {
   c->dist_sum = kw.dist_sum;
   c->sort_pack = kw.sort_pack;
   c->auc_sort = kw.auc_sort;
-  c->slot_line = kw.slot_layout == 2;
-  c->slot_es = c->slot_line ? line_es(c->P.V_dim) : kw.slot_layout == 0 ? 0 : fat_es(c->P.V_dim);
+  c->slot_line = kw.slot_layout == 2 ? 1 + kw.vaux16 : 0;
+  c->slot_es = c->slot_line ? line_es(c->P.V_dim, kw.vaux16 != 0) : kw.slot_layout == 0 ? 0 : fat_es(c->P.V_dim);
   c->fat_fwd = kw.fat_fwd;
   c->nt_mask = kw.nt;
   c->bwd_two_pass = kw.bwd_two_pass;

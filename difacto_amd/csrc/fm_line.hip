@@ -393,20 +393,169 @@ __global__ __launch_bounds__(kFmNT) void k_fm_bwd_line(BwdArgs a) {
   bwd_block_stats(a, dnew, ninit, nins, nlive, nlocc);
 }
 
+// ---- ... with fp16 Vaux (slot_layout=line vaux=f16, V_dim 16) ---------------------------------
+// [Entry 32 B | V 64 B | Vaux 16 x fp16] is the line's eight pieces again, and a key's four lanes
+// (lane l: coordinates 4l..4l+3, k_fm_bwd's d = 16 layout) request them once, two loads each:
+//   lane l: V piece l;  lanes 0, 1: the entry halves;  lanes 2, 3: the two Vaux pieces (eight
+//   halves each: the coordinates of lanes 0, 1 and of lanes 2, 3)
+// G = 4 makes the group a DPP quad, so the pieces travel by quad_perm moves in the VALU, not
+// through the LDS crossbar as line_bcast's shuffles do: the entry halves are lanes 0 and 1 of
+// the quad broadcast, and a lane's four halves are dword pair l % 2 of lane 2 + l / 2's piece —
+// quad_perm [2, 2, 3, 3] of its four dwords and a select, widened in registers (f16_widen).
+// After the update every lane narrows its own four accumulators (vaux16_round) and the line is
+// written in one issue as it was read: the hot entry half from lane 0, a V piece and the lane's
+// own 8 bytes of Vaux from every lane — no trip back to lanes 2 and 3.
+template <int CTRL>
+__device__ __forceinline__ float4 quad_perm(float4 v) {
+  auto mv = [](float x) {
+    const int i = __float_as_int(x);
+    return __int_as_float(__builtin_amdgcn_update_dpp(i, i, CTRL, 0xF, 0xF, false));
+  };
+  return make_float4(mv(v.x), mv(v.y), mv(v.z), mv(v.w));
+}
+
+__device__ __forceinline__ void line16_load(const Table& T, int64_t s, int l, bool nt, float4* h0,
+                                            float4* h1, float (&v)[4], float (&c)[4]) {
+  const float* sp = reinterpret_cast<const float*>(ent_at(T, s));
+  const float4 fv = ld4(sp + 8 + 4 * l, nt);
+  const float4 fx = ld4(sp + (l < 2 ? 4 * l : 16 + 4 * l), nt);  // (Vaux: floats 24..31)
+  *h0 = quad_perm<0x00>(fx);                                    // quad_perm:[0,0,0,0]
+  *h1 = quad_perm<0x55>(fx);                                    // quad_perm:[1,1,1,1]
+  const float4 cx = quad_perm<0xFA>(fx);                        // quad_perm:[2,2,3,3]
+  const uint32_t c01 = __float_as_uint((l & 1) ? cx.z : cx.x);
+  const uint32_t c23 = __float_as_uint((l & 1) ? cx.w : cx.y);
+  v[0] = fv.x; v[1] = fv.y; v[2] = fv.z; v[3] = fv.w;
+  c[0] = f16_widen(c01 & 0xFFFFu); c[1] = f16_widen(c01 >> 16);
+  c[2] = f16_widen(c23 & 0xFFFFu); c[3] = f16_widen(c23 >> 16);
+}
+
+__global__ __launch_bounds__(kFmNT) void k_fm_bwd_line16(BwdArgs a) {
+  constexpr int G = 4, CPL = 4, UNR = 4, SPB = kFmNT / G;
+  const int g = threadIdx.x / G;
+  const int l = threadIdx.x % G;
+  const int gb = (int)(threadIdx.x % kWave) - l;
+  const int64_t u = (int64_t)blockIdx.x * SPB + g;
+  const int64_t nseg = a.nseg_host >= 0 ? a.nseg_host : (int64_t)a.ds->u_count;
+  int dnew = 0, ninit = 0, nins = 0;
+  unsigned nlive = 0, nlocc = 0;
+  if (u < nseg) {
+    const bool ntb = (a.nt & kNtBwdTable) != 0, nto = (a.nt & kNtBwdOcc) != 0;
+    const uint32_t s0 = ldnt(a.segstart + u, nto), s1 = ldnt(a.segstart + u + 1, nto);
+    const uint32_t cidx = a.segcol ? a.segcol[u] : (uint32_t)u;
+    const bool valued = a.occ_x != nullptr;
+    constexpr int d = 16;
+    const int64_t xs = a.xs > d ? a.xs : d;
+    const uint32_t len = s1 - s0;
+    // ---- the key's line and the first UNR occurrences of its segment, as in k_fm_bwd_line
+    uint64_t key = 0;
+    uint32_t sl = a.insert_keys ? 0u : a.slot[cidx];
+    bool dead = !a.insert_keys && sl == kNoSlot;
+    if (a.insert_keys) {
+      key = ldnt(a.uniq + cidx, nto);
+      sl = (uint32_t)tbl_hash(key, a.T);
+    }
+    float4 h0, h1;
+    float vcur[CPL], ccur[CPL];
+    line16_load(a.T, dead ? 0 : (int64_t)sl, l, ntb, &h0, &h1, vcur, ccur);
+    uint32_t row[UNR];
+    float x[UNR];
+#pragma unroll
+    for (int t = 0; t < UNR; ++t) {
+      const uint32_t i = s0 + ((uint32_t)t < len ? (uint32_t)t : 0u);
+      row[t] = occ_get(a, i, valued, nto, &x[t]);
+    }
+    // ---- the key check: Get's find-or-insert (model_[key]) for a key away from home
+    if (a.insert_keys) {
+      const uint64_t ek =
+          ((uint64_t)__float_as_uint(h1.w) << 32) | (uint64_t)__float_as_uint(h1.z);
+      if (ek != key) {  // group-uniform
+        int sf = 0;
+        if (l == 0) {
+          bool inserted;
+          const int64_t r = tbl_insert(a.T, key, &inserted);
+          if (r < 0) atomicOr(&a.dsw->err, insert_error(r));
+          sf = r < 0 ? (int)kNoSlot : (int)r;
+          nins = inserted ? 1 : 0;
+        }
+        sl = (uint32_t)__shfl(sf, gb, kWave);
+        dead = sl == kNoSlot;
+        if (!dead) line16_load(a.T, (int64_t)sl, l, ntb, &h0, &h1, vcur, ccur);
+      }
+    }
+    if (dead) {  // not in the table (the error word says why): read as absent, no update
+      h0 = make_float4(0.f, __int_as_float(-1), 0.f, 0.f);
+      h1.x = 0.f;
+    }
+    float4 e = make_float4(h0.x, h0.z, h0.w, h1.x);  // {w, sqrt_g, z, fea_cnt}
+    const int vrow = __float_as_int(h0.y);           // (the key's own slot, or -1)
+    // V was pulled iff present and not (l1_shrk && w == 0) (SGDUpdater::Get, :40-43)
+    const int vq = (vrow >= 0 && !(a.Pm.l1_shrk && e.x == 0.f)) ? vrow : -1;
+    // ---- p and XV*p of the first occurrences' rows (XV*p only for a key whose V takes part)
+    const float* zp = a.zpad + ((cidx & 255u) << 4);
+    float g0[CPL], pr[UNR], xr[UNR][CPL];
+#pragma unroll
+    for (int k = 0; k < CPL; ++k) g0[k] = 0.f;
+#pragma unroll
+    for (int t = 0; t < UNR; ++t) {
+      pr[t] = xs > d ? a.XVp[(int64_t)row[t] * xs + d] : a.p[row[t]];
+      load_coords<CPL, true>(vq >= 0 ? a.XVp + (int64_t)row[t] * xs : zp, l, d, xr[t]);
+    }
+    float gw = 0.f, acc[CPL];
+    bwd_key_sums<G, CPL, true, UNR>(a, l, u, s0, s1, valued, d, xs, vq, row, x, pr, xr, vcur, g0, gw,
+                                    acc);
+    // Update(kGradient): UpdateW (FTRL), then UpdateV (AdaGrad) if V was pulled; the new
+    // accumulators narrow to fp16 for the store only (eta and V have used them unrounded)
+    bool tr;
+    const int dw = ftrl_update(a.Pm, gw, &e, &tr);
+    uint32_t ch[CPL] = {0u, 0u, 0u, 0u};
+    if (vq >= 0) {
+#pragma unroll
+      for (int k = 0; k < CPL; ++k) {
+        const float gk = acc[k] + a.Pm.V_l2 * vcur[k];  // adagrad_update's g
+        adagrad_update(a.Pm, acc[k], &vcur[k], &ccur[k]);
+        ch[k] = vaux16_round(ccur[k], gk, e.y, 4 * l + k);
+      }
+    }
+    // ---- the write-back: one issue to the line
+    if (!dead) {
+      float* sp = reinterpret_cast<float*>(ent_at(a.T, (int64_t)sl));
+      if (l == 0) st4(sp, make_float4(e.x, __int_as_float(vrow), e.y, e.z), ntb);
+      if (vq >= 0) {
+        st4(sp + 8 + 4 * l, make_float4(vcur[0], vcur[1], vcur[2], vcur[3]), ntb);
+        st2(sp + 24 + 2 * l, make_float2(__uint_as_float(ch[0] | (ch[1] << 16)),
+                                         __uint_as_float(ch[2] | (ch[3] << 16))), ntb);
+      }
+    }
+    if (l == 0) {
+      dnew = dead ? 0 : dw;
+      // InitV on a 0 -> nonzero transition (sgd_updater.cc:118-121); e.w is fea_cnt
+      const bool need = !dead && tr && vrow < 0 && e.w > (float)a.Pm.V_threshold;
+      a.flags[u] = need ? 1u : 0u;
+      // InitV's slot: it reads the slots of flagged keys only (in the steady state none)
+      if (need && a.insert_keys) a.slot[cidx] = sl;
+      ninit = need ? 1 : 0;
+      nlive = vq >= 0 ? 1u : 0u;
+      nlocc = vq >= 0 ? len : 0u;
+    }
+  }
+  bwd_block_stats(a, dnew, ninit, nins, nlive, nlocc);
+}
+
 // the fused backward of a line table: G = the lanes of d / 4 float4 (bwd_lanes' layout, so
 // bwd_fused_blocks counts its blocks too)
 int launch_bwd_line(const BwdArgs& a, int64_t nseg_bound, hipStream_t st, long lds,
                     size_t lds_default) {
   const size_t lds_bytes = lds >= 0 ? (size_t)lds : lds_default;
   if (nseg_bound <= 0) return DFX_OK;
-  if (line_es(a.d) == 0 || a.T.d != a.d || a.vlist) {
-    set_error("line slots: the fused backward needs V_dim 4, 8 or 12");
+  if (line_es(a.d, a.T.line == 2) == 0 || a.T.d != a.d || a.vlist) {
+    set_error("line slots: the fused backward needs V_dim 4, 8 or 12, or 16 with vaux=f16");
     return DFX_ERR_ARG;
   }
   const int G = a.d == 4 ? 1 : a.d == 8 ? 2 : 4;
   const int64_t spb = kFmNT / G;
   const dim3 grid((unsigned)((nseg_bound + spb - 1) / spb));
-  if (G == 1) hipLaunchKernelGGL(k_fm_bwd_line<1>, grid, dim3(kFmNT), lds_bytes, st, a);
+  if (a.T.line == 2) hipLaunchKernelGGL(k_fm_bwd_line16, grid, dim3(kFmNT), lds_bytes, st, a);
+  else if (G == 1) hipLaunchKernelGGL(k_fm_bwd_line<1>, grid, dim3(kFmNT), lds_bytes, st, a);
   else if (G == 2) hipLaunchKernelGGL(k_fm_bwd_line<2>, grid, dim3(kFmNT), lds_bytes, st, a);
   else hipLaunchKernelGGL(k_fm_bwd_line<4>, grid, dim3(kFmNT), lds_bytes, st, a);
   DFX_HIP(hipGetLastError());

@@ -38,10 +38,10 @@ static_assert(kIvNT == kFinNT, "the fused InitV's blocks run the step's finalize
 // with fat or line slots) written to its entry, and the rand_r state at its first draw, 3 * d * all steps
 // past the seed (all: its rank over every owner's draws of this Update).  seed and nv0 are the
 // store's as of the kernel's start.  A full pool: kErrPoolFull, no row, 0xFFFFFFFF returned.
-// LINE (here and below): the table has line slots — Vaux behind V in the slot, a V row per slot
+// LINE (here and below; Table::line, 0 / 1 / 2): the table has line slots — Vaux behind V in the slot, a V row per slot
 // and no pool.  A template parameter, not a test of Table::line, so that the kernels of the
 // split and fat layouts are the code they were
-template <bool LINE = false>
+template <int LINE = 0>
 __device__ inline uint32_t initv_place(const Table& T, uint32_t seed, uint64_t nv0, uint32_t own,
                                        uint64_t all, uint32_t slot, int* err, uint32_t* state) {
   *state = lcg_advance(seed, 3ull * (uint64_t)T.d * all);
@@ -61,12 +61,17 @@ __device__ inline void initv_jumps(int d, uint32_t* A, uint32_t* C) {
 
 // The block's n placed keys drawn (st, vrow: initv_place's, in LDS; the caller's barriers around
 // it): a coordinate per thread, or a whole row per thread where V is wider than kIvMaxD
-template <bool LINE = false>
+template <int LINE = 0>
 __device__ inline void initv_draw(const Table& T, uint32_t n, const uint32_t* st,
                                   const uint32_t* vrow, float scale, const uint32_t* A,
                                   const uint32_t* C) {
   const int d = T.d;
-  if constexpr (LINE) {  // (d <= 12)
+  if constexpr (LINE == 2) {  // (d = 16; Vaux is fp16: the 0.f stored through the pointer is +0)
+    initv_draw_list<kIvNT>(n, st, vrow, d, scale, A, C, [&](uint32_t r) { return row_V(T, r); },
+                           [&](uint32_t r) { return reinterpret_cast<uint16_t*>(row_V(T, r) + d); });
+    return;
+  }
+  if constexpr (LINE == 1) {  // (d <= 12)
     initv_draw_list<kIvNT>(n, st, vrow, d, scale, A, C, [&](uint32_t r) { return row_V(T, r); },
                            [&](uint32_t r) { return row_V(T, r) + d; });
     return;
@@ -118,12 +123,12 @@ __device__ inline bool initv_arrive(unsigned long long* word, uint32_t v, uint32
 constexpr int kIvItems = 32, kIvTile = kIvNT * kIvItems, kIvList = 4096;
 
 // -> the request count of the step if this block took the last tile, else 0
-template <bool LINE>
+template <int LINE>
 __device__ uint32_t initv_onepass_body(const uint32_t* flags, const uint32_t* slot, const Table& T,
                                        float scale, DevState* ds, unsigned long long* status,
                                        int64_t n, uint32_t need);
 
-template <bool LINE>
+template <int LINE>
 __global__ __launch_bounds__(kIvNT) void k_initv_onepass(const uint32_t* flags,
                                                          const uint32_t* slot, Table T,
                                                          float scale, DevState* ds,
@@ -143,7 +148,7 @@ __global__ __launch_bounds__(kIvNT) void k_initv_onepass(const uint32_t* flags,
   if (initv_arrive(&ds->iv_done, part, need, &total)) step_finalize_body<kFinNT>(fin, total, s_red);
 }
 
-template <bool LINE>
+template <int LINE>
 __device__ uint32_t initv_onepass_body(const uint32_t* flags, const uint32_t* slot, const Table& T,
                                        float scale, DevState* ds, unsigned long long* status,
                                        int64_t n, uint32_t need) {
@@ -267,7 +272,7 @@ __global__ __launch_bounds__(kIvNT) void k_initv_rank_count(const uint32_t* flag
   *count_out = (int64_t)F;
 }
 
-template <bool LINE>
+template <int LINE>
 __global__ __launch_bounds__(kIvNT) void k_initv_rank_draw(
     const uint32_t* flags, int64_t bound, const uint32_t* nuniq, const uint32_t* ftotal,
     const uint32_t* ts, const uint32_t* segslot, const int64_t* Fall, int rank, int nranks,
@@ -350,12 +355,16 @@ int initv_rank_draw(Context* c, const Lane& L, const uint32_t* flags, const uint
   const int64_t ntiles = std::max<int64_t>(1, (bound + kIvrTile - 1) / kIvrTile);
   DFX_TRY(L.ws->tiles.ensure(sizeof(uint32_t) * (ntiles + 1)));
   const dim3 g((unsigned)std::min<int64_t>(ntiles, kIvrGrid));
-  if (c->T.line)
-    hipLaunchKernelGGL(k_initv_rank_draw<true>, g, dim3(kIvNT), 0, L.stream, flags, bound, nuniq,
+  if (c->T.line == 2)
+    hipLaunchKernelGGL(k_initv_rank_draw<2>, g, dim3(kIvNT), 0, L.stream, flags, bound, nuniq,
+                       ftotal, L.ws->tiles.as<uint32_t>(), segslot, counts_all, rank, nranks, c->T,
+                       c->P.V_init_scale, c->ds, fcount, &L.ds->ivr_ticket[1], cap_host);
+  else if (c->T.line)
+    hipLaunchKernelGGL(k_initv_rank_draw<1>, g, dim3(kIvNT), 0, L.stream, flags, bound, nuniq,
                        ftotal, L.ws->tiles.as<uint32_t>(), segslot, counts_all, rank, nranks, c->T,
                        c->P.V_init_scale, c->ds, fcount, &L.ds->ivr_ticket[1], cap_host);
   else
-    hipLaunchKernelGGL(k_initv_rank_draw<false>, g, dim3(kIvNT), 0, L.stream, flags, bound, nuniq,
+    hipLaunchKernelGGL(k_initv_rank_draw<0>, g, dim3(kIvNT), 0, L.stream, flags, bound, nuniq,
                        ftotal, L.ws->tiles.as<uint32_t>(), segslot, counts_all, rank, nranks, c->T,
                        c->P.V_init_scale, c->ds, fcount, &L.ds->ivr_ticket[1], cap_host);
   DFX_HIP(hipGetLastError());
@@ -372,12 +381,16 @@ int run_initv(Context* c, int64_t n_bound, const uint32_t* flags, const uint32_t
     DFX_TRY(ws.ivstat.ensure((size_t)ntiles * 8));
     if (ws.ivstat.p != before)  // fresh words read as unpublished (tag 0, flag 0)
       DFX_HIP(hipMemsetAsync(ws.ivstat.p, 0, ws.ivstat.bytes, c->stream));
-    if (c->T.line)
-      hipLaunchKernelGGL(k_initv_onepass<true>, dim3((unsigned)ntiles), dim3(kIvNT), 0, c->stream,
+    if (c->T.line == 2)
+      hipLaunchKernelGGL(k_initv_onepass<2>, dim3((unsigned)ntiles), dim3(kIvNT), 0, c->stream,
+                         flags, slot, c->T, c->P.V_init_scale, c->ds, nds, &c->ds->n_init,
+                         ws.ivstat.as<unsigned long long>(), *fin);
+    else if (c->T.line)
+      hipLaunchKernelGGL(k_initv_onepass<1>, dim3((unsigned)ntiles), dim3(kIvNT), 0, c->stream,
                          flags, slot, c->T, c->P.V_init_scale, c->ds, nds, &c->ds->n_init,
                          ws.ivstat.as<unsigned long long>(), *fin);
     else
-      hipLaunchKernelGGL(k_initv_onepass<false>, dim3((unsigned)ntiles), dim3(kIvNT), 0, c->stream,
+      hipLaunchKernelGGL(k_initv_onepass<0>, dim3((unsigned)ntiles), dim3(kIvNT), 0, c->stream,
                          flags, slot, c->T, c->P.V_init_scale, c->ds, nds, &c->ds->n_init,
                          ws.ivstat.as<unsigned long long>(), *fin);
     DFX_HIP(hipGetLastError());

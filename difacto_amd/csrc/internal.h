@@ -284,7 +284,7 @@ struct Context {
   long bwd_lds = -1;  // LDS bytes reserved per fused-backward block (kwarg bwd_lds; -1 default)
   int autogrow = 1;   // grow the table / V pool before a step could overflow them (kwarg)
   int slot_es = 0;    // Table::es of this context's store (kwarg slot_layout)
-  int slot_line = 0;  // Table::line: slot_layout=line
+  int slot_line = 0;  // Table::line: slot_layout=line (2: with vaux=f16)
   int fat_fwd = 1;    // kwarg fat_fwd
   int fwd_cpl = 8;        // kwarg fwd_cpl: V coordinates per lane of the probe forward
   int nt_mask = 0;        // kwarg nt (common.h kNt*)

@@ -131,7 +131,7 @@ __global__ __launch_bounds__(kNT) void k_mp_write(Table T, int64_t slot0, uint32
                    : __float_as_uint(e->z);
     } else {
       const int k = j - head;
-      v = __float_as_uint(k < d ? row_V(T, e->vrow)[k] : row_C(T, e->vrow)[k - d]);
+      v = __float_as_uint(k < d ? row_V(T, e->vrow)[k] : vaux_get(T, e->vrow, k - d));
     }
     const uint64_t g = base + 4ull * q;
     if (g + 4u <= cap) {
@@ -166,7 +166,7 @@ __device__ inline int mt_field(const Table& T, int64_t slot, int j, int aux, int
     case mt::kSqrtG: f = e->sqrt_g; break;
     case mt::kZ: f = e->z; break;
     case mt::kV: f = row_V(T, e->vrow)[k]; break;
-    default: f = row_C(T, e->vrow)[k]; break;
+    default: f = vaux_get(T, e->vrow, k); break;
   }
   return mt::fmt_field(what, u, f, j == nf - 1, out);
 }

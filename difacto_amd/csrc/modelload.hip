@@ -259,10 +259,9 @@ __global__ __launch_bounds__(kNT) void k_ml_insert(MlFile f, const uint4* __rest
     if (row < 0) continue;
     const uint32_t* src = f.F + g0 + (start[r] & 0x7FFFFFFFu) + (f.aux ? 6 : 4);
     float* V = row_V(T, row);
-    float* C = row_C(T, row);
     for (int k = threadIdx.x % G; k < d; k += G) {
       V[k] = __uint_as_float(src[k]);
-      C[k] = f.aux ? __uint_as_float(src[d + k]) : 0.f;
+      vaux_put(T, row, k, f.aux ? __uint_as_float(src[d + k]) : 0.f);
     }
   }
   block_count_add(ins, &ds->n_keys);

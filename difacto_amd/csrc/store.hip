@@ -158,9 +158,15 @@ __global__ __launch_bounds__(kStNT) void k_push_grad(int64_t n, const uint64_t* 
         } else if (vr < 0) {
           atomicOr(&ds->err, kErrNoV);
         } else {
+          // (fp16 Vaux: the store narrows by vaux16_round — g is adagrad_update's, e.y the new
+          // sqrt_g of this key's UpdateW above; eta and V use the unrounded accumulator)
           float* V = row_V(T, vr);
-          float* C = row_C(T, vr);
-          for (int k = 0; k < d; ++k) adagrad_update(P, vals[o + 1 + k], V + k, C + k);
+          for (int k = 0; k < d; ++k) {
+            float cg = vaux_get(T, vr, k);
+            const float g = vals[o + 1 + k] + P.V_l2 * V[k];
+            adagrad_update(P, vals[o + 1 + k], V + k, &cg);
+            vaux_put(T, vr, k, T.line == 2 ? f16_widen(vaux16_round(cg, g, e.y, k)) : cg);
+          }
         }
       }
       // InitV when w leaves 0 and the feature is frequent enough (sgd_updater.cc:118-121)
@@ -210,9 +216,9 @@ __global__ void k_rehash(Table O, int64_t ocap, Table T, DevState* ds, uint32_t*
   if (s < 0) { atomicOr(&ds->err, kErrTableFull); return; }
   if (T.es && e.vrow >= 0) {
     const float* V0 = row_V(O, e.vrow);
-    const float* C0 = row_C(O, e.vrow);
+    const float* C0 = row_C_pool(O, e.vrow);  // (line tables move by k_rehash_line)
     float* V1 = row_V(T, s);
-    float* C1 = row_C(T, s);
+    float* C1 = row_C_pool(T, s);
     for (int k = 0; k < T.d; ++k) {
       V1[k] = V0[k];
       C1[k] = C0[k];
@@ -626,10 +632,9 @@ __global__ void k_load(int64_t n, const uint64_t* keys, const float4* st, const 
       if (vr[i] >= 0 && T.es) {
         const float* src = VV + (vr[i] - vbase) * 2 * (int64_t)T.d;
         float* V = row_V(T, s);
-        float* C = row_C(T, s);
         for (int k = 0; k < T.d; ++k) {
           V[k] = src[k];
-          C[k] = src[T.d + k];
+          vaux_put(T, s, k, src[T.d + k]);  // (fp16 Vaux: the file's fp32, to the nearest)
         }
         en->vrow = (int32_t)s;
       } else if (vr[i] >= 0) {
@@ -702,7 +707,8 @@ static int for_each_entry(Context* c, int64_t s0, int64_t ns, std::vector<float>
   DFX_TRY(read_counters(c, &hc));
   if (T.es) {
     std::vector<Entry> raw((size_t)std::min<int64_t>(ns, kHostChunk) << T.es);
-    std::vector<float> aux(T.line ? 0 : (size_t)std::min<int64_t>(ns, kHostChunk) * d);
+    // (line slots: Vaux came with the slot, behind V; fp16 Vaux is widened into aux's one row)
+    std::vector<float> aux(T.line ? d : (size_t)std::min<int64_t>(ns, kHostChunk) * d);
     for (int64_t i0 = s0; i0 < s0 + ns; i0 += kHostChunk) {
       const int64_t n = std::min<int64_t>(kHostChunk, s0 + ns - i0);
       DFX_HIP(hipMemcpy(raw.data(), ent_at(T, i0), ((size_t)n << T.es) * sizeof(Entry),
@@ -714,8 +720,13 @@ static int for_each_entry(Context* c, int64_t s0, int64_t ns, std::vector<float>
         if (e.key == kEmptyKey) continue;
         const bool v = e.vrow >= 0;
         const float* V = reinterpret_cast<const float*>(&raw[(size_t)i << T.es] + 1);
-        // (line slots: Vaux came with the slot, behind V)
-        fn(e, v ? V : nullptr, v ? (T.line ? V + d : aux.data() + (size_t)i * d) : nullptr);
+        if (v && T.line == 2) {
+          uint16_t h[16];
+          memcpy(h, V + d, sizeof(h));
+          for (int k = 0; k < d; ++k) aux[k] = f16_widen(h[k]);
+        }
+        fn(e, v ? V : nullptr,
+           v ? (T.line == 1 ? V + d : T.line ? aux.data() : aux.data() + (size_t)i * d) : nullptr);
       }
     }
     return DFX_OK;
@@ -944,8 +955,14 @@ int dfx_store_entry(dfx_ctx* ctx, uint64_t key, float* state, float* V, int* has
       *has_v = e.vrow >= 0;
       if (e.vrow >= 0 && V) {
         DFX_HIP(hipMemcpy(V, row_V(T, e.vrow), T.d * 4, hipMemcpyDeviceToHost));
-        DFX_HIP(hipMemcpy(V + T.d, row_C(T, e.vrow), T.d * 4,
-                          hipMemcpyDeviceToHost));
+        if (T.line == 2) {  // fp16 Vaux, widened
+          uint16_t h[16];
+          DFX_HIP(hipMemcpy(h, row_V(T, e.vrow) + T.d, sizeof(h), hipMemcpyDeviceToHost));
+          for (int k = 0; k < T.d; ++k) V[T.d + k] = f16_widen(h[k]);
+        } else {
+          DFX_HIP(hipMemcpy(V + T.d, T.line ? row_V(T, e.vrow) + T.d : row_C_pool(T, e.vrow),
+                            T.d * 4, hipMemcpyDeviceToHost));
+        }
       }
       *found = 1;
       return DFX_OK;

@@ -1379,6 +1379,7 @@ int main(int argc, char** argv) {
   // the store's slot layout, a context kwarg passed through (include/difacto_amd.h): said with
   // the plan; line slots are the single context's (the sharded stores refuse them)
   for (const auto& kv : rest) {
+    if (kv.first == "vaux") std::printf("vaux: %s\n", kv.second.c_str());
     if (kv.first != "slot_layout") continue;
     std::printf("slot_layout: %s\n", kv.second.c_str());
     if (rc == 0 && plan.sharded && kv.second == "line") {

@@ -85,7 +85,12 @@ typedef struct dfx_progress {
  * key's entry and V share one 64/128-byte slot when 4 <= V_dim <= 24 and V_dim % 4 == 0; line:
  * V_dim 4, 8 or 12 only, else DFX_ERR_ARG — the entry, V and Vaux in one slot of 64 bytes
  * (V_dim 4) or 128, a key's whole state in one 128-byte line and no V pool; same results bit for
- * bit; the single-GPU context only: dfx_dist_* and dfx_split_* calls return DFX_ERR_ARG); the
+ * bit; the single-GPU context only: dfx_dist_* and dfx_split_* calls return DFX_ERR_ARG);
+ * vaux=f32|f16 (f16: with slot_layout=line at V_dim 16 only, else DFX_ERR_ARG — the AdaGrad
+ * accumulators Vaux stored as fp16 so that a V_dim 16 key fits one 128-byte line, rounded
+ * stochastically by a hash of each update's own operands (csrc/vaux16.h): an opt-in approximation
+ * of the reference's AdaGrad state, NOT its arithmetic, deterministic and exact against its own
+ * CPU restatement; model files hold fp32 Vaux, narrowed to the nearest fp16 on load); the
  * sharded store's push_agg=sum|ranks and hash=ordered|mixed; and execution choices that do
  * not change results (A/B switches, measured in DESIGN.md): fwd_probe, xvp_row, bwd_lds,
  * sort_pack, sort_items, sort_lookback, auc_sort=radix|merge|bucket|wbucket, fat_fwd, fat_bwd,
