@@ -209,8 +209,9 @@ $(DISTLIB): difacto_amd/host/split_host.cc difacto_amd/host/split_host.h \
 	  difacto_amd/host/split_host.cc -Ldifacto_amd -ldifacto_amd -L/opt/rocm/lib -lrccl -lamdhip64 \
 	  -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,/opt/rocm/lib
 
-# the line-slot backward: new code, built without packed fp32 arithmetic (v_pk_*_f32)
-$(OBJDIR)/fm_line.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+# the line-slot backward and the half-row kernels: new code, built without packed fp32 arithmetic
+# (v_pk_*_f32)
+$(OBJDIR)/fm_line.o $(OBJDIR)/fm_half.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJDIR)

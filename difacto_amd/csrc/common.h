@@ -6,6 +6,7 @@
 
 #include "revbytes.h"
 #include "vaux16.h"
+#include "vhalf.h"
 
 namespace dfx {
 
@@ -227,6 +228,10 @@ struct Table {
   // line == 2 (kwarg vaux=f16, d = 16 only): Vaux is d fp16 — [Entry 32 B | V 64 B | Vaux 32 B],
   // 128 bytes; stored through vaux16_round (vaux16.h), read back widened
   int line;
+  // half rows (kwarg vrows=f16, d = 32 / 64, the split layout only): the pool holds vcap rows of
+  // 4 d bytes, V as d fp16 bit patterns and Vaux as d more (vhalf.h); vrow and row allocation
+  // are the split layout's.  Last, so that the fields above stay where they were
+  int half;
 };
 
 __host__ __device__ inline Entry* ent_at(const Table& t, int64_t s) { return t.ent + (s << t.es); }
@@ -239,17 +244,38 @@ __host__ __device__ inline float* row_V(const Table& t, int64_t vr) {
 __host__ __device__ inline float* row_C_pool(const Table& t, int64_t vr) {
   return t.es ? t.V + vr * (int64_t)t.d : t.V + vr * 2 * (int64_t)t.d + t.d;
 }
+// A half row (Table::half): V's d fp16, then Vaux's
+__host__ __device__ inline uint16_t* half_row(const Table& t, int64_t vr) {
+  return reinterpret_cast<uint16_t*>(t.V) + vr * 2 * (int64_t)t.d;
+}
 // Vaux coordinate k of V row vr in any layout, read and written: what every caller that can meet
 // a line table goes through.  With fp16 Vaux the read widens exactly and the write narrows to
 // the nearest fp16 — exact for what such a slot held (a rebuild, a load of its own file) and for
 // InitV's 0; an Update narrows by vaux16_round and hands the result here
 __host__ __device__ inline float vaux_get(const Table& t, int64_t vr, int k) {
+  if (t.half) return f16_widen(half_row(t, vr)[t.d + k]);
   if (t.line == 2) return f16_widen(reinterpret_cast<const uint16_t*>(row_V(t, vr) + t.d)[k]);
   return (t.line ? row_V(t, vr) + t.d : row_C_pool(t, vr))[k];
 }
 __host__ __device__ inline void vaux_put(const Table& t, int64_t vr, int k, float c) {
-  if (t.line == 2) reinterpret_cast<uint16_t*>(row_V(t, vr) + t.d)[k] = (uint16_t)f16_nearest(c);
+  if (t.half) half_row(t, vr)[t.d + k] = (uint16_t)f16_nearest(c);
+  else if (t.line == 2) reinterpret_cast<uint16_t*>(row_V(t, vr) + t.d)[k] = (uint16_t)f16_nearest(c);
   else (t.line ? row_V(t, vr) + t.d : row_C_pool(t, vr))[k] = c;
+}
+// bytes of one pool row of the split layout: [V | Vaux] as fp32, or as fp16 in a half table
+__host__ __device__ inline int64_t pool_row_bytes(const Table& t) {
+  return (t.half ? 4 : 8) * (int64_t)t.d;
+}
+// V coordinate k of V row vr, beside vaux_get / vaux_put: what a caller that can meet a half
+// table goes through.  There the read widens exactly and the write narrows to the nearest fp16 —
+// exact for what such a row held and for a file it wrote; an Update narrows by vhalf_round /
+// vaux16_round and hands the widened result here
+__host__ __device__ inline float v_get(const Table& t, int64_t vr, int k) {
+  return t.half ? f16_widen(half_row(t, vr)[k]) : row_V(t, vr)[k];
+}
+__host__ __device__ inline void v_put(const Table& t, int64_t vr, int k, float v) {
+  if (t.half) half_row(t, vr)[k] = (uint16_t)f16_nearest(v);
+  else row_V(t, vr)[k] = v;
 }
 // the V rows the table has room for: the pool's, or with line slots one per slot
 __host__ __device__ inline int64_t vrow_cap(const Table& t) {

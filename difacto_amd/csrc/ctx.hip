@@ -90,6 +90,10 @@ struct Kw {
   // vaux=f16 (with slot_layout=line at V_dim 16 only): Vaux stored as fp16, rounded by
   // vaux16_round — an opt-in approximation of the reference's AdaGrad state, not its arithmetic
   int vaux16 = 0;
+  // vrows=f16 (V_dim 32 or 64, loss=fm, slot_layout=auto|split: the split layout): the pool's
+  // [V | Vaux] rows stored as fp16, rounded by vhalf_round / vaux16_round (vhalf.h) — an opt-in
+  // approximation of the reference, not its arithmetic; kernels of their own (fm_half.hip)
+  int vrows16 = 0;
   int fat_fwd = 1;  // fat_fwd=0: with fat slots, the split forward walk (A/B of the one-trip read)
   // diag=noauc|noloc|noauc_noloc: MEASUREMENT ONLY (the headroom of the side lanes): no AUC
   // lane, or each Localizer parity run once and its output reused (results are then wrong
@@ -218,6 +222,11 @@ static int parse_kwargs(const char* kwargs, Kw* kw) {
       else if (v == "f16") kw->vaux16 = 1;
       else { set_error("unknown vaux: " + v + " (f32|f16)"); return DFX_ERR_ARG; }
     }
+    else if (k == "vrows") {
+      if (v == "f32") kw->vrows16 = 0;
+      else if (v == "f16") kw->vrows16 = 1;
+      else { set_error("unknown vrows: " + v + " (f32|f16)"); return DFX_ERR_ARG; }
+    }
     else if (k == "auc_sort") {
       if (v == "radix") kw->auc_sort = 1;
       else if (v == "merge") kw->auc_sort = 0;
@@ -257,6 +266,13 @@ static int parse_kwargs(const char* kwargs, Kw* kw) {
   if (!kw->loss_fm) kw->P.V_dim = 0;  // LogitLoss ignores V (logit_loss.h)
   if (kw->slot_layout == 1 && fat_es(kw->P.V_dim) == 0) {
     set_error("slot_layout=fat needs 4 <= V_dim <= 24 with V_dim % 4 == 0");
+    return DFX_ERR_ARG;
+  }
+  if (kw->vrows16 && !(kw->loss_fm && (kw->P.V_dim == 32 || kw->P.V_dim == 64) &&
+                       kw->slot_layout <= 0 && !kw->vaux16)) {
+    set_error("vrows=f16 needs V_dim=32 or 64, loss=fm and slot_layout=auto or split, without "
+              "vaux=f16 (fp16 [V | Vaux] rows live in the split layout's pool; V_dim 128 is not "
+              "built)");
     return DFX_ERR_ARG;
   }
   if (kw->vaux16 && (kw->slot_layout != 2 || line_es(kw->P.V_dim, true) == 0)) {
@@ -358,6 +374,7 @@ int dfx_ctx_create(int device, const char* kwargs, dfx_ctx** out) {
   c->auc_sort = kw.auc_sort;
   c->slot_line = kw.slot_layout == 2 ? 1 + kw.vaux16 : 0;
   c->slot_es = c->slot_line ? line_es(c->P.V_dim, kw.vaux16 != 0) : kw.slot_layout == 0 ? 0 : fat_es(c->P.V_dim);
+  c->vrows_half = kw.vrows16;
   c->fat_fwd = kw.fat_fwd;
   c->nt_mask = kw.nt;
   c->bwd_two_pass = kw.bwd_two_pass;

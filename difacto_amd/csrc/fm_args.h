@@ -183,6 +183,12 @@ int launch_bwd_fused(const BwdArgs& a, int64_t nseg_bound, hipStream_t st, long 
 // lds_default: the fused backward's LDS reservation when lds < 0
 int launch_bwd_line(const BwdArgs& a, int64_t nseg_bound, hipStream_t st, long lds,
                     size_t lds_default);
+// ... and of a half-row table (kwarg vrows=f16, fm_half.hip), with its fused forward (probe
+// mode: a.index) and the blocks its backward launches over nseg_bound keys (BwdArgs::live_part)
+int launch_bwd_half(const BwdArgs& a, int64_t nseg_bound, hipStream_t st, long lds,
+                    size_t lds_default);
+int launch_fwd_half(const FwdArgs& a, hipStream_t st, int* nblk);
+int64_t bwd_half_blocks(int d, int64_t nseg_bound);
 // the chunk partials of long segments (before the backward reads them)
 int launch_bwd_chunks(const BwdArgs& a, int64_t chunk_bound, hipStream_t st, bool aligned);
 

@@ -39,14 +39,14 @@ static_assert(kIvNT == kFinNT, "the fused InitV's blocks run the step's finalize
 // past the seed (all: its rank over every owner's draws of this Update).  seed and nv0 are the
 // store's as of the kernel's start.  A full pool: kErrPoolFull, no row, 0xFFFFFFFF returned.
 // LINE (here and below; Table::line, 0 / 1 / 2): the table has line slots — Vaux behind V in the slot, a V row per slot
-// and no pool.  A template parameter, not a test of Table::line, so that the kernels of the
+// and no pool; 3: half rows in the split layout's pool (Table::half).  A template parameter, not a test of Table::line, so that the kernels of the
 // split and fat layouts are the code they were
 template <int LINE = 0>
 __device__ inline uint32_t initv_place(const Table& T, uint32_t seed, uint64_t nv0, uint32_t own,
                                        uint64_t all, uint32_t slot, int* err, uint32_t* state) {
   *state = lcg_advance(seed, 3ull * (uint64_t)T.d * all);
   const int64_t vr = initv_row(T, nv0, own, slot);
-  if (vr >= (LINE ? (int64_t)T.mask + 1 : T.vcap)) {
+  if (vr >= ((LINE == 1 || LINE == 2) ? (int64_t)T.mask + 1 : T.vcap)) {
     atomicOr(err, kErrPoolFull);
     return 0xFFFFFFFFu;
   }
@@ -66,6 +66,17 @@ __device__ inline void initv_draw(const Table& T, uint32_t n, const uint32_t* st
                                   const uint32_t* vrow, float scale, const uint32_t* A,
                                   const uint32_t* C) {
   const int d = T.d;
+  if constexpr (LINE == 3) {  // half rows (Table::half, d = 32 / 64): the draw to the nearest fp16
+    for (uint32_t q = threadIdx.x; q < n * (uint32_t)d; q += kIvNT) {
+      const uint32_t i = q / (uint32_t)d, j = q - i * (uint32_t)d;
+      if (vrow[i] == 0xFFFFFFFFu) continue;
+      uint32_t s = A[j] * st[i] + C[j];  // (initv_draw_list's draw)
+      uint16_t* row = half_row(T, vrow[i]);
+      row[j] = (uint16_t)f16_nearest(initv_value(rand_r_dev(&s), scale));
+      row[d + j] = 0;
+    }
+    return;
+  }
   if constexpr (LINE == 2) {  // (d = 16; Vaux is fp16: the 0.f stored through the pointer is +0)
     initv_draw_list<kIvNT>(n, st, vrow, d, scale, A, C, [&](uint32_t r) { return row_V(T, r); },
                            [&](uint32_t r) { return reinterpret_cast<uint16_t*>(row_V(T, r) + d); });
@@ -330,7 +341,7 @@ __global__ __launch_bounds__(kIvNT) void k_initv_rank_draw(
   uint32_t none;
   if (!initv_arrive(ticket, 0u, gridDim.x, &none) || threadIdx.x != 0) return;
   if (fcount) *fcount = 0u;
-  initv_advance(ds, T.d, (uint64_t)tot, F, LINE ? (int64_t)T.mask + 1 : T.vcap);
+  initv_advance(ds, T.d, (uint64_t)tot, F, (LINE == 1 || LINE == 2) ? (int64_t)T.mask + 1 : T.vcap);
   if (cap_host) {
     cap_host[0] = ds->n_keys;
     cap_host[1] = ds->n_vrows;
@@ -355,7 +366,11 @@ int initv_rank_draw(Context* c, const Lane& L, const uint32_t* flags, const uint
   const int64_t ntiles = std::max<int64_t>(1, (bound + kIvrTile - 1) / kIvrTile);
   DFX_TRY(L.ws->tiles.ensure(sizeof(uint32_t) * (ntiles + 1)));
   const dim3 g((unsigned)std::min<int64_t>(ntiles, kIvrGrid));
-  if (c->T.line == 2)
+  if (c->T.half)
+    hipLaunchKernelGGL(k_initv_rank_draw<3>, g, dim3(kIvNT), 0, L.stream, flags, bound, nuniq,
+                       ftotal, L.ws->tiles.as<uint32_t>(), segslot, counts_all, rank, nranks, c->T,
+                       c->P.V_init_scale, c->ds, fcount, &L.ds->ivr_ticket[1], cap_host);
+  else if (c->T.line == 2)
     hipLaunchKernelGGL(k_initv_rank_draw<2>, g, dim3(kIvNT), 0, L.stream, flags, bound, nuniq,
                        ftotal, L.ws->tiles.as<uint32_t>(), segslot, counts_all, rank, nranks, c->T,
                        c->P.V_init_scale, c->ds, fcount, &L.ds->ivr_ticket[1], cap_host);
@@ -381,7 +396,11 @@ int run_initv(Context* c, int64_t n_bound, const uint32_t* flags, const uint32_t
     DFX_TRY(ws.ivstat.ensure((size_t)ntiles * 8));
     if (ws.ivstat.p != before)  // fresh words read as unpublished (tag 0, flag 0)
       DFX_HIP(hipMemsetAsync(ws.ivstat.p, 0, ws.ivstat.bytes, c->stream));
-    if (c->T.line == 2)
+    if (c->T.half)
+      hipLaunchKernelGGL(k_initv_onepass<3>, dim3((unsigned)ntiles), dim3(kIvNT), 0, c->stream,
+                         flags, slot, c->T, c->P.V_init_scale, c->ds, nds, &c->ds->n_init,
+                         ws.ivstat.as<unsigned long long>(), *fin);
+    else if (c->T.line == 2)
       hipLaunchKernelGGL(k_initv_onepass<2>, dim3((unsigned)ntiles), dim3(kIvNT), 0, c->stream,
                          flags, slot, c->T, c->P.V_init_scale, c->ds, nds, &c->ds->n_init,
                          ws.ivstat.as<unsigned long long>(), *fin);

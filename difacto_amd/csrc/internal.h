@@ -34,7 +34,10 @@ void set_error(const std::string& msg);
 #define DFX_NO_LINE(ctx)                                                                      \
   DFX_CHECK_ARG(!(ctx)->c.slot_line,                                                          \
                 "slot_layout=line is the single-GPU context only: the sharded stores "        \
-                "(dfx_dist_*, dfx_split_*) need slot_layout=auto, split or fat")
+                "(dfx_dist_*, dfx_split_*) need slot_layout=auto, split or fat");             \
+  DFX_CHECK_ARG(!(ctx)->c.vrows_half,                                                         \
+                "vrows=f16 is the single-GPU context only: the sharded stores "               \
+                "(dfx_dist_*, dfx_split_*) need vrows=f32")
 
 #define DFX_TRY(expr)             \
   do {                            \
@@ -285,6 +288,7 @@ struct Context {
   int autogrow = 1;   // grow the table / V pool before a step could overflow them (kwarg)
   int slot_es = 0;    // Table::es of this context's store (kwarg slot_layout)
   int slot_line = 0;  // Table::line: slot_layout=line (2: with vaux=f16)
+  int vrows_half = 0; // Table::half: kwarg vrows=f16 (the split layout's pool rows as fp16)
   int fat_fwd = 1;    // kwarg fat_fwd
   int fwd_cpl = 8;        // kwarg fwd_cpl: V coordinates per lane of the probe forward
   int nt_mask = 0;        // kwarg nt (common.h kNt*)

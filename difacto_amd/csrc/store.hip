@@ -122,8 +122,7 @@ __global__ __launch_bounds__(kStNT) void k_pull_write(int64_t n, Table T, Params
   vals[o] = w;
   const int d = T.d;
   if (live) {
-    const float* V = row_V(T, vr);
-    for (int k = 0; k < d; ++k) vals[o + 1 + k] = V[k];
+    for (int k = 0; k < d; ++k) vals[o + 1 + k] = v_get(T, vr, k);
   }
   if (lens) lens[i] = live ? d + 1 : 1;
 }
@@ -160,12 +159,14 @@ __global__ __launch_bounds__(kStNT) void k_push_grad(int64_t n, const uint64_t* 
         } else {
           // (fp16 Vaux: the store narrows by vaux16_round — g is adagrad_update's, e.y the new
           // sqrt_g of this key's UpdateW above; eta and V use the unrounded accumulator)
-          float* V = row_V(T, vr);
+          // (half rows: V narrows by vhalf_round too, as the fused backward does)
           for (int k = 0; k < d; ++k) {
-            float cg = vaux_get(T, vr, k);
-            const float g = vals[o + 1 + k] + P.V_l2 * V[k];
-            adagrad_update(P, vals[o + 1 + k], V + k, &cg);
-            vaux_put(T, vr, k, T.line == 2 ? f16_widen(vaux16_round(cg, g, e.y, k)) : cg);
+            float cg = vaux_get(T, vr, k), v = v_get(T, vr, k);
+            const float g = vals[o + 1 + k] + P.V_l2 * v;
+            adagrad_update(P, vals[o + 1 + k], &v, &cg);
+            v_put(T, vr, k, T.half ? f16_widen(vhalf_round(v, g, e.y, k)) : v);
+            vaux_put(T, vr, k,
+                     T.line == 2 || T.half ? f16_widen(vaux16_round(cg, g, e.y, k)) : cg);
           }
         }
       }
@@ -382,12 +383,13 @@ int table_alloc(Context* c, int64_t n_keys, int64_t n_vrows) {
   T.d = c->P.V_dim;
   T.es = c->slot_es;
   T.line = c->slot_line;
+  T.half = c->vrows_half;
   DFX_TRY(table_alloc_entries(&T, cap, c->stream));
   DFX_HIP(hipStreamSynchronize(c->stream));
   c->cap = cap;
   if (T.es) return DFX_OK;  // the Vaux pool came with the slots (line slots: Vaux itself)
   T.vcap = T.d > 0 ? (n_vrows > 0 ? n_vrows : 1) : 0;
-  if (T.d > 0) DFX_HIP(hipMalloc(&T.V, T.vcap * 2 * T.d * sizeof(float)));
+  if (T.d > 0) DFX_HIP(hipMalloc(&T.V, T.vcap * pool_row_bytes(T)));
   return DFX_OK;
 }
 
@@ -432,7 +434,7 @@ static ReservePlan reserve_plan(const Context* c, int64_t n_keys, int64_t n_vrow
     p.bytes += p.cap * (int64_t)(sizeof(Entry) << T.es) +
                (T.es && !T.line ? p.cap * (int64_t)T.d * (int64_t)sizeof(float) : 0);
   p.pool = T.d > 0 && !T.es && n_vrows > T.vcap;  // fat slots: V grows with the slots
-  if (p.pool) p.bytes += n_vrows * 2 * T.d * (int64_t)sizeof(float);
+  if (p.pool) p.bytes += n_vrows * pool_row_bytes(T);
   return p;
 }
 
@@ -450,9 +452,9 @@ int store_reserve(Context* c, int64_t n_keys, int64_t n_vrows) {
     HostCounters h;
     DFX_TRY(read_counters(c, &h));
     float* nV;
-    DFX_HIP(hipMalloc(&nV, n_vrows * 2 * T.d * sizeof(float)));
+    DFX_HIP(hipMalloc(&nV, n_vrows * pool_row_bytes(T)));  // (rows move whole, as bytes)
     if (h.n_vrows) {
-      DFX_HIP(hipMemcpy(nV, T.V, h.n_vrows * 2 * T.d * sizeof(float), hipMemcpyDeviceToDevice));
+      DFX_HIP(hipMemcpy(nV, T.V, h.n_vrows * pool_row_bytes(T), hipMemcpyDeviceToDevice));
     }
     (void)hipFree(T.V);
     T.V = nV;
@@ -655,8 +657,10 @@ __global__ void k_penalty(Table T, int64_t cap, Params P, double* acc) {
     const int vr = ent_at(T, i)->vrow;
     if (vr >= 0) {
       nnz += T.d;
-      const float* V = row_V(T, vr);
-      for (int k = 0; k < T.d; ++k) objv += .5 * P.l2 * V[k] * V[k];  // (sic) l2, :21
+      for (int k = 0; k < T.d; ++k) {
+        const float v = v_get(T, vr, k);
+        objv += .5 * P.l2 * v * v;  // (sic) l2, :21
+      }
     }
   }
   for (int off = 32; off > 0; off >>= 1) {
@@ -738,7 +742,13 @@ static int for_each_entry(Context* c, int64_t s0, int64_t ns, std::vector<float>
     DFX_HIP(hipMemcpy(ent.data(), T.ent + s0, ns * sizeof(Entry), hipMemcpyDeviceToHost));
   if (VV.empty()) {
     VV.resize((size_t)hc.n_vrows * 2 * d);
-    if (!VV.empty()) DFX_HIP(hipMemcpy(VV.data(), T.V, VV.size() * 4, hipMemcpyDeviceToHost));
+    if (!VV.empty() && T.half) {  // half rows, widened exactly: files and dumps hold fp32
+      std::vector<uint16_t> hv(VV.size());
+      DFX_HIP(hipMemcpy(hv.data(), T.V, hv.size() * 2, hipMemcpyDeviceToHost));
+      for (size_t i = 0; i < hv.size(); ++i) VV[i] = f16_widen(hv[i]);
+    } else if (!VV.empty()) {
+      DFX_HIP(hipMemcpy(VV.data(), T.V, VV.size() * 4, hipMemcpyDeviceToHost));
+    }
   }
   for (const Entry& e : ent) {
     if (e.key == kEmptyKey) continue;
@@ -898,7 +908,8 @@ int dfx_store_bytes(dfx_ctx* ctx, int64_t* table_bytes, int64_t* pool_bytes) {
   const Table& T = c->T;
   if (table_bytes) *table_bytes = T.ent ? c->cap * (int64_t)(sizeof(Entry) << T.es) : 0;
   if (pool_bytes)
-    *pool_bytes = !T.V ? 0 : T.vcap * (int64_t)T.d * (int64_t)sizeof(float) * (T.es ? 1 : 2);
+    *pool_bytes = !T.V ? 0 : T.es ? T.vcap * (int64_t)T.d * (int64_t)sizeof(float)
+                                  : T.vcap * pool_row_bytes(T);
   return DFX_OK;
 }
 
@@ -953,7 +964,11 @@ int dfx_store_entry(dfx_ctx* ctx, uint64_t key, float* state, float* V, int* has
     if (e.key == key) {
       state[0] = e.w; state[1] = e.sqrt_g; state[2] = e.z; state[3] = e.fea_cnt;
       *has_v = e.vrow >= 0;
-      if (e.vrow >= 0 && V) {
+      if (e.vrow >= 0 && V && T.half) {  // a half row, widened
+        uint16_t h[128];
+        DFX_HIP(hipMemcpy(h, half_row(T, e.vrow), 4 * T.d, hipMemcpyDeviceToHost));
+        for (int k = 0; k < 2 * T.d; ++k) V[k] = f16_widen(h[k]);
+      } else if (e.vrow >= 0 && V) {
         DFX_HIP(hipMemcpy(V, row_V(T, e.vrow), T.d * 4, hipMemcpyDeviceToHost));
         if (T.line == 2) {  // fp16 Vaux, widened
           uint16_t h[16];
@@ -1082,6 +1097,10 @@ int dfx_store_load_part(dfx_ctx* ctx, const char* path, int rank, int nranks) {
   if (!VV.empty() && T.es) {  // fat slots: k_load copies each row into its key's slot
     DFX_HIP(hipMalloc(&dVV, VV.size() * 4));
     DFX_HIP(hipMemcpy(dVV, VV.data(), VV.size() * 4, hipMemcpyHostToDevice));
+  } else if (!VV.empty() && T.half) {  // the file's fp32 to the nearest fp16 (exact for a file
+    std::vector<uint16_t> hv(VV.size());  // a half table wrote)
+    for (size_t i = 0; i < hv.size(); ++i) hv[i] = (uint16_t)f16_nearest(VV[i]);
+    DFX_HIP(hipMemcpy(half_row(T, hc.n_vrows), hv.data(), hv.size() * 2, hipMemcpyHostToDevice));
   } else if (!VV.empty()) {
     DFX_HIP(hipMemcpy(row_V(T, hc.n_vrows), VV.data(), VV.size() * 4, hipMemcpyHostToDevice));
   }

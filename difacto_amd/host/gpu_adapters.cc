@@ -217,7 +217,7 @@ KWArgs GpuSGDUpdater::Init(const KWArgs& kwargs) {
   // these two were listed, dfx_train's slot_layout= was printed but never reached the context)
   static const std::set<std::string> known = {
       "l1", "l2", "V_l2", "lr", "lr_beta", "V_lr", "V_lr_beta", "V_init_scale", "V_threshold",
-      "V_dim", "l1_shrk", "seed", "max_keys", "max_vrows", "slot_layout", "vaux"};
+      "V_dim", "l1_shrk", "seed", "max_keys", "max_vrows", "slot_layout", "vaux", "vrows"};
   KWArgs mine;
   KWArgs rest = Consume(kwargs, known, &mine);
   ctx_ = std::make_shared<GpuContext>(0, mine);

@@ -1380,6 +1380,13 @@ int main(int argc, char** argv) {
   // the plan; line slots are the single context's (the sharded stores refuse them)
   for (const auto& kv : rest) {
     if (kv.first == "vaux") std::printf("vaux: %s\n", kv.second.c_str());
+    if (kv.first == "vrows") {  // (half rows: the single context's too)
+      std::printf("vrows: %s\n", kv.second.c_str());
+      if (rc == 0 && plan.sharded && kv.second == "f16") {
+        err = "vrows=f16 is the single-GPU context only: a sharded run needs vrows=f32";
+        rc = 1;
+      }
+    }
     if (kv.first != "slot_layout") continue;
     std::printf("slot_layout: %s\n", kv.second.c_str());
     if (rc == 0 && plan.sharded && kv.second == "line") {

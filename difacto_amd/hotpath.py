@@ -322,6 +322,12 @@ class Store:
         check(_lib.lib().dfx_store_bytes(self.ctx.h, ctypes.byref(tb), ctypes.byref(pb)))
         return tb.value, pb.value
 
+    def half_widen_table(self):
+        """-> uint32[65536]: the float32 bits the vrows=f16 kernels widen each fp16 pattern to"""
+        out = np.zeros(65536, np.uint32)
+        check(_lib.lib().dfx_half_widen_table(self.ctx.h, out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
     def probe_stats(self):
         """-> (mean probe distance, longest probe distance, table capacity)"""
         m, mx, cap = ctypes.c_double(0), ctypes.c_int64(0), ctypes.c_int64(0)

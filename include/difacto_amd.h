@@ -90,7 +90,17 @@ typedef struct dfx_progress {
  * accumulators Vaux stored as fp16 so that a V_dim 16 key fits one 128-byte line, rounded
  * stochastically by a hash of each update's own operands (csrc/vaux16.h): an opt-in approximation
  * of the reference's AdaGrad state, NOT its arithmetic, deterministic and exact against its own
- * CPU restatement; model files hold fp32 Vaux, narrowed to the nearest fp16 on load); the
+ * CPU restatement; model files hold fp32 Vaux, narrowed to the nearest fp16 on load);
+ * vrows=f32|f16 (f16: V_dim 32 or 64 with loss=fm and slot_layout=auto or split, without
+ * vaux=f16, else DFX_ERR_ARG — the split layout's pool rows stored as [V: d fp16 | Vaux: d fp16],
+ * half the pool and half the 128-byte lines per key; every read widens exactly, the arithmetic is
+ * fp32, and each Update's two stores round stochastically by a hash of the update's own operands
+ * (csrc/vhalf.h, csrc/vaux16.h), InitV's draw to the nearest fp16: an opt-in approximation of the
+ * reference, NOT its arithmetic, deterministic and exact against its own CPU restatement; kernels
+ * of its own for the fused step (csrc/fm_half.hip); the single-GPU context only: dfx_dist_* and
+ * dfx_split_* calls return DFX_ERR_ARG; model files hold fp32, narrowed to the nearest fp16 on
+ * load, by the host loop: dfx_store_save_dev, dfx_store_dump_dev and dfx_store_load_dev return
+ * DFX_ERR_ARG on such a context); the
  * sharded store's push_agg=sum|ranks and hash=ordered|mixed; and execution choices that do
  * not change results (A/B switches, measured in DESIGN.md): fwd_probe, xvp_row, bwd_lds,
  * sort_pack, sort_items, sort_lookback, auc_sort=radix|merge|bucket|wbucket, fat_fwd, fat_bwd,
@@ -701,6 +711,9 @@ int dfx_store_stats(dfx_ctx* ctx, int64_t* n_keys, int64_t* n_vrows, double* new
 /* device bytes of the model: the table's slots, and the V pool beside them (the split layout's
  * [V | Vaux] rows, fat slots' Vaux rows; 0 with slot_layout=line, which has none) */
 int dfx_store_bytes(dfx_ctx* ctx, int64_t* table_bytes, int64_t* pool_bytes);
+/* (a test hook) the float32 bits the vrows=f16 kernels widen each of the 65536 fp16 bit patterns
+ * to, by one launch of their own widening, into out_host[65536] */
+int dfx_half_widen_table(dfx_ctx* ctx, uint32_t* out_host);
 /* table health: mean and longest distance of a stored key from its home slot; capacity in
  * slots (a test / diagnostics hook) */
 int dfx_store_probe_stats(dfx_ctx* ctx, double* mean_probe, int64_t* max_probe,
