@@ -43,7 +43,7 @@ all: $(LIB) $(DISTLIB) oracle $(HOSTBIN) $(TRAINBIN) $(READERBIN) $(GENBIN) $(CO
   build/gen_libsvm build/locbench \
   build/reshuffle_check build/resample_check build/fmtg_check build/train_options_tests \
   build/train_options_resample_tests build/train_options_adfea_tests build/gen_adfea \
-  build/modeltext_check build/train_options_model_tests
+  build/modeltext_check build/train_options_model_tests build/half_round_check
 
 $(RBENCH): difacto_amd/host/reader.cc tools/reader_bench.cc difacto_amd/host/reader.h $(CITYHDR)
 	@mkdir -p build
@@ -137,6 +137,11 @@ build/fmtg_check: tools/fmtg_check.cc $(CSRC)/fmtg.h $(CSRC)/expf.h
 # test infrastructure: csrc/modeltext.h (the device model dump's lines) against a std::ostream
 build/modeltext_check: tools/modeltext_check.cc $(CSRC)/modeltext.h $(CSRC)/fmtg.h \
   $(CSRC)/revbytes.h $(CSRC)/expf.h
+	@mkdir -p build
+	g++ -std=c++17 -O2 -Wall -ffp-contract=off -o $@ $<
+
+# test infrastructure: csrc/vhalf.h and csrc/vaux16.h (the half rows' roundings) from the host
+build/half_round_check: tests/host/half_round_check.cc $(CSRC)/vhalf.h $(CSRC)/vaux16.h
 	@mkdir -p build
 	g++ -std=c++17 -O2 -Wall -ffp-contract=off -o $@ $<
 

@@ -191,6 +191,7 @@ _SIGS = {
     "dfx_store_probe_stats": (ctypes.c_int, [vp, vp, vp, vp]),
     "dfx_store_bytes": (ctypes.c_int, [vp, vp, vp]),
     "dfx_half_widen_table": (ctypes.c_int, [vp, vp]),
+    "dfx_half_round_table": (ctypes.c_int, [vp, c_i64, vp, vp]),
     "dfx_dist_union": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]),
     "dfx_dist_union_rows": (ctypes.c_int, [vp, vp, vp, ctypes.c_int64, vp, ctypes.c_int,
                                            ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp, vp]),

@@ -396,6 +396,19 @@ __global__ void k_half_widen_table(uint32_t* out) {
   out[h] = f32_bits(f[0]);
 }
 
+// ---- the narrowing functions on the device (dfx_half_round_table) ------------------------------
+// in: n tuples {bits of nv, bits of g, bits of sg, j}; out: n triples {vhalf_round(nv, g, sg, j),
+// vaux16_round(|nv|, g, sg, j), f16_nearest(nv)} — the step kernels' own inline functions
+__global__ void k_half_round_table(const uint32_t* in, uint32_t* out, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float nv = bits_f32(in[4 * i]), g = bits_f32(in[4 * i + 1]), sg = bits_f32(in[4 * i + 2]);
+  const int j = (int)in[4 * i + 3];
+  out[3 * i] = vhalf_round(nv, g, sg, j);
+  out[3 * i + 1] = vaux16_round(bits_f32(in[4 * i] & 0x7FFFFFFFu), g, sg, j);
+  out[3 * i + 2] = f16_nearest(nv);
+}
+
 }  // namespace dfx
 
 using namespace dfx;
@@ -409,6 +422,23 @@ extern "C" int dfx_half_widen_table(dfx_ctx* ctx, uint32_t* out_host) {
   DFX_HIP(hipGetLastError());
   DFX_HIP(hipMemcpyAsync(out_host, c->ws.rowtmp.p, 65536 * sizeof(uint32_t), hipMemcpyDeviceToHost,
                          c->stream));
+  DFX_HIP(hipStreamSynchronize(c->stream));
+  return DFX_OK;
+}
+
+extern "C" int dfx_half_round_table(dfx_ctx* ctx, int64_t n, const uint32_t* in_host,
+                                    uint32_t* out_host) {
+  DFX_CHECK_ARG(ctx && in_host && out_host && n > 0 && n <= (1 << 24), "bad argument");
+  Context* c = &ctx->c;
+  const size_t in_bytes = (size_t)n * 16, out_bytes = (size_t)n * 12;
+  DFX_TRY(c->ws.rowtmp.ensure(in_bytes + out_bytes));
+  uint32_t* in = c->ws.rowtmp.as<uint32_t>();
+  uint32_t* out = in + 4 * n;
+  DFX_HIP(hipMemcpyAsync(in, in_host, in_bytes, hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(k_half_round_table, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
+                     in, out, n);
+  DFX_HIP(hipGetLastError());
+  DFX_HIP(hipMemcpyAsync(out_host, out, out_bytes, hipMemcpyDeviceToHost, c->stream));
   DFX_HIP(hipStreamSynchronize(c->stream));
   return DFX_OK;
 }

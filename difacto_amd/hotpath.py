@@ -328,6 +328,17 @@ class Store:
         check(_lib.lib().dfx_half_widen_table(self.ctx.h, out.ctypes.data_as(ctypes.c_void_p)))
         return out
 
+    def half_round_table(self, tuples):
+        """tuples uint32[n, 4] = (bits of nv, bits of g, bits of sg, j) -> uint32[n, 3]: the fp16
+        bits of vhalf_round(nv, g, sg, j), vaux16_round(|nv|, g, sg, j) and f16_nearest(nv) as the
+        vrows=f16 kernels compile them, one launch"""
+        t = np.ascontiguousarray(tuples, np.uint32)
+        assert t.ndim == 2 and t.shape[1] == 4 and len(t) > 0
+        out = np.zeros((len(t), 3), np.uint32)
+        check(_lib.lib().dfx_half_round_table(self.ctx.h, len(t), t.ctypes.data_as(ctypes.c_void_p),
+                                              out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
     def probe_stats(self):
         """-> (mean probe distance, longest probe distance, table capacity)"""
         m, mx, cap = ctypes.c_double(0), ctypes.c_int64(0), ctypes.c_int64(0)

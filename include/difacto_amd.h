@@ -714,6 +714,10 @@ int dfx_store_bytes(dfx_ctx* ctx, int64_t* table_bytes, int64_t* pool_bytes);
 /* (a test hook) the float32 bits the vrows=f16 kernels widen each of the 65536 fp16 bit patterns
  * to, by one launch of their own widening, into out_host[65536] */
 int dfx_half_widen_table(dfx_ctx* ctx, uint32_t* out_host);
+/* (a test hook) the narrowing functions as the vrows=f16 kernels compile them: in_host holds n
+ * tuples {bits of nv, bits of g, bits of sg, j}; out_host[3 n] gets, per tuple, vhalf_round(nv, g,
+ * sg, j), vaux16_round(|nv|, g, sg, j) and f16_nearest(nv) (fp16 bit patterns), by one launch */
+int dfx_half_round_table(dfx_ctx* ctx, int64_t n, const uint32_t* in_host, uint32_t* out_host);
 /* table health: mean and longest distance of a stored key from its home slot; capacity in
  * slots (a test / diagnostics hook) */
 int dfx_store_probe_stats(dfx_ctx* ctx, double* mean_probe, int64_t* max_probe,

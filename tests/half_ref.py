@@ -89,3 +89,5 @@ class Updater(L16.Updater):
             self.rounded_v[1] += int((V < nv).sum())
             self.rounded[0] += int((c > nc).sum())
             self.rounded[1] += int((c < nc).sum())
+        self.rounded[2] += int(((c > 0) & (c < f32(2.0 ** -14))).sum())    # (line16_ref's counts)
+        self.rounded[3] += int((c == f32(65504)).sum())

@@ -100,7 +100,7 @@ _CYCLE = [(None, True), (None, False), (0.0, True), (0.0, False), (None, True), 
           ("huge+", False), ("huge-", True), (0.0, True), (None, False), (None, True)]
 
 
-def plant(d, huge, seed=29):
+def plant(d, huge, seed=29, narrow=None):
     """-> model entries (key, w, sqrt_g, z, V | None, Vaux | None) for edge_ref.write_model, in a
     shuffled order (a file's order is the split layout's pool-row order; slots go by the hash).
 
@@ -109,7 +109,10 @@ def plant(d, huge, seed=29):
     what the two w terms weigh (~1e38) and a wrong V term shows; the sum is past FLT_MAX, which
     Evaluate's float accumulator cannot hold, so the oracle is not consulted there.  not huge: the same plant without |w| > 2^64 and with
     V ~ N(0, 1) / 2 — sums of order 100, where the l1 terms show and the oracle can be asked.
-    Vaux in [0.5, 100), not fp16 numbers: never V's values, and a vaux=f16 slot narrows them."""
+    Vaux in [0.5, 100), not fp16 numbers: never V's values, and a vaux=f16 slot narrows them.
+    narrow: applied to V and Vaux (half_ref.nearest_f16 for a vrows=f16 table, whose load is then
+    exact; not with huge, whose V no fp16 holds)."""
+    assert narrow is None or not huge
     rng = np.random.default_rng(seed + d)
     keys = _private_keys(PLANT_KEYS)[0]
     out = []
@@ -127,6 +130,8 @@ def plant(d, huge, seed=29):
         if has_v and d > 0:
             V = (rng.standard_normal(d) * (2.0 ** 60 if huge else .5)).astype(F)
             C = (rng.random(d) * 99.5 + .5).astype(F)
+            if narrow is not None:
+                V, C = narrow(V), narrow(C)
         out.append((int(k), F(w), sg, z, V, C))
     return [out[i] for i in rng.permutation(len(out))]
 
@@ -177,6 +182,9 @@ LAYOUTS = [
     (12, dict(slot_layout="line"), (2, 1)),
     (16, LINE16, (2, 2)),
 ]
+# half rows (vrows=f16): the split layout's table, pool rows of [V | Vaux] fp16
+HALF = dict(vrows="f16")
+HALF_LAYOUTS = [(32, HALF, (0, 0)), (64, HALF, (0, 0))]
 # what table_alloc can be handed: es 0 (split), fat_es's 1 and 2, line_es's 1 and 2, line16's 2
 EVERY_ES_LINE = {(0, 0), (1, 0), (2, 0), (1, 1), (2, 1), (2, 2)}
 

@@ -11,6 +11,7 @@ from difacto_amd import data as D
 from oracle import oracle as O
 from tests import backward_ref as R
 from tests import edge_ref as E
+from tests import half_ref as HR
 from tests import line16_ref as L16
 from tests import penalty_ref as PR
 from tests.test_gpu_line_slots import LAZY, H, _assert_store, _batch, _bits, _steps  # noqa: F401
@@ -22,6 +23,7 @@ LAYOUT_IDS = range(len(PR.LAYOUTS))
 TRAINED = [("split", 8, dict(slot_layout="split"), O.Updater), ("fat", 8, {}, O.Updater),
            ("line", 8, dict(slot_layout="line"), O.Updater), ("line16", 16, PR.LINE16, L16.Updater)]
 REBUILT = [("split", 5, {}, O.Updater)] + TRAINED[1:]
+HALF_TRAINED = [("half%d" % d, d, kw, HR.Updater) for d, kw, _ in PR.HALF_LAYOUTS]
 
 
 def _check(st, entries, l1, l2, d, tag):
@@ -82,8 +84,35 @@ def test_planted_model(H, tmp_path, i, dev):
         c.close()
 
 
+@pytest.mark.parametrize("d,kw,want", PR.HALF_LAYOUTS, ids=["half32", "half64"])
+def test_planted_model_half(H, tmp_path, d, kw, want):
+    """the plain planted model narrowed to fp16 in a vrows=f16 table (k_penalty reads the V half of
+    a pool row through v_get): the load is exact, V and Vaux bit for bit (the host loader: the
+    device loader refuses a half table)"""
+    planted = PR.plant(d, False, narrow=HR.nearest_f16)
+    path = str(tmp_path / "m")
+    E.write_model(path, d, planted)
+    c = H.Context(0, max_keys=1 << 10, V_dim=d, l1=PR.L1, l2=PR.L2, V_l2=PR.V_L2, **kw)
+    st = H.Store(c)
+    _assert_layout(st, d, want)
+    assert st.evaluate() == (0.0, 0)
+    st.load(path)
+    assert st.stats()["n_keys"] == len(planted)
+    kinds = _check(st, PR.model_entries(planted), PR.L1, PR.L2, d, "half V_dim %d" % d)
+    for name in PR.KINDS:
+        assert (kinds[name] > 0) == (name != "huge"), (name, kinds)
+    for key, w, sg, z, V, C in planted[::5]:
+        got = st.entry(key)
+        assert np.array_equal(_bits(got[0][:3]), _bits([w, sg, z])), key
+        assert (got[1] is None) == (V is None), key
+        if V is not None:
+            assert np.array_equal(_bits(got[1]), _bits(np.concatenate([V, C]))), key
+    c.close()
+
+
 # ---------------------------------------------------------------- b. trained models
-@pytest.mark.parametrize("name,d,kw,updater", TRAINED, ids=[t[0] for t in TRAINED])
+@pytest.mark.parametrize("name,d,kw,updater", TRAINED + HALF_TRAINED,
+                         ids=[t[0] for t in TRAINED + HALF_TRAINED])
 def test_trained_model(H, name, d, kw, updater):
     """a count push and two training steps, the labels flipped in between (test_lazy_v_bit_equal's
     recipe with l2 > 0): the store is the updater's bit for bit, then its penalty the yardstick's

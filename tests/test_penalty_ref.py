@@ -7,6 +7,7 @@ import pytest
 from oracle import oracle as O
 from tests import backward_ref as R
 from tests import edge_ref as E
+from tests import half_ref as HR
 from tests import line16_ref as L16
 from tests import penalty_ref as PR
 
@@ -114,6 +115,39 @@ def test_plant_discriminates(i, huge):
     for name, wrong in PR.variants(planted).items():
         print("  %s: S' %.17g, |S' - S| = %.3g bounds" % (name, wrong, abs(wrong - S) / bound))
         assert abs(wrong - S) > 100 * bound, (name, wrong, S, bound)
+
+
+@pytest.mark.parametrize("d", [32, 64])
+def test_half_plant_discriminates(d):
+    """the plain plant narrowed to fp16 (what a vrows=f16 table holds exactly): every class but
+    huge, V and Vaux all fp16 numbers and still apart, and each wrong kernel — v_get reading the
+    Vaux half among them — more than 100 bounds from S"""
+    assert [(dd, kw) for dd, kw, _ in PR.HALF_LAYOUTS] == [(32, PR.HALF), (64, PR.HALF)]
+    planted = PR.plant(d, False, narrow=HR.nearest_f16)
+    S, nnz, bound, kinds = PR.penalty(PR.model_entries(planted), PR.L1, PR.L2, d)
+    print("half V_dim %d: S %.17g nnz %d bound %.3g %s" % (d, S, nnz, bound, kinds))
+    assert len({k for k, *_ in planted}) == len(planted) == PR.PLANT_KEYS
+    for name in PR.KINDS:
+        assert (kinds[name] > 0) == (name != "huge"), name
+    for k, w, sg, z, V, C in planted:
+        if V is not None:
+            assert np.array_equal(V, HR.nearest_f16(V)) and np.array_equal(C, HR.nearest_f16(C))
+            assert not np.array_equal(V, C) and V.shape == C.shape == (d,)
+    for name, wrong in PR.variants(planted).items():
+        print("  %s: S' %.17g, |S' - S| = %.3g bounds" % (name, wrong, abs(wrong - S) / bound))
+        assert abs(wrong - S) > 100 * bound, (name, wrong, S, bound)
+
+
+@pytest.mark.parametrize("d", [32, 64])
+def test_lazy_recipe_on_half_rows(d):
+    """what test_gpu_penalty's trained half-row cases assert about the yardstick's state"""
+    blk, neg, uniq = PR.lazy_batches()
+    up = HR.Updater(**dict(PR.LAZY_CFG, V_dim=d))
+    for step in range(3):
+        R.fused_step(up, (blk, neg)[step % 2], push_cnt=(step == 0))
+    hidden, bare = PR.hidden_and_bare(up, uniq)
+    kinds = PR.penalty(PR.entries_of(up, uniq), PR.LAZY_CFG["l1"], PR.LAZY_CFG["l2"], d)[3]
+    assert hidden > 0 and bare > 0 and kinds["zero_v"] >= hidden and kinds["w_v"] > 0, kinds
 
 
 def test_layouts_cover_every_es_and_line():
