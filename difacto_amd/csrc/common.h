@@ -228,7 +228,8 @@ struct Table {
   // line == 2 (kwarg vaux=f16, d = 16 only): Vaux is d fp16 — [Entry 32 B | V 64 B | Vaux 32 B],
   // 128 bytes; stored through vaux16_round (vaux16.h), read back widened
   int line;
-  // half rows (kwarg vrows=f16, d = 32 / 64, the split layout only): the pool holds vcap rows of
+  // half rows (kwarg vrows=f16 at d = 32 / 64, vrows=f16wide at d = 128; the split layout only):
+  // the pool holds vcap rows of
   // 4 d bytes, V as d fp16 bit patterns and Vaux as d more (vhalf.h); vrow and row allocation
   // are the split layout's.  Last, so that the fields above stay where they were
   int half;

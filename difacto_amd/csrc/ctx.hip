@@ -94,6 +94,13 @@ struct Kw {
   // [V | Vaux] rows stored as fp16, rounded by vhalf_round / vaux16_round (vhalf.h) — an opt-in
   // approximation of the reference, not its arithmetic; kernels of their own (fm_half.hip)
   int vrows16 = 0;
+  // vrows=f16wide (V_dim 128, loss=fm, slot_layout=auto|split, bwd_two_pass=1): the same rows at
+  // the wide shape, 512 bytes — four adjacent 128-byte lines where fp32 rows take eight — with the
+  // same reads, arithmetic and roundings, and so the same opt-in approximation of the reference,
+  // not its arithmetic.  A value of its own, not vrows=f16 at V_dim 128, because the step is not
+  // the narrow one widened: the forward spreads a row's lookups over its 16 lanes and the
+  // backward is the wide step's two passes, pass W as it is and a pass V of its own (fm_half.hip)
+  int vrows16w = 0;
   int fat_fwd = 1;  // fat_fwd=0: with fat slots, the split forward walk (A/B of the one-trip read)
   // diag=noauc|noloc|noauc_noloc: MEASUREMENT ONLY (the headroom of the side lanes): no AUC
   // lane, or each Localizer parity run once and its output reused (results are then wrong
@@ -223,9 +230,12 @@ static int parse_kwargs(const char* kwargs, Kw* kw) {
       else { set_error("unknown vaux: " + v + " (f32|f16)"); return DFX_ERR_ARG; }
     }
     else if (k == "vrows") {
-      if (v == "f32") kw->vrows16 = 0;
-      else if (v == "f16") kw->vrows16 = 1;
-      else { set_error("unknown vrows: " + v + " (f32|f16)"); return DFX_ERR_ARG; }
+      if (v != "f32" && v != "f16" && v != "f16wide") {
+        set_error("unknown vrows: " + v + " (f32|f16|f16wide)");
+        return DFX_ERR_ARG;
+      }
+      kw->vrows16 = v == "f16";
+      kw->vrows16w = v == "f16wide";
     }
     else if (k == "auc_sort") {
       if (v == "radix") kw->auc_sort = 1;
@@ -273,6 +283,12 @@ static int parse_kwargs(const char* kwargs, Kw* kw) {
     set_error("vrows=f16 needs V_dim=32 or 64, loss=fm and slot_layout=auto or split, without "
               "vaux=f16 (fp16 [V | Vaux] rows live in the split layout's pool; V_dim 128 is not "
               "built)");
+    return DFX_ERR_ARG;
+  }
+  if (kw->vrows16w && !(kw->loss_fm && kw->P.V_dim == 128 && kw->slot_layout <= 0 && !kw->vaux16 &&
+                        kw->bwd_two_pass != 0)) {
+    set_error("vrows=f16wide needs V_dim=128, loss=fm and slot_layout=auto or split, without "
+              "vaux=f16 and with bwd_two_pass=1 (V_dim 32 and 64 have vrows=f16)");
     return DFX_ERR_ARG;
   }
   if (kw->vaux16 && (kw->slot_layout != 2 || line_es(kw->P.V_dim, true) == 0)) {
@@ -374,7 +390,7 @@ int dfx_ctx_create(int device, const char* kwargs, dfx_ctx** out) {
   c->auc_sort = kw.auc_sort;
   c->slot_line = kw.slot_layout == 2 ? 1 + kw.vaux16 : 0;
   c->slot_es = c->slot_line ? line_es(c->P.V_dim, kw.vaux16 != 0) : kw.slot_layout == 0 ? 0 : fat_es(c->P.V_dim);
-  c->vrows_half = kw.vrows16;
+  c->vrows_half = kw.vrows16 | kw.vrows16w;
   c->fat_fwd = kw.fat_fwd;
   c->nt_mask = kw.nt;
   c->bwd_two_pass = kw.bwd_two_pass;

@@ -1115,6 +1115,9 @@ __global__ __launch_bounds__(kFmNT) void k_fm_bwd(BwdArgs a) {
 // (C5 65.7 -> 92.3 M ex/s): the default at >= 32 lanes per key (V_dim >= 128).
 constexpr int kBwdWNT = 256;
 
+// SG (a half table, vrows=f16wide: fm_half.hip's pass V): the entry's new sqrt_g goes beside the
+// list (bwd_list_sg), for the roundings of pass V; the pass touches no pool row either way
+template <bool SG = false>
 __global__ __launch_bounds__(kBwdWNT) void k_fm_bwd_w(BwdArgs a) {
   __shared__ int red[kBwdWNT / kWave], redn[kBwdWNT / kWave], redi[kBwdWNT / kWave];
   __shared__ unsigned redl[kBwdWNT / kWave], redo[kBwdWNT / kWave];
@@ -1132,6 +1135,7 @@ __global__ __launch_bounds__(kBwdWNT) void k_fm_bwd_w(BwdArgs a) {
     const int64_t u = rd * stride + (int64_t)blockIdx.x * kBwdWNT + threadIdx.x;
     bool listed = false;
     uint4 item = make_uint4(0u, 0u, 0u, 0u);
+    float item_sg = 0.f;
     if (u < nseg) {
       const uint32_t s0 = a.segstart[u], s1 = a.segstart[u + 1];
       const uint32_t len = s1 - s0;
@@ -1245,6 +1249,7 @@ __global__ __launch_bounds__(kBwdWNT) void k_fm_bwd_w(BwdArgs a) {
         // V starts on the key's walk without reading segstart / choff again
         const uint32_t first = (a.choff && len > (uint32_t)kChunkOcc) ? a.choff[u] : s0;
         item = make_uint4(first, (uint32_t)vq, __float_as_uint(xxp), len);
+        item_sg = e.y;
         nlive += 1u;
         nlocc += len;
       }
@@ -1265,7 +1270,11 @@ __global__ __launch_bounds__(kBwdWNT) void k_fm_bwd_w(BwdArgs a) {
       wbase = t ? atomicAdd(a.vcount, t) : 0u;
     }
     __syncthreads();
-    if (listed) a.vlist[wbase + wcnt[wv] + (uint32_t)__popcll(m & lanemask_lt())] = item;
+    if (listed) {
+      const uint32_t at = wbase + wcnt[wv] + (uint32_t)__popcll(m & lanemask_lt());
+      a.vlist[at] = item;
+      if constexpr (SG) bwd_list_sg(a)[at] = item_sg;
+    }
     __syncthreads();
   }
   for (int off = 32; off > 0; off >>= 1) {
@@ -1737,7 +1746,9 @@ bool bwd_two_pass(int d) {
 int launch_bwd_fused(const BwdArgs& a, int64_t nseg_bound, hipStream_t st, long lds) {
   DFX_TRY(check_row_p(a));
   if (a.T.line) return launch_bwd_line(a, nseg_bound, st, lds, kBwdLdsCapFused);
-  if (a.T.half) return launch_bwd_half(a, nseg_bound, st, lds, kBwdLdsCapFused);
+  // half rows: one pass at V_dim 32 / 64; at 128 (vrows=f16wide) pass W below, then their pass V
+  if (a.T.half && !(a.vlist && a.d == 128))
+    return launch_bwd_half(a, nseg_bound, st, lds, kBwdLdsCapFused);
   if (!a.vlist) return launch_bwd<true>(a, nseg_bound, st, true, lds);
   if (nseg_bound <= 0) return DFX_OK;
   int G, CPL;
@@ -1758,7 +1769,11 @@ int launch_bwd_fused(const BwdArgs& a, int64_t nseg_bound, hipStream_t st, long 
   }
   BwdArgs b = a;
   b.nwstat = (int32_t)gw;
-  hipLaunchKernelGGL(k_fm_bwd_w, dim3((unsigned)gw), dim3(kBwdWNT), 0, st, b);
+  if (a.T.half) {
+    hipLaunchKernelGGL(k_fm_bwd_w<true>, dim3((unsigned)gw), dim3(kBwdWNT), 0, st, b);
+    return launch_bwd_half_v(b, nseg_bound, st, lds_bytes);
+  }
+  hipLaunchKernelGGL(k_fm_bwd_w<false>, dim3((unsigned)gw), dim3(kBwdWNT), 0, st, b);
   const int64_t epb = kFmNT / G;
   // pass V: enough blocks that a group takes about one listed key (blocks past the list exit
   // at once) — the list's keys differ widely in walk length, and a resident grid's stride
@@ -1777,7 +1792,9 @@ int bwd_two_pass_reserve(Context* c, Workspace& ws, int64_t nseg_bound, BwdArgs*
   g->vcount = nullptr;
   if (c->bwd_two_pass == 0 || !bwd_two_pass(c->P.V_dim) || nseg_bound <= 0) return DFX_OK;
   const int64_t nw = bwd_fused_blocks(c->P.V_dim, nseg_bound, true, 0);
-  DFX_TRY(ws.vlist.ensure((size_t)(nseg_bound + 1 + nw) * sizeof(uint4)));
+  // (a half table: and a float per listed key behind the block counts, bwd_list_sg)
+  DFX_TRY(ws.vlist.ensure((size_t)(nseg_bound + 1 + nw) * sizeof(uint4) +
+                          (c->T.half ? (size_t)nseg_bound * sizeof(float) : 0)));
   g->vlist = ws.vlist.as<uint4>();
   g->vcount = reinterpret_cast<uint32_t*>(g->vlist + nseg_bound);
   g->wstat = reinterpret_cast<int4*>(g->vlist + nseg_bound + 1);

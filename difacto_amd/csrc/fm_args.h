@@ -189,6 +189,15 @@ int launch_bwd_half(const BwdArgs& a, int64_t nseg_bound, hipStream_t st, long l
                     size_t lds_default);
 int launch_fwd_half(const FwdArgs& a, hipStream_t st, int* nblk);
 int64_t bwd_half_blocks(int d, int64_t nseg_bound);
+// ... at V_dim 128 (kwarg vrows=f16wide) the two-pass backward's pass V over pass W's list, after
+// k_fm_bwd_w<true> on the same arguments (launch_bwd_fused)
+int launch_bwd_half_v(const BwdArgs& a, int64_t nseg_bound, hipStream_t st, size_t lds_bytes);
+// A half table's pass V rounds with the entry's new sqrt_g, which the list's items have no word
+// for: pass W leaves it per listed key, at the item's index, in floats behind its block counts
+// (bwd_two_pass_reserve sizes the buffer for them when the table is half)
+__host__ __device__ inline float* bwd_list_sg(const BwdArgs& a) {
+  return reinterpret_cast<float*>(a.wstat + a.nwstat);
+}
 // the chunk partials of long segments (before the backward reads them)
 int launch_bwd_chunks(const BwdArgs& a, int64_t chunk_bound, hipStream_t st, bool aligned);
 

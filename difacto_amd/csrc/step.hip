@@ -417,8 +417,10 @@ int train_step(Context* c, const dfx_batch* b, int job_type, int push_cnt, uint6
     // (diagnostic, dfx_prof_enable_marks bit 9) the live-V key / occurrence counts
     const bool count_live = c->prof_n < c->prof_max && (c->prof_mask >> 9 & 1u);
     DFX_TRY(bwd_two_pass_reserve(c, ws, nnz, &g));
-    const int64_t nbb = c->T.half ? bwd_half_blocks(d, nnz)
-                                  : bwd_fused_blocks(d, nnz, g.vlist != nullptr, g.cpl | g.cpl_from << 8);
+    // (half rows at V_dim 128, vrows=f16wide, run pass W: its blocks count)
+    const int64_t nbb = c->T.half && !g.vlist
+                            ? bwd_half_blocks(d, nnz)
+                            : bwd_fused_blocks(d, nnz, g.vlist != nullptr, g.cpl | g.cpl_from << 8);
     if (count_live) {
       DFX_TRY(ws.live.ensure((size_t)nbb * sizeof(uint2)));
       g.live_part = ws.live.as<uint2>();

@@ -965,7 +965,7 @@ int dfx_store_entry(dfx_ctx* ctx, uint64_t key, float* state, float* V, int* has
       state[0] = e.w; state[1] = e.sqrt_g; state[2] = e.z; state[3] = e.fea_cnt;
       *has_v = e.vrow >= 0;
       if (e.vrow >= 0 && V && T.half) {  // a half row, widened
-        uint16_t h[128];
+        uint16_t h[256];  // (d <= 128)
         DFX_HIP(hipMemcpy(h, half_row(T, e.vrow), 4 * T.d, hipMemcpyDeviceToHost));
         for (int k = 0; k < 2 * T.d; ++k) V[k] = f16_widen(h[k]);
       } else if (e.vrow >= 0 && V) {

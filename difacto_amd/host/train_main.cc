@@ -1382,7 +1382,7 @@ int main(int argc, char** argv) {
     if (kv.first == "vaux") std::printf("vaux: %s\n", kv.second.c_str());
     if (kv.first == "vrows") {  // (half rows: the single context's too)
       std::printf("vrows: %s\n", kv.second.c_str());
-      if (rc == 0 && plan.sharded && kv.second == "f16") {
+      if (rc == 0 && plan.sharded && (kv.second == "f16" || kv.second == "f16wide")) {
         err = "vrows=f16 is the single-GPU context only: a sharded run needs vrows=f32";
         rc = 1;
       }

@@ -91,7 +91,15 @@ typedef struct dfx_progress {
  * stochastically by a hash of each update's own operands (csrc/vaux16.h): an opt-in approximation
  * of the reference's AdaGrad state, NOT its arithmetic, deterministic and exact against its own
  * CPU restatement; model files hold fp32 Vaux, narrowed to the nearest fp16 on load);
- * vrows=f32|f16 (f16: V_dim 32 or 64 with loss=fm and slot_layout=auto or split, without
+ * vrows=f32|f16|f16wide (f16wide: what f16 is, at V_dim 128 — with loss=fm, slot_layout=auto or
+ * split and bwd_two_pass=1, without vaux=f16, else DFX_ERR_ARG: the pool row is [V: 128 fp16 |
+ * Vaux: 128 fp16], 512 bytes, four adjacent 128-byte lines where fp32 rows take eight; the same
+ * exact widening, fp32 arithmetic, stochastic rounds (j the coordinate's index in the row) and
+ * InitV draw, so the same opt-in approximation of the reference, NOT its arithmetic, deterministic
+ * and exact against its own CPU restatement; a value of its own because the step is the wide
+ * one's — a forward that spreads a row's lookups over 16 lanes, the two-pass backward with a pass
+ * V over half rows (csrc/fm_half.hip) — and with f16's limits: one GPU, fp32 model files by the
+ * host loops; f16: V_dim 32 or 64 with loss=fm and slot_layout=auto or split, without
  * vaux=f16, else DFX_ERR_ARG — the split layout's pool rows stored as [V: d fp16 | Vaux: d fp16],
  * half the pool and half the 128-byte lines per key; every read widens exactly, the arithmetic is
  * fp32, and each Update's two stores round stochastically by a hash of the update's own operands
