@@ -226,7 +226,10 @@ struct Table {
   // [Entry 32 B | V 4d B | Vaux 4d B | pad] in 64 bytes (d = 4) or 128 (d = 8, 12), a key's whole
   // state in one 128-byte line; es as with fat slots (d = 8: 2, not 1), vrow = slot, no pool.
   // line == 2 (kwarg vaux=f16, d = 16 only): Vaux is d fp16 — [Entry 32 B | V 64 B | Vaux 32 B],
-  // 128 bytes; stored through vaux16_round (vaux16.h), read back widened
+  // 128 bytes; stored through vaux16_round (vaux16.h), read back widened.
+  // line == 3 (kwargs slot_layout=line vrows=f16, d = 24 only): V is fp16 too — [Entry 32 B | V: 24
+  // fp16 | Vaux: 24 fp16], 128 bytes with no pad, 16-byte pieces 0-1 the entry, 2-4 V, 5-7 Vaux;
+  // stored through vhalf_round / vaux16_round (vhalf.h), read back widened
   int line;
   // half rows (kwarg vrows=f16 at d = 32 / 64, vrows=f16wide at d = 128; the split layout only):
   // the pool holds vcap rows of
@@ -249,17 +252,23 @@ __host__ __device__ inline float* row_C_pool(const Table& t, int64_t vr) {
 __host__ __device__ inline uint16_t* half_row(const Table& t, int64_t vr) {
   return reinterpret_cast<uint16_t*>(t.V) + vr * 2 * (int64_t)t.d;
 }
+// The halves of slot vr of a line table at d = 24 (Table::line == 3): V's 24 fp16, then Vaux's
+__host__ __device__ inline uint16_t* line24_row(const Table& t, int64_t vr) {
+  return reinterpret_cast<uint16_t*>(row_V(t, vr));
+}
 // Vaux coordinate k of V row vr in any layout, read and written: what every caller that can meet
 // a line table goes through.  With fp16 Vaux the read widens exactly and the write narrows to
 // the nearest fp16 — exact for what such a slot held (a rebuild, a load of its own file) and for
 // InitV's 0; an Update narrows by vaux16_round and hands the result here
 __host__ __device__ inline float vaux_get(const Table& t, int64_t vr, int k) {
   if (t.half) return f16_widen(half_row(t, vr)[t.d + k]);
+  if (t.line == 3) return f16_widen(line24_row(t, vr)[t.d + k]);
   if (t.line == 2) return f16_widen(reinterpret_cast<const uint16_t*>(row_V(t, vr) + t.d)[k]);
   return (t.line ? row_V(t, vr) + t.d : row_C_pool(t, vr))[k];
 }
 __host__ __device__ inline void vaux_put(const Table& t, int64_t vr, int k, float c) {
   if (t.half) half_row(t, vr)[t.d + k] = (uint16_t)f16_nearest(c);
+  else if (t.line == 3) line24_row(t, vr)[t.d + k] = (uint16_t)f16_nearest(c);
   else if (t.line == 2) reinterpret_cast<uint16_t*>(row_V(t, vr) + t.d)[k] = (uint16_t)f16_nearest(c);
   else (t.line ? row_V(t, vr) + t.d : row_C_pool(t, vr))[k] = c;
 }
@@ -272,10 +281,12 @@ __host__ __device__ inline int64_t pool_row_bytes(const Table& t) {
 // exact for what such a row held and for a file it wrote; an Update narrows by vhalf_round /
 // vaux16_round and hands the widened result here
 __host__ __device__ inline float v_get(const Table& t, int64_t vr, int k) {
+  if (t.line == 3) return f16_widen(line24_row(t, vr)[k]);
   return t.half ? f16_widen(half_row(t, vr)[k]) : row_V(t, vr)[k];
 }
 __host__ __device__ inline void v_put(const Table& t, int64_t vr, int k, float v) {
   if (t.half) half_row(t, vr)[k] = (uint16_t)f16_nearest(v);
+  else if (t.line == 3) line24_row(t, vr)[k] = (uint16_t)f16_nearest(v);
   else row_V(t, vr)[k] = v;
 }
 // the V rows the table has room for: the pool's, or with line slots one per slot
@@ -298,8 +309,10 @@ __host__ __device__ inline int fat_es(int d) {
 
 // line slot stride for V_dim d (0: d has no line layout): the entry, V and Vaux in 64 or 128
 // bytes — d = 4: 64; d = 8 (96 bytes of state, which would straddle lines at that stride) and
-// d = 12: 128; d = 16 only with fp16 Vaux (h16; 32 + 64 + 32 bytes): 128
-__host__ __device__ inline int line_es(int d, bool h16 = false) {
+// d = 12: 128; d = 16 only with fp16 Vaux (h16; 32 + 64 + 32 bytes): 128; d = 24 only with fp16 V
+// and Vaux (h24; 32 + 48 + 48 bytes): 128
+__host__ __device__ inline int line_es(int d, bool h16 = false, bool h24 = false) {
+  if (h24) return d == 24 ? 2 : 0;
   if (h16) return d == 16 ? 2 : 0;
   return d == 4 ? 1 : (d == 8 || d == 12) ? 2 : 0;
 }

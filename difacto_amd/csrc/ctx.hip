@@ -92,7 +92,9 @@ struct Kw {
   int vaux16 = 0;
   // vrows=f16 (V_dim 32 or 64, loss=fm, slot_layout=auto|split: the split layout): the pool's
   // [V | Vaux] rows stored as fp16, rounded by vhalf_round / vaux16_round (vhalf.h) — an opt-in
-  // approximation of the reference, not its arithmetic; kernels of their own (fm_half.hip)
+  // approximation of the reference, not its arithmetic; kernels of their own (fm_half.hip).
+  // With slot_layout=line at V_dim 24 (the one line shape): the same halves inside the key's
+  // 128-byte slot, no pool (Table::line == 3, fm_line.hip)
   int vrows16 = 0;
   // vrows=f16wide (V_dim 128, loss=fm, slot_layout=auto|split, bwd_two_pass=1): the same rows at
   // the wide shape, 512 bytes — four adjacent 128-byte lines where fp32 rows take eight — with the
@@ -278,11 +280,14 @@ static int parse_kwargs(const char* kwargs, Kw* kw) {
     set_error("slot_layout=fat needs 4 <= V_dim <= 24 with V_dim % 4 == 0");
     return DFX_ERR_ARG;
   }
-  if (kw->vrows16 && !(kw->loss_fm && (kw->P.V_dim == 32 || kw->P.V_dim == 64) &&
-                       kw->slot_layout <= 0 && !kw->vaux16)) {
+  // (slot_layout=line vrows=f16 at V_dim 24: fp16 V and Vaux inside the key's line, Table::line 3)
+  const bool line24 = kw->vrows16 && kw->loss_fm && kw->P.V_dim == 24 && kw->slot_layout == 2 &&
+                      !kw->vaux16;
+  if (kw->vrows16 && !line24 && !(kw->loss_fm && (kw->P.V_dim == 32 || kw->P.V_dim == 64) &&
+                                  kw->slot_layout <= 0 && !kw->vaux16)) {
     set_error("vrows=f16 needs V_dim=32 or 64, loss=fm and slot_layout=auto or split, without "
               "vaux=f16 (fp16 [V | Vaux] rows live in the split layout's pool; V_dim 128 is not "
-              "built)");
+              "built); V_dim 24 with slot_layout=line is the one line shape");
     return DFX_ERR_ARG;
   }
   if (kw->vrows16w && !(kw->loss_fm && kw->P.V_dim == 128 && kw->slot_layout <= 0 && !kw->vaux16 &&
@@ -296,9 +301,9 @@ static int parse_kwargs(const char* kwargs, Kw* kw) {
               "key fit one 128-byte line; no other layout or V_dim has it)");
     return DFX_ERR_ARG;
   }
-  if (kw->slot_layout == 2 && !kw->vaux16 && line_es(kw->P.V_dim) == 0) {
+  if (kw->slot_layout == 2 && !kw->vaux16 && !line24 && line_es(kw->P.V_dim) == 0) {
     set_error("slot_layout=line needs V_dim 4, 8 or 12 (the entry, V and Vaux in one 128-byte "
-              "line), or V_dim 16 with vaux=f16");
+              "line), or V_dim 16 with vaux=f16, or V_dim 24 with vrows=f16");
     return DFX_ERR_ARG;
   }
   return DFX_OK;
@@ -388,9 +393,12 @@ int dfx_ctx_create(int device, const char* kwargs, dfx_ctx** out) {
   c->dist_sum = kw.dist_sum;
   c->sort_pack = kw.sort_pack;
   c->auc_sort = kw.auc_sort;
-  c->slot_line = kw.slot_layout == 2 ? 1 + kw.vaux16 : 0;
-  c->slot_es = c->slot_line ? line_es(c->P.V_dim, kw.vaux16 != 0) : kw.slot_layout == 0 ? 0 : fat_es(c->P.V_dim);
-  c->vrows_half = kw.vrows16 | kw.vrows16w;
+  // (slot_layout=line vrows=f16, V_dim 24: Table::line 3; Table::half is the split layout's pool)
+  const bool line24 = kw.slot_layout == 2 && kw.vrows16;
+  c->slot_line = kw.slot_layout == 2 ? (line24 ? 3 : 1 + kw.vaux16) : 0;
+  c->slot_es = c->slot_line ? line_es(c->P.V_dim, kw.vaux16 != 0, line24)
+                            : kw.slot_layout == 0 ? 0 : fat_es(c->P.V_dim);
+  c->vrows_half = line24 ? 0 : kw.vrows16 | kw.vrows16w;
   c->fat_fwd = kw.fat_fwd;
   c->nt_mask = kw.nt;
   c->bwd_two_pass = kw.bwd_two_pass;

@@ -595,6 +595,7 @@ int launch_fwd(const FwdArgs& a, hipStream_t st) {
 
 int launch_fwd_fused(const FwdArgs& a, hipStream_t st, int* nblk, bool spread) {
   if (a.T.half) return launch_fwd_half(a, st, nblk);  // half rows: fm_half.hip
+  if (a.T.line == 3) return launch_fwd_line24(a, st, nblk);  // fp16 V in the slot: fm_line.hip
   int G, CPL;
   bool vec;
   lanes_for(a.d, true, &G, &CPL, &vec);

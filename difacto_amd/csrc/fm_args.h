@@ -183,6 +183,10 @@ int launch_bwd_fused(const BwdArgs& a, int64_t nseg_bound, hipStream_t st, long 
 // lds_default: the fused backward's LDS reservation when lds < 0
 int launch_bwd_line(const BwdArgs& a, int64_t nseg_bound, hipStream_t st, long lds,
                     size_t lds_default);
+// ... at V_dim 24 with fp16 V and Vaux in the slot (Table::line == 3) the fused forward of its own
+// (launch_fwd_fused goes there when the table says so) and the blocks its backward launches
+int launch_fwd_line24(const FwdArgs& a, hipStream_t st, int* nblk);
+int64_t bwd_line24_blocks(int64_t nseg_bound);
 // ... and of a half-row table (kwarg vrows=f16, fm_half.hip), with its fused forward (probe
 // mode: a.index) and the blocks its backward launches over nseg_bound keys (BwdArgs::live_part)
 int launch_bwd_half(const BwdArgs& a, int64_t nseg_bound, hipStream_t st, long lds,

@@ -14,33 +14,6 @@
 
 namespace dfx {
 
-typedef uint32_t dfx_u4v __attribute__((ext_vector_type(4)));
-
-// a lane's 16-byte piece of a half row: eight fp16 bit patterns, coordinate k in the low half of
-// word k / 2 for even k
-__device__ __forceinline__ dfx_u4v ldh(const uint16_t* p, bool nt) {
-  const dfx_u4v* q = reinterpret_cast<const dfx_u4v*>(p);
-  return nt ? __builtin_nontemporal_load(q) : *q;
-}
-__device__ __forceinline__ void sth(uint16_t* p, dfx_u4v v, bool nt) {
-  dfx_u4v* q = reinterpret_cast<dfx_u4v*>(p);
-  if (nt) __builtin_nontemporal_store(v, q);
-  else *q = v;
-}
-__device__ __forceinline__ void half8_widen(dfx_u4v p, float (&f)[8]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    f[2 * i] = f16_widen(p[i] & 0xFFFFu);
-    f[2 * i + 1] = f16_widen(p[i] >> 16);
-  }
-}
-__device__ __forceinline__ dfx_u4v half8_pack(const uint32_t (&h)[8]) {
-  dfx_u4v p;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) p[i] = h[2 * i] | (h[2 * i + 1] << 16);
-  return p;
-}
-
 // ---- the fused backward -------------------------------------------------------------------------
 // Two dependent trips per key, as in the split layout (the row's address is the entry's vrow), each
 // issued once by the group:
@@ -359,23 +332,11 @@ __global__ __launch_bounds__(kFmNT, 2) void k_fm_fwd_h(FwdArgs a) {
   }
 }
 
-// a resident grid for kernel K (its groups loop over rows): at most want blocks
-template <typename K>
-static int64_t half_resident_grid(K kern, int64_t want) {
-  int per_cu = 0, dev = 0, cus = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kFmNT, 0) != hipSuccess ||
-      per_cu <= 0 || hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      cus <= 0)
-    return want;
-  return std::min<int64_t>(want, (int64_t)per_cu * cus);
-}
-
 template <int G, bool VALUED>
 static int launch_fwd_half_g(const FwdArgs& a, hipStream_t st, int* nblk) {
   static int64_t resident = 0;  // per kernel
   const int64_t rpb = kFmNT / G, want = (a.B + rpb - 1) / rpb;
-  if (resident <= 0) resident = half_resident_grid(k_fm_fwd_h<G, VALUED>, INT32_MAX);
+  if (resident <= 0) resident = resident_grid_for(k_fm_fwd_h<G, VALUED>, INT32_MAX);
   *nblk = (int)std::min<int64_t>(want, resident);
   hipLaunchKernelGGL((k_fm_fwd_h<G, VALUED>), dim3((unsigned)*nblk), dim3(kFmNT), 0, st, a);
   DFX_HIP(hipGetLastError());
@@ -521,7 +482,7 @@ template <bool VALUED>
 static int launch_fwd_half_wide(const FwdArgs& a, hipStream_t st, int* nblk) {
   static int64_t resident = 0;  // per kernel
   const int64_t rpb = kFmNT / kHwG, want = (a.B + rpb - 1) / rpb;
-  if (resident <= 0) resident = half_resident_grid(k_fm_fwd_hw<VALUED>, INT32_MAX);
+  if (resident <= 0) resident = resident_grid_for(k_fm_fwd_hw<VALUED>, INT32_MAX);
   *nblk = (int)std::min<int64_t>(want, resident);
   hipLaunchKernelGGL((k_fm_fwd_hw<VALUED>), dim3((unsigned)*nblk), dim3(kFmNT), 0, st, a);
   DFX_HIP(hipGetLastError());

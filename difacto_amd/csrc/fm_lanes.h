@@ -1,6 +1,8 @@
-// Lane helpers of the FM kernels shared by fm.hip and fm_line.hip: a lane's coordinates of a
-// row, and an occurrence's p.
+// Lane helpers of the FM kernels shared by fm.hip, fm_line.hip and fm_half.hip: a lane's
+// coordinates of a row, an occurrence's p, a lane's 16-byte piece of fp16 values.
 #pragma once
+#include <algorithm>
+
 #include "fm_args.h"
 
 namespace dfx {
@@ -54,6 +56,47 @@ __device__ inline void store_coords(float* row, int l, int d, const float (&v)[C
 __device__ inline float row_p(const BwdArgs& a, uint32_t r, int d, int64_t xs) {
   if (a.p && (xs <= d || (4 * d) % 128 == 0)) return a.p[r];
   return a.XVp[(int64_t)r * xs + d];
+}
+
+// ---- 16-byte pieces of fp16 bit patterns (half rows, fm_half.hip; line slots at d = 24,
+// fm_line.hip) -----------------------------------------------------------------------------------
+typedef uint32_t dfx_u4v __attribute__((ext_vector_type(4)));
+
+// a lane's 16-byte piece of a half row: eight fp16 bit patterns, coordinate k in the low half of
+// word k / 2 for even k
+__device__ __forceinline__ dfx_u4v ldh(const uint16_t* p, bool nt) {
+  const dfx_u4v* q = reinterpret_cast<const dfx_u4v*>(p);
+  return nt ? __builtin_nontemporal_load(q) : *q;
+}
+__device__ __forceinline__ void sth(uint16_t* p, dfx_u4v v, bool nt) {
+  dfx_u4v* q = reinterpret_cast<dfx_u4v*>(p);
+  if (nt) __builtin_nontemporal_store(v, q);
+  else *q = v;
+}
+__device__ __forceinline__ void half8_widen(dfx_u4v p, float (&f)[8]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    f[2 * i] = f16_widen(p[i] & 0xFFFFu);
+    f[2 * i + 1] = f16_widen(p[i] >> 16);
+  }
+}
+__device__ __forceinline__ dfx_u4v half8_pack(const uint32_t (&h)[8]) {
+  dfx_u4v p;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) p[i] = h[2 * i] | (h[2 * i + 1] << 16);
+  return p;
+}
+
+// a resident grid for kernel K (its groups loop over rows): at most want blocks
+template <typename K>
+inline int64_t resident_grid_for(K kern, int64_t want) {
+  int per_cu = 0, dev = 0, cus = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kFmNT, 0) != hipSuccess ||
+      per_cu <= 0 || hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+      cus <= 0)
+    return want;
+  return std::min<int64_t>(want, (int64_t)per_cu * cus);
 }
 
 }  // namespace dfx

@@ -39,14 +39,15 @@ static_assert(kIvNT == kFinNT, "the fused InitV's blocks run the step's finalize
 // past the seed (all: its rank over every owner's draws of this Update).  seed and nv0 are the
 // store's as of the kernel's start.  A full pool: kErrPoolFull, no row, 0xFFFFFFFF returned.
 // LINE (here and below; Table::line, 0 / 1 / 2): the table has line slots — Vaux behind V in the slot, a V row per slot
-// and no pool; 3: half rows in the split layout's pool (Table::half).  A template parameter, not a test of Table::line, so that the kernels of the
+// and no pool; 3: half rows in the split layout's pool (Table::half); 4: line slots at d = 24, V and
+// Vaux as fp16 in the slot (Table::line == 3).  A template parameter, not a test of Table::line, so that the kernels of the
 // split and fat layouts are the code they were
 template <int LINE = 0>
 __device__ inline uint32_t initv_place(const Table& T, uint32_t seed, uint64_t nv0, uint32_t own,
                                        uint64_t all, uint32_t slot, int* err, uint32_t* state) {
   *state = lcg_advance(seed, 3ull * (uint64_t)T.d * all);
   const int64_t vr = initv_row(T, nv0, own, slot);
-  if (vr >= ((LINE == 1 || LINE == 2) ? (int64_t)T.mask + 1 : T.vcap)) {
+  if (vr >= ((LINE == 1 || LINE == 2 || LINE == 4) ? (int64_t)T.mask + 1 : T.vcap)) {
     atomicOr(err, kErrPoolFull);
     return 0xFFFFFFFFu;
   }
@@ -66,12 +67,13 @@ __device__ inline void initv_draw(const Table& T, uint32_t n, const uint32_t* st
                                   const uint32_t* vrow, float scale, const uint32_t* A,
                                   const uint32_t* C) {
   const int d = T.d;
-  if constexpr (LINE == 3) {  // half rows (Table::half, d = 32 / 64): the draw to the nearest fp16
+  // half rows (Table::half, d = 32 / 64), or the slot's halves (d = 24): the draw to the nearest fp16
+  if constexpr (LINE == 3 || LINE == 4) {
     for (uint32_t q = threadIdx.x; q < n * (uint32_t)d; q += kIvNT) {
       const uint32_t i = q / (uint32_t)d, j = q - i * (uint32_t)d;
       if (vrow[i] == 0xFFFFFFFFu) continue;
       uint32_t s = A[j] * st[i] + C[j];  // (initv_draw_list's draw)
-      uint16_t* row = half_row(T, vrow[i]);
+      uint16_t* row = LINE == 3 ? half_row(T, vrow[i]) : line24_row(T, vrow[i]);
       row[j] = (uint16_t)f16_nearest(initv_value(rand_r_dev(&s), scale));
       row[d + j] = 0;
     }
@@ -341,7 +343,8 @@ __global__ __launch_bounds__(kIvNT) void k_initv_rank_draw(
   uint32_t none;
   if (!initv_arrive(ticket, 0u, gridDim.x, &none) || threadIdx.x != 0) return;
   if (fcount) *fcount = 0u;
-  initv_advance(ds, T.d, (uint64_t)tot, F, (LINE == 1 || LINE == 2) ? (int64_t)T.mask + 1 : T.vcap);
+  initv_advance(ds, T.d, (uint64_t)tot, F,
+                (LINE == 1 || LINE == 2 || LINE == 4) ? (int64_t)T.mask + 1 : T.vcap);
   if (cap_host) {
     cap_host[0] = ds->n_keys;
     cap_host[1] = ds->n_vrows;
@@ -368,6 +371,10 @@ int initv_rank_draw(Context* c, const Lane& L, const uint32_t* flags, const uint
   const dim3 g((unsigned)std::min<int64_t>(ntiles, kIvrGrid));
   if (c->T.half)
     hipLaunchKernelGGL(k_initv_rank_draw<3>, g, dim3(kIvNT), 0, L.stream, flags, bound, nuniq,
+                       ftotal, L.ws->tiles.as<uint32_t>(), segslot, counts_all, rank, nranks, c->T,
+                       c->P.V_init_scale, c->ds, fcount, &L.ds->ivr_ticket[1], cap_host);
+  else if (c->T.line == 3)
+    hipLaunchKernelGGL(k_initv_rank_draw<4>, g, dim3(kIvNT), 0, L.stream, flags, bound, nuniq,
                        ftotal, L.ws->tiles.as<uint32_t>(), segslot, counts_all, rank, nranks, c->T,
                        c->P.V_init_scale, c->ds, fcount, &L.ds->ivr_ticket[1], cap_host);
   else if (c->T.line == 2)
@@ -398,6 +405,10 @@ int run_initv(Context* c, int64_t n_bound, const uint32_t* flags, const uint32_t
       DFX_HIP(hipMemsetAsync(ws.ivstat.p, 0, ws.ivstat.bytes, c->stream));
     if (c->T.half)
       hipLaunchKernelGGL(k_initv_onepass<3>, dim3((unsigned)ntiles), dim3(kIvNT), 0, c->stream,
+                         flags, slot, c->T, c->P.V_init_scale, c->ds, nds, &c->ds->n_init,
+                         ws.ivstat.as<unsigned long long>(), *fin);
+    else if (c->T.line == 3)
+      hipLaunchKernelGGL(k_initv_onepass<4>, dim3((unsigned)ntiles), dim3(kIvNT), 0, c->stream,
                          flags, slot, c->T, c->P.V_init_scale, c->ds, nds, &c->ds->n_init,
                          ws.ivstat.as<unsigned long long>(), *fin);
     else if (c->T.line == 2)

@@ -287,7 +287,7 @@ struct Context {
   long bwd_lds = -1;  // LDS bytes reserved per fused-backward block (kwarg bwd_lds; -1 default)
   int autogrow = 1;   // grow the table / V pool before a step could overflow them (kwarg)
   int slot_es = 0;    // Table::es of this context's store (kwarg slot_layout)
-  int slot_line = 0;  // Table::line: slot_layout=line (2: with vaux=f16)
+  int slot_line = 0;  // Table::line: slot_layout=line (2: with vaux=f16; 3: vrows=f16 at V_dim 24)
   int vrows_half = 0; // Table::half: kwarg vrows=f16 (the split layout's pool rows as fp16)
   int fat_fwd = 1;    // kwarg fat_fwd
   int fwd_cpl = 8;        // kwarg fwd_cpl: V coordinates per lane of the probe forward

@@ -375,7 +375,7 @@ int mf_write_file(dfx_ctx* ctx, const char* path, bool text, int aux, int rev,
   DFX_CHECK_ARG(ctx && path, "null argument");
   DFX_CHECK_ARG(chunk_slots >= 0, "model file: chunk_slots < 0");
   Context* c = &ctx->c;
-  DFX_CHECK_ARG(!c->vrows_half, "vrows=f16: the device model writers read fp32 pool rows; use the "
+  DFX_CHECK_ARG(!c->vrows_half && c->slot_line != 3, "vrows=f16: the device model writers read fp32 pool rows; use the "
                             "host writers (dfx_store_save / dfx_store_dump, model_write=host)");
   DFX_HIP(hipSetDevice(c->device));
   aux = aux ? 1 : 0;

@@ -327,7 +327,7 @@ int ml_load(dfx_ctx* ctx, const char* path, int rank, int nranks, int64_t tile_d
                                      tile_dwords % 16 == 0),
                 "store_load_dev: tile_dwords must be 0 or a multiple of 16 in [32, 8192]");
   Context* c = &ctx->c;
-  DFX_CHECK_ARG(!c->vrows_half, "vrows=f16: the device model loader writes fp32 pool rows; use the "
+  DFX_CHECK_ARG(!c->vrows_half && c->slot_line != 3, "vrows=f16: the device model loader writes fp32 pool rows; use the "
                             "host loader (dfx_store_load, model_read=host)");
   DFX_HIP(hipSetDevice(c->device));
   if (stats) std::fill(stats, stats + 6, (int64_t)0);

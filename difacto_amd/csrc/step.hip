@@ -418,7 +418,9 @@ int train_step(Context* c, const dfx_batch* b, int job_type, int push_cnt, uint6
     const bool count_live = c->prof_n < c->prof_max && (c->prof_mask >> 9 & 1u);
     DFX_TRY(bwd_two_pass_reserve(c, ws, nnz, &g));
     // (half rows at V_dim 128, vrows=f16wide, run pass W: its blocks count)
-    const int64_t nbb = c->T.half && !g.vlist
+    // (line slots at V_dim 24: four lanes a key, not bwd_lanes' eight)
+    const int64_t nbb = c->T.line == 3 ? bwd_line24_blocks(nnz)
+                        : c->T.half && !g.vlist
                             ? bwd_half_blocks(d, nnz)
                             : bwd_fused_blocks(d, nnz, g.vlist != nullptr, g.cpl | g.cpl_from << 8);
     if (count_live) {

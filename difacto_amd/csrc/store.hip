@@ -159,14 +159,15 @@ __global__ __launch_bounds__(kStNT) void k_push_grad(int64_t n, const uint64_t* 
         } else {
           // (fp16 Vaux: the store narrows by vaux16_round — g is adagrad_update's, e.y the new
           // sqrt_g of this key's UpdateW above; eta and V use the unrounded accumulator)
-          // (half rows: V narrows by vhalf_round too, as the fused backward does)
+          // (half rows, and line slots at d = 24: V narrows by vhalf_round too, as the fused
+          // backward does)
+          const bool hv = T.half || T.line == 3;
           for (int k = 0; k < d; ++k) {
             float cg = vaux_get(T, vr, k), v = v_get(T, vr, k);
             const float g = vals[o + 1 + k] + P.V_l2 * v;
             adagrad_update(P, vals[o + 1 + k], &v, &cg);
-            v_put(T, vr, k, T.half ? f16_widen(vhalf_round(v, g, e.y, k)) : v);
-            vaux_put(T, vr, k,
-                     T.line == 2 || T.half ? f16_widen(vaux16_round(cg, g, e.y, k)) : cg);
+            v_put(T, vr, k, hv ? f16_widen(vhalf_round(v, g, e.y, k)) : v);
+            vaux_put(T, vr, k, T.line == 2 || hv ? f16_widen(vaux16_round(cg, g, e.y, k)) : cg);
           }
         }
       }
@@ -633,10 +634,9 @@ __global__ void k_load(int64_t n, const uint64_t* keys, const float4* st, const 
       ent_set_state(en, e);
       if (vr[i] >= 0 && T.es) {
         const float* src = VV + (vr[i] - vbase) * 2 * (int64_t)T.d;
-        float* V = row_V(T, s);
-        for (int k = 0; k < T.d; ++k) {
-          V[k] = src[k];
-          vaux_put(T, s, k, src[T.d + k]);  // (fp16 Vaux: the file's fp32, to the nearest)
+        for (int k = 0; k < T.d; ++k) {  // (fp16 V / Vaux: the file's fp32, to the nearest)
+          v_put(T, s, k, src[k]);
+          vaux_put(T, s, k, src[T.d + k]);
         }
         en->vrow = (int32_t)s;
       } else if (vr[i] >= 0) {
@@ -712,7 +712,8 @@ static int for_each_entry(Context* c, int64_t s0, int64_t ns, std::vector<float>
   if (T.es) {
     std::vector<Entry> raw((size_t)std::min<int64_t>(ns, kHostChunk) << T.es);
     // (line slots: Vaux came with the slot, behind V; fp16 Vaux is widened into aux's one row)
-    std::vector<float> aux(T.line ? d : (size_t)std::min<int64_t>(ns, kHostChunk) * d);
+    // (d = 24, fp16 V too: both widened, aux's row is [V | Vaux])
+    std::vector<float> aux(T.line ? 2 * d : (size_t)std::min<int64_t>(ns, kHostChunk) * d);
     for (int64_t i0 = s0; i0 < s0 + ns; i0 += kHostChunk) {
       const int64_t n = std::min<int64_t>(kHostChunk, s0 + ns - i0);
       DFX_HIP(hipMemcpy(raw.data(), ent_at(T, i0), ((size_t)n << T.es) * sizeof(Entry),
@@ -728,6 +729,13 @@ static int for_each_entry(Context* c, int64_t s0, int64_t ns, std::vector<float>
           uint16_t h[16];
           memcpy(h, V + d, sizeof(h));
           for (int k = 0; k < d; ++k) aux[k] = f16_widen(h[k]);
+        }
+        if (v && T.line == 3) {
+          uint16_t h[48];
+          memcpy(h, V, sizeof(h));
+          for (int k = 0; k < 2 * d; ++k) aux[k] = f16_widen(h[k]);
+          fn(e, aux.data(), aux.data() + d);
+          continue;
         }
         fn(e, v ? V : nullptr,
            v ? (T.line == 1 ? V + d : T.line ? aux.data() : aux.data() + (size_t)i * d) : nullptr);
@@ -967,6 +975,10 @@ int dfx_store_entry(dfx_ctx* ctx, uint64_t key, float* state, float* V, int* has
       if (e.vrow >= 0 && V && T.half) {  // a half row, widened
         uint16_t h[256];  // (d <= 128)
         DFX_HIP(hipMemcpy(h, half_row(T, e.vrow), 4 * T.d, hipMemcpyDeviceToHost));
+        for (int k = 0; k < 2 * T.d; ++k) V[k] = f16_widen(h[k]);
+      } else if (e.vrow >= 0 && V && T.line == 3) {  // the slot's 48 halves, widened
+        uint16_t h[48];
+        DFX_HIP(hipMemcpy(h, line24_row(T, e.vrow), sizeof(h), hipMemcpyDeviceToHost));
         for (int k = 0; k < 2 * T.d; ++k) V[k] = f16_widen(h[k]);
       } else if (e.vrow >= 0 && V) {
         DFX_HIP(hipMemcpy(V, row_V(T, e.vrow), T.d * 4, hipMemcpyDeviceToHost));

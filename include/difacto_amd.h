@@ -108,7 +108,10 @@ typedef struct dfx_progress {
  * of its own for the fused step (csrc/fm_half.hip); the single-GPU context only: dfx_dist_* and
  * dfx_split_* calls return DFX_ERR_ARG; model files hold fp32, narrowed to the nearest fp16 on
  * load, by the host loop: dfx_store_save_dev, dfx_store_dump_dev and dfx_store_load_dev return
- * DFX_ERR_ARG on such a context); the
+ * DFX_ERR_ARG on such a context; and f16 with slot_layout=line at V_dim 24, loss=fm, without
+ * vaux=f16 — the one line shape: [Entry 32 B | V: 24 fp16 | Vaux: 24 fp16], a key's whole state in
+ * one 128-byte line and no pool, with the same widening, arithmetic, rounds and limits, and
+ * kernels of its own (csrc/fm_line.hip)); the
  * sharded store's push_agg=sum|ranks and hash=ordered|mixed; and execution choices that do
  * not change results (A/B switches, measured in DESIGN.md): fwd_probe, xvp_row, bwd_lds,
  * sort_pack, sort_items, sort_lookback, auc_sort=radix|merge|bucket|wbucket, fat_fwd, fat_bwd,
